@@ -7,17 +7,27 @@
 One "step" = one matcher pass (matching_ncc_dlc_2, MIMC_module.c:805-842) over one batch of synthetic grid points.
 Workload at N=1 = BASELINE configs[1] (C2): 4096x4096 synthetic pair, 200,000 grid points (500x400), ocw 16 (33x33 chip),
 ~15 DLC pivots (65x65 window).  Inputs (both images, xyuvav, pivot CSR) are resident in HBM before the timed region:
-`value` is the kernel-only rate; `value_incl_io` is SURVEY 8(d)(i)'s figure with the pivot/xyuvav upload and the result
-download inside every step.
+`value` is the kernel-only rate; `value_incl_io` (--full) is SURVEY 8(d)(i)'s figure with the pivot/xyuvav upload and the
+result download inside every step.
 
 At N>1 (one rank per GPU, torch.distributed, backend nccl = RCCL) the headline is BASELINE configs[2] (C3): the SAME
 200,000 points sharded over the ranks in cost-balanced blocks (strong scaling), every step = the rank's share + ONE
 all-gather of the padded (du,dv,ncc) blocks + the re-ordering to grid order.  The weak-scaling figure (every rank matches
-its own 200,000-point lattice) is reported next to it in `weak`.
+its own 200,000-point lattice) is reported next to it in `weak` (--full).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and, at N=1, `cpu_baseline` (the compiled
-reference OpenMP path when oracle/_ref travelled here, else the parity-verified C restatement), a parity figure against
-it, and `f32_path` (the same workload forced onto the tiled f32 kernel, what 16-bit imagery gets).
+Prints ONE JSON line on rank 0 with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of one
+timed step) and `roofline`.  A plain run does only that: set-up, W warm-up steps, the K timed steps, the line.
+
+--full adds the secondary figures, each of which takes runs of its own: at N=1 `incl_io`, `cpu_baseline` (the compiled
+reference OpenMP path when oracle/_ref is present, else the parity-verified C restatement) with a parity figure against
+it, `f32_path` (the same workload forced onto the tiled f32 kernel, what 16-bit imagery gets), `kernels`, `qm` and
+`program`; at N>1 the scaling figure that is not the headline (`strong` or `weak`) and `qm`.  The --no-* options and
+--qm-sweeps / --cpu-sample shape the --full run.
+
+--dump-outputs DIR writes what the timed path returned in its last step to DIR/match.npy (float32 [points][3]: du, dv,
+ncc, in grid order; at N>1 with --scaling weak, rank r's lattice is the r-th block of rows; above 64 MB a fixed seeded
+sample of rows, whose indices go to DIR/match_rows.npy as float64).
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -35,6 +45,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md, Chip-leve
 KERNEL_NAMES = {"u8_mfma": "match_ncc_dlc_mx", "u8_exact": "match_ncc_dlc_px<PxU8>", "f32_tiled": "match_ncc_dlc_px<PxF32i>",
                 "u16_scaled": "match_ncc_dlc_px<PxU16>", "u8_offset": "match_ncc_dlc_px<PxU8o>", "general_f32": "match_ncc_dlc_f32"}
 DTYPES = {"u8_mfma": "u8", "u8_exact": "u8", "u16_scaled": "u16", "u8_offset": "u8"}
+DUMP_LIMIT_BYTES = 64_000_000     # --dump-outputs: all files together, headers included
 
 
 def kernel_source_sha16():
@@ -105,6 +116,19 @@ def timed(torch, dist, world, dev, step, steps, warmup):
     return elapsed, kern_ms, per_rank
 
 
+def dump_outputs(dirname, name, arr):
+    """DIR/<name>.npy as float32; above DUMP_LIMIT_BYTES a fixed, seeded sample of rows (indices in DIR/<name>_rows.npy, float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(arr, np.float32)
+    row_bytes = a.nbytes // max(a.shape[0], 1)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)         # rows + their float64 indices, room for two headers
+        rows = np.sort(np.random.default_rng(20260101).choice(a.shape[0], keep, replace=False))
+        np.save(os.path.join(dirname, f"{name}_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -115,20 +139,27 @@ def main():
                     help="auto: exact u8 kernel when the pair is 8-bit integral; f32: the register-tiled f32 kernel "
                          "(what 16-bit / filtered imagery gets); general: force the fallback f32 kernel")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
-                    help="which figure is the headline `value` at N>1 (the other one is reported too): strong = the config's "
+                    help="which figure is the headline `value` at N>1 (--full reports the other one too): strong = the config's "
                          "points sharded across the ranks (BASELINE configs[2], default); weak = every rank matches its own "
                          "lattice of the config's size")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, default). gloo + MIMC3_BENCH_ONE_DEVICE=1 rehearses the N>1 path on a 1-GPU box")
     ap.add_argument("--qm-sweeps", type=int, default=10,
-                    help="also time the QM pseudo-smoothing update (BASELINE configs[4]: 10 sweeps fused on device); 0 = skip")
+                    help="with --full, also time the QM pseudo-smoothing update (BASELINE configs[4]: 10 sweeps fused on device); 0 = skip")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-program", action="store_true",
                     help="skip the extra `program` object (the reference program's whole data path, mimc3_vmap, once)")
     ap.add_argument("--no-f32-path", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the secondary legs (register-tiled kernel alone, null-free pair, the program's 32 passes)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="grid points for the CPU baseline (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures (io, CPU baseline + parity, f32 path, kernel legs, QM, program; at N>1 the "
+                         "other scaling figure); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's output of the last timed step to DIR/match.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from mimc3_amd import api, shard, synth   # raises if libmimc3_hip.so is missing: no CPU fallback
@@ -199,49 +230,57 @@ def main():
         alg_bytes = algorithmic_bytes(piv_off, piv_uv, case.ocw)
         n_job, n_rank0, scaling = n_all, n_all, "n/a"        # one rank: nothing scales
         got = leg.d_out.cpu().numpy()
+        dumped = got
         path = ctx.last_path()
     else:
-        # ---- strong: BASELINE configs[2], the config's points in cost-balanced shares
-        cost = api.point_cost(piv_off, case.ocw)
-        order, start, per, imb = shard.balanced_shares(cost, world)
-        mine = order[start[rank]:start[rank + 1]]
-        sxy, soff, suv = shard.gather_problem(xy_all, piv_off, piv_uv, mine)
-        leg_s = Leg(torch, api, dev, sxy, soff, suv, per)
+        # a plain run times the headline's scaling figure only; --full times both
         field = {}
-        to_grid = shard.Unpermute(order, start, per, dev)
+        if args.scaling == "strong" or args.full:
+            # ---- strong: BASELINE configs[2], the config's points in cost-balanced shares
+            cost = api.point_cost(piv_off, case.ocw)
+            order, start, per, imb = shard.balanced_shares(cost, world)
+            mine = order[start[rank]:start[rank + 1]]
+            sxy, soff, suv = shard.gather_problem(xy_all, piv_off, piv_uv, mine)
+            leg_s = Leg(torch, api, dev, sxy, soff, suv, per)
+            to_grid = shard.Unpermute(order, start, per, dev)
 
-        def gather_strong(leg):
-            g = shard.all_gather_blocks(leg.d_out, per, world)                 # the ONE exchange: [world][per][3]
-            field["full"] = to_grid(g)                                         # grid order, on every rank
+            def gather_strong(leg):
+                g = shard.all_gather_blocks(leg.d_out, per, world)                 # the ONE exchange: [world][per][3]
+                field["full"] = to_grid(g)                                         # grid order, on every rank
 
-        el_s, km_s, pr_s = timed(torch, dist, world, dev, make_step(leg_s, gather_strong), args.steps, args.warmup)
-        # ---- weak: every rank its own lattice of the config's size (lattice r shifted r px in x: an N-times denser grid)
-        xy_w = xy_all.copy()
-        xy_w[:, 2] += rank; xy_w[:, 0] += rank * case.mpp
-        woff, wuv = api.get_uv_pivot(xy_w, case.dt, case.mpp, case.ocw, H, W)
-        leg_w = Leg(torch, api, dev, xy_w, woff, wuv, n_all)
+            el_s, km_s, pr_s = timed(torch, dist, world, dev, make_step(leg_s, gather_strong), args.steps, args.warmup)
+            result["strong"] = {"value": n_all * args.steps / el_s, "ms_per_step": el_s / args.steps * 1e3, "kernel_ms_rank0": km_s,
+                                "grid_points_rank0": int(leg_s.n), "points_per_step": n_all, "work_imbalance": imb, "per_rank": pr_s,
+                                "what": f"{args.config}'s {n_all} points in cost-balanced shares of {shard.default_block(n_all, world)}-point blocks"}
+        if args.scaling == "weak" or args.full:
+            # ---- weak: every rank its own lattice of the config's size (lattice r shifted r px in x: an N-times denser grid)
+            xy_w = xy_all.copy()
+            xy_w[:, 2] += rank; xy_w[:, 0] += rank * case.mpp
+            woff, wuv = api.get_uv_pivot(xy_w, case.dt, case.mpp, case.ocw, H, W)
+            leg_w = Leg(torch, api, dev, xy_w, woff, wuv, n_all)
 
-        def gather_weak(leg):
-            field["weak"] = shard.all_gather_blocks(leg.d_out, n_all, world)
+            def gather_weak(leg):
+                field["weak"] = shard.all_gather_blocks(leg.d_out, n_all, world)
 
-        el_w, km_w, pr_w = timed(torch, dist, world, dev, make_step(leg_w, gather_weak), args.steps, args.warmup)
-        strong = {"value": n_all * args.steps / el_s, "ms_per_step": el_s / args.steps * 1e3, "kernel_ms_rank0": km_s,
-                  "grid_points_rank0": int(leg_s.n), "points_per_step": n_all, "work_imbalance": imb, "per_rank": pr_s,
-                  "what": f"{args.config}'s {n_all} points in cost-balanced shares of {shard.default_block(n_all, world)}-point blocks"}
-        weak = {"value": n_all * world * args.steps / el_w, "ms_per_step": el_w / args.steps * 1e3, "kernel_ms_rank0": km_w,
-                "grid_points_rank0": n_all, "points_per_step": n_all * world, "per_rank": pr_w,
-                "what": f"every rank its own {n_all}-point lattice (shifted r px), all-gather of [{world}][{n_all}][3]"}
-        result["strong"], result["weak"] = strong, weak
+            el_w, km_w, pr_w = timed(torch, dist, world, dev, make_step(leg_w, gather_weak), args.steps, args.warmup)
+            result["weak"] = {"value": n_all * world * args.steps / el_w, "ms_per_step": el_w / args.steps * 1e3, "kernel_ms_rank0": km_w,
+                              "grid_points_rank0": n_all, "points_per_step": n_all * world, "per_rank": pr_w,
+                              "what": f"every rank its own {n_all}-point lattice (shifted r px), all-gather of [{world}][{n_all}][3]"}
         if args.scaling == "strong":
             elapsed, kern_ms, n_job, n_rank0, scaling = el_s, km_s, n_all, leg_s.n, "strong"
             alg_bytes = algorithmic_bytes(soff, suv, case.ocw) if leg_s.n else 0
+            dumped = field["full"]
         else:
             elapsed, kern_ms, n_job, n_rank0, scaling = el_w, km_w, n_all * world, n_all, "weak"
             alg_bytes = algorithmic_bytes(woff, wuv, case.ocw)
-        got = field["full"].cpu().numpy()
+            dumped = field["weak"].reshape(-1, 3)                                  # [world][points][3]: rank r's lattice is block r
+        got = (field["full"] if "full" in field else dumped).cpu().numpy()
+        dumped = dumped.cpu().numpy()
         path = ctx.last_path()
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, "match", dumped)
         value = n_job * args.steps / elapsed
         achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
         kname = KERNEL_NAMES.get(path, path)
@@ -300,7 +339,8 @@ def main():
         res["check"] = {"valid_frac": float(valid.mean()),
                         "median_du_dv": [float(np.nanmedian(got[:, 0])), float(np.nanmedian(got[:, 1]))],
                         "true_shift": list(case.shift)}
-        if world == 1:
+        res["full"] = args.full
+        if world == 1 and args.full:
             res["incl_io"] = io_leg(api, ctx, case, xy_all, piv_off, piv_uv, min(args.steps, 10), got)
             res["value_incl_io"] = res["incl_io"]["value"]
             cpu = None
@@ -312,9 +352,9 @@ def main():
             if not args.no_legs and args.path == "auto" and path == "u8_mfma":
                 res["kernels"] = kernel_legs(torch, dist, dev, api, synth, ctx, leg, make_step, piv_off, piv_uv, case, args, got)
                 ctx.set_path(args.path)
-        if args.qm_sweeps > 0:
+        if args.full and args.qm_sweeps > 0:
             res["qm"] = qm_leg(torch, api, synth, ctx, dev, case, args.qm_sweeps, check=(world == 1 and not args.no_cpu_baseline))
-        if world == 1 and not args.no_program:
+        if world == 1 and args.full and not args.no_program:
             res["program"] = program_leg(api, ctx, xy_all)
             if not args.no_legs:
                 res["program"]["passes"] = passes_leg(torch, api, ctx, dev, case, xy_all)

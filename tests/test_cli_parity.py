@@ -75,6 +75,14 @@ def test_cli_vs_program_live_16bit(cli, tmp_path):
 HYBRID = os.path.join(ROOT, "oracle", "_ref", "MIMC3_main_on_hip")
 
 
+def hybrid_env(**extra):
+    """oracle/_ref may have been linked in another checkout of the tree (it is built only where the reference sources are),
+    so the library path recorded in the binary need not lead here: the loader is pointed at THIS tree's libmimc3_hip.so."""
+    lib = os.path.join(ROOT, "mimc3_amd", "csrc")
+    ld = os.environ.get("LD_LIBRARY_PATH")
+    return dict(os.environ, LD_LIBRARY_PATH=lib + (os.pathsep + ld if ld else ""), **extra)
+
+
 @pytest.mark.skipif(not (os.path.exists(PROG) and os.path.exists(HYBRID)), reason="oracle/_ref programs did not travel to this box")
 def test_reference_main_on_the_shim_vs_reference_program(tmp_path):
     """INTEGRATION.md option A taken to the end: the reference's OWN main() + GMA.c + MIMC_misc.c linked against
@@ -91,7 +99,7 @@ def test_reference_main_on_the_shim_vs_reference_program(tmp_path):
     a = write_inputs(str(tmp_path / "a"), i0, i1, xy, t0, t1)
     b = write_inputs(str(tmp_path / "b"), i0, i1, xy, t0, t1)
     subprocess.run([PROG] + a, check=True, env=dict(os.environ, MIMC3_REF_SEED="9"), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    p = subprocess.run([HYBRID] + b, env=dict(os.environ, MIMC3_CP_SEED="9"), capture_output=True, text=True)
+    p = subprocess.run([HYBRID] + b, env=hybrid_env(MIMC3_CP_SEED="9"), capture_output=True, text=True)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     for k in OUTS:
         name = f"vmap_{t0}_{t1}_{k}.GMA"
