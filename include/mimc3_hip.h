@@ -38,6 +38,8 @@ extern "C" {
 #define MIMC3_ECAP     (-3)  /* caller-provided output capacity too small                        */
 #define MIMC3_ENODEV   (-4)  /* no usable HIP device                                             */
 #define MIMC3_ESTATE   (-5)  /* context in the wrong state (e.g. images not set)                 */
+#define MIMC3_EUNSUPPORTED (-6)  /* input kind the entry point does not handle (yet), e.g. a pair that
+                                is not 8-bit for mimc3_match_ncc_full                             */
 
 typedef struct mimc3_ctx mimc3_ctx;   /* opaque: device id, stream, resident images, workspaces */
 
@@ -73,7 +75,9 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *   5 = the matrix-core form of kernel 1 (dense correlation surfaces on v_mfma_i32_16x16x64_i8), taken first for the
  *       chip sizes it is built for; the points it does not take (null pixels in the window or chip, corridors wider than
  *       its 32 x 32 cell tile, ...) are flagged and done by kernel 1 right behind;
- *   0 = general f32 kernel (any ocw, any window size) otherwise.
+ *   0 = general f32 kernel (any ocw, any window size) otherwise;
+ *   6 = the exhaustive search (mimc3_match_ncc_full): the matrix-core kernel's surfaces, every point on the matrix cores
+ *       (it does not depend on the mode).
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -108,6 +112,51 @@ int mimc3_match_ncc_dlc_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, i
                             float *d_out, void *stream);
 int mimc3_pivot_extent(const int32_t *piv_uv, const int64_t *piv_off, int32_t N,
                        int32_t *max_npiv, int32_t *max_abs_u, int32_t *max_abs_v);
+
+/* ---- Exhaustive-search NCC offsets with peak quality (no reference counterpart: the complement of the DLC matcher that
+ *      find_ncc_peak's TODOs ask for, MIMC_module.c:649,790, and the AMPCOR-style record MIMC_single_match.c:1-27 promises).
+ *
+ *   Inputs, for grid point i:
+ *     uv0 = ((int)xyuvav[i][2], (int)xyuvav[i][3]);
+ *     chip: (2 ocw + 1)^2 pixels of i0 centred at uv0, as extract_refchip cuts it (:845-855);
+ *     search centre c = uv0 + offset + shift[i], shift an optional int32 [N][2] (NULL = zero);
+ *     integer offsets s = (su, sv) in [-R, R]^2, 1 <= R <= 15;
+ *     swap = 1 exchanges the roles of i0 and i1, as in the DLC entry.
+ *   Per-cell NCC(s): the reference's cell formula (:719-734) -- null exclusion at MIN_DN, f64, no contraction, cast to f32 --
+ *     of the chip with the box of i1 centred at c + s.  Box pixels outside the image are 0, i.e. nulls.  Unlike the DLC window
+ *     there is no never-written last row or column: the box is the plane itself.
+ *   Per-point outcome:
+ *     validity  investigate_valid_grid's rule (:605-644, f32 ratios, > 0.8) on the chip and on the whole (2R + 2 ocw + 1)^2
+ *               search box; if either fails the status is -3;
+ *     peak      the largest finite NCC(s); on ties the lowest k = (su + R)(2R + 1) + (sv + R) wins (u outer, v inner, as the
+ *               reference's 3x3 scan); NaN never wins; no finite cell: status -2;
+ *     border    |su| = R or |sv| = R at the peak: status -4 (no fit);
+ *     fit       otherwise the reference's 3x3 quadratic fit (:757-788) with its float/double mix, exactly:
+ *               c0..c5 = (f32 expressions of the 9 cells) / 36 in f64 (c5 = (-4 n0 + 8 n1 - 4 n2 + 8 n3 + 20 n4 + 8 n5 - 4 n6
+ *               + 8 n7 - 4 n8) / 36, the constant of the same fit), du' = (float)((double)(float)(-2 c2 c3 + c1 c4) / det),
+ *               det = 4 c0 c2 - c1^2, dv' likewise with (-2 c0 c4 + c1 c3).
+ *   Output, f32 [N][8] per point:
+ *     0, 1  du, dv = du' + (float)(su + shift_u), dv' + (float)(sv + shift_v): the displacement relative to uv0 + offset, like
+ *           columns 0 and 1 of the DLC matcher.  NaN when the status is negative.
+ *     2     ncc_peak: the peak cell's f32 NCC, or the status -2 / -3 / -4
+ *     3     ncc_fit: the fitted quadratic's value at its extremum (f64: x* = (-2 c2 c3 + c1 c4) / det, y* = (-2 c0 c4 + c1 c3) / det,
+ *           c0 x*^2 + c1 x* y* + c2 y*^2 + c3 x* + c4 y* + c5), stored as f32
+ *     4     snr: ncc_peak^2 / mean(NCC^2) over the finite cells outside the 3x3 block around the peak (f64, stored as f32; NaN if
+ *           there are none)
+ *     5-7   the fit's Hessian 2 c0, c1, 2 c2 (h_uu, h_uv, h_vv): the peak-sharpness input of a covariance
+ *     Columns 3-7 are NaN when the status is negative.
+ *   Refusals: ocw outside {7, 15, 16, 30, 32, 40} or R outside 1..15: MIMC3_EINVAL; a chip that leaves the image, or a search box
+ *   beyond the planes' 256-px zero border: MIMC3_EBOUNDS; a pair that did not classify as 8-bit (u8 planes): MIMC3_EUNSUPPORTED.
+ *   mimc3_ctx_last_path reports 6. */
+int mimc3_match_ncc_full(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                         const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t swap, float *out /*[N][8] host*/);
+/* Device-resident variant: d_xyuvav [N][6], d_shift [N][2] or NULL, d_out [N][8] device pointers; enqueues on `stream`, no sync.
+ * The caller guarantees the bounds the host entry checks (a point that breaks them gets an all-NaN record and no read). */
+int mimc3_match_ncc_full_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                             const int32_t *d_shift, int32_t ocw, int32_t R, int32_t swap, float *d_out, void *stream);
+/* Host helper: the a-priori displacement as whole pixels, get_uv_pivot's sign convention (:559-598):
+ *   shift[i] = (floor(vx dt / 365 / mpp + 0.5), floor(-vy dt / 365 / mpp + 0.5))   (f64, vx = xyuvav[i][4], vy = xyuvav[i][5]) */
+int mimc3_prior_shift(const double *xyuvav, int32_t N, float dt, float mpp, int32_t *shift /*[N][2]*/);
 
 /* ---- a2 on the device.  get_uv_pivot has two halves: the CORRIDOR of a point (theta = atan2(vy, vx), the normalised step,
  *      the corridor length, MIMC_module.c:559-573) needs libm and is computed on the host, bit-equal to the reference's;

@@ -48,6 +48,9 @@ _lib.mimc3_get_uv_pivot.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, C.c_
 _lib.mimc3_match_ncc_dlc.argtypes = [_vp, _f64p, C.c_int32, _i32p, _i32p, _i64p, C.c_int32, C.c_int32, _f32p]
 _lib.mimc3_match_ncc_dlc_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
+_lib.mimc3_match_ncc_full.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, _f32p]
+_lib.mimc3_match_ncc_full_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
+_lib.mimc3_prior_shift.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, _i32p]
 _lib.mimc3_pivot_corridors.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _vp]
 _lib.mimc3_get_uv_pivot_dev.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _vp]
 _lib.mimc3_match_ncc_dlc_geo.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _f32p]
@@ -189,6 +192,15 @@ def get_uv_pivot_counts(xyuvav, dt, mpp, ocw, H, W, aw_sf=1.8, aw_cre=10.0):
 
 
 CORRIDOR_BYTES = 24      # MIMC3_CORRIDOR_BYTES
+
+
+def prior_shift(xyuvav, dt, mpp):
+    """The a-priori displacement in whole pixels, get_uv_pivot's sign convention -> int32[N][2]:
+    (floor(vx dt / 365 / mpp + 0.5), floor(-vy dt / 365 / mpp + 0.5)) -- the search centres of match_ncc_full."""
+    xy = np.ascontiguousarray(xyuvav, np.float64)
+    out = np.empty((xy.shape[0], 2), np.int32)
+    _check(_lib.mimc3_prior_shift(xy, xy.shape[0], dt, mpp, out), "prior_shift")
+    return out
 
 
 def pivot_corridors(xyuvav, dt, mpp, aw_sf=1.8, aw_cre=10.0):
@@ -422,6 +434,28 @@ class Context:
         _check(_lib.mimc3_match_ncc_dlc_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_piv_uv, d_piv_off,
                                             mn, mu, mv, ocw, 1 if swap else 0, d_out, stream), "matching_ncc_dlc_2_dev")
 
+    # -- exhaustive search ----------------------------------------------------------------------
+    def match_ncc_full(self, xyuvav, offset, ocw, radius, shift=None, swap=False):
+        """Exhaustive-search NCC offsets with peak quality (mimc3_match_ncc_full) on the resident 8-bit pair -> float32[N][8]:
+        du, dv, ncc_peak (or the status -2 / -3 / -4), ncc_fit, snr, h_uu, h_uv, h_vv.  Every offset in [-radius, radius]^2
+        around uv0 + offset + shift[i] (shift int32[N][2] or None)."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        out = np.empty((n, 8), np.float32)
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_full: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_full(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
+                                         None if sh is None else sh.ctypes.data, ocw, radius, 1 if swap else 0, out), "match_ncc_full")
+        return out
+
+    def match_ncc_full_dev(self, d_xyuvav, n, offset, ocw, radius, d_out, d_shift=0, stream=0, swap=False):
+        """Device-pointer variant (enqueue only): d_xyuvav [n][6] f64, d_shift [n][2] int32 or 0, d_out [n][8] f32."""
+        _check(_lib.mimc3_match_ncc_full_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                             1 if swap else 0, d_out, stream), "match_ncc_full_dev")
+
     # -- QM -----------------------------------------------------------------------------------
     def get_dpf_pseudosmoothing(self, dpf, dpf_dx, dpf_dy, ruv, mvn, nclus, xyuvav, max_sweeps=101):
         """get_dpf_pseudosmoothing (MIMC_module.c:1986-2312). Returns (dpf, dx, dy, sweeps); inputs untouched."""
@@ -653,7 +687,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

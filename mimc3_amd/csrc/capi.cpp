@@ -726,6 +726,92 @@ extern "C" int mimc3_match_ncc_dlc(mimc3_ctx *c, const double *xyuvav, int32_t N
 }
 
 // ---------------------------------------------------------------------------------------------
+// exhaustive-search NCC offsets with peak quality (match_mx_kernel.hip, full mode): every (2R+1)^2 cell of a point on the
+// matrix cores, 8-bit pairs only
+// ---------------------------------------------------------------------------------------------
+static bool full_ocw_ok(int32_t ocw) { return ocw == 7 || ocw == 15 || ocw == 16 || ocw == 30 || ocw == 32 || ocw == 40; }
+
+extern "C" int mimc3_match_ncc_full_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                        const int32_t *d_shift, int32_t ocw, int32_t R, int32_t swap, float *d_out, void *stream)
+{
+    if (!c || !d_xyuvav || !d_out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full_dev: bad argument");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full_dev: ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full_dev: R must be in 1..15");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_full_dev: images not set");
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_full_dev: not on a chip-atlas context");
+    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, "mimc3_match_ncc_full_dev: the pair is not 8-bit (u8 planes only)");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));         // (enqueued on the context's stream and drained before the kernels read them)
+    mimc3::MatchU8Args u{};
+    u.Wp = c->Wp; u.pad = mimc3::kU8Pad; u.H = c->H; u.W = c->W; u.thr = min_dn_threshold();
+    u.xyuvav = d_xyuvav; u.xy_stride = c->xy_stride; u.xy_col = c->xy_col; u.N = N; u.off_u = off_u; u.off_v = off_v;
+    u.full_shift = d_shift; u.full_R = R; u.ocw = ocw; u.swap = swap ? 1 : 0; u.out = d_out;
+    u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
+    u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
+    DevBuf &ml = c->mxl[c->lane];
+    HIP_TRY(ml.reserve((size_t)N));
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
+    u.mx_flags = static_cast<uint8_t *>(ml.p);
+    const hipError_t e = mimc3::launch_match_full_mx(u, s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "full-search kernel launch");
+    c->last_path = 6;
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_full(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                    int32_t ocw, int32_t R, int32_t swap, float *out)
+{
+    if (!c || !xyuvav || !offset || !out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full: bad argument");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full: ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full: R must be in 1..15");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_full: images not set");
+    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, "mimc3_match_ncc_full: the pair is not 8-bit (u8 planes only)");
+    // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
+    const int64_t pad = mimc3::kU8Pad;
+    for (int32_t g = 0; g < N; ++g) {
+        const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
+        if (u0 - ocw < 0 || u0 + ocw >= c->W || v0 - ocw < 0 || v0 + ocw >= c->H)
+            return mimc3::fail(MIMC3_EBOUNDS, "mimc3_match_ncc_full: grid point " + std::to_string(g) + " chip leaves the image");
+        const int64_t cu = (int64_t)u0 + offset[0] + (shift ? shift[2 * (size_t)g] : 0), cv = (int64_t)v0 + offset[1] + (shift ? shift[2 * (size_t)g + 1] : 0);
+        const int64_t h = R + ocw;
+        if (cu - h < -pad || cu + h >= c->W + pad || cv - h < -pad || cv + h >= c->H + pad)
+            return mimc3::fail(MIMC3_EBOUNDS, "mimc3_match_ncc_full: grid point " + std::to_string(g) + " search box leaves the zero border");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
+    HIP_TRY(c->out.reserve(sizeof(float) * 8 * (size_t)N));
+    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
+    const int32_t *d_shift = nullptr;
+    if (shift) {
+        HIP_TRY(c->puv.reserve(sizeof(int32_t) * 2 * (size_t)N));
+        RC_TRY(h2d_copy(c, c->puv.p, shift, sizeof(int32_t) * 2 * (size_t)N));
+        d_shift = static_cast<const int32_t *>(c->puv.p);
+    }
+    const int rc = mimc3_match_ncc_full_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, swap,
+                                            static_cast<float *>(c->out.p), c->stream);
+    if (rc) return rc;
+    return d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N);
+}
+
+// the a-priori displacement in pixels (get_uv_pivot's sign convention, :559-598), rounded to the nearest integer
+extern "C" int mimc3_prior_shift(const double *xyuvav, int32_t N, float dt, float mpp, int32_t *shift)
+{
+    if (!xyuvav || !shift || N <= 0 || !(mpp > 0.0f)) return mimc3::fail(MIMC3_EINVAL, "mimc3_prior_shift: bad argument");
+    for (int32_t g = 0; g < N; ++g) {
+        const double vx = xyuvav[6 * (size_t)g + 4], vy = xyuvav[6 * (size_t)g + 5];
+        const double du = vx * (double)dt / 365.0 / (double)mpp, dv = -vy * (double)dt / 365.0 / (double)mpp;
+        if (!std::isfinite(du) || !std::isfinite(dv) || std::fabs(du) > 1e9 || std::fabs(dv) > 1e9)
+            return mimc3::fail(MIMC3_EINVAL, "mimc3_prior_shift: grid point " + std::to_string(g) + " has no finite a-priori displacement");
+        shift[2 * (size_t)g] = (int32_t)std::floor(du + 0.5);
+        shift[2 * (size_t)g + 1] = (int32_t)std::floor(dv + 0.5);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // a2 on the device: pivot lists expanded from per-point corridors (pivot_kernel.hip)
 // ---------------------------------------------------------------------------------------------
 static_assert(sizeof(mimc3::CorridorPOD) == sizeof(mimc3::CorridorDev) && offsetof(mimc3::CorridorPOD, length) == offsetof(mimc3::CorridorDev, length),

@@ -1,0 +1,97 @@
+// MIMC3_hip_offsets -- exhaustive-search NCC offsets with peak quality over libmimc3_hip.so (MI355X): the AMPCOR-style table that
+// MIMC_single_match.c:1-27 describes.
+//
+//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15]
+//
+// Inputs as for MIMC3_hip (the file names start with YYYYMMDDhhmmss; dt from the two timestamps); both images 8-bit.  Steps: the
+// control-point offset (mimc3_vmap_cp, as the reference program measures it), the a-priori shift of every grid point
+// (mimc3_prior_shift), then every offset in [-R, R]^2 around uv0 + offset + shift (mimc3_match_ncc_full).  Outputs in <outdir>:
+//   offsets_<t0>_<t1>.GMA  f32 [N][10]: the [N][8] record of mimc3_match_ncc_full (du, dv, ncc_peak / status, ncc_fit, snr, h_uu,
+//                          h_uv, h_vv) and u, v of the grid point
+//   offsets_<t0>_<t1>.txt  the points with a non-negative status, one per line, AMPCOR's column order: u du v dv snr h_uu h_vv h_uv;
+//                          du, dv there are the whole displacement (the control-point offset added); a first comment line names
+//                          the columns and the offset
+// Environment: MIMC3_HIP_DEVICE (default 0), MIMC3_CP_SEED (as for MIMC3_hip).
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+#include <unistd.h>
+#include "../../../include/mimc3_hip.h"
+
+#include "cli_io.h"
+
+int main(int argc, char *argv[])
+{
+    printf("MIMC3_hip_offsets -- MI355X build (%s)\n", mimc3_version());
+    if (argc < 5 || argc > 7) {
+        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15]\n", argv[0]);
+        return 2;
+    }
+    const int32_t ocw = argc > 5 ? atoi(argv[5]) : 15, R = argc > 6 ? atoi(argv[6]) : 15;
+    char t0[15], t1[15];
+    if (!timestamp_of(argv[1], t0) || !timestamp_of(argv[2], t1)) {
+        fprintf(stderr, "image paths must contain a '/' and the file names must start with YYYYMMDDhhmmss\n");
+        return 2;
+    }
+    const float dt = (float)(datenum(t1) - datenum(t0));
+    const std::string base = std::string(argv[4]) + "/offsets_" + t0 + "_" + t1;
+    std::vector<double> xy;
+    int32_t N = 0, ncol = 0;
+    if (!load_gma_double(argv[3], xy, N, ncol) || ncol != 6) { fprintf(stderr, "cannot read %s as an [N][6] float64 .GMA\n", argv[3]); return 2; }
+    RawImage i0, i1;
+    if (!load_tiff(argv[1], i0) || !load_tiff(argv[2], i1)) { fprintf(stderr, "cannot read the TIFF images\n"); return 2; }
+    if (i0.H != i1.H || i0.W != i1.W) { fprintf(stderr, "the two images differ in size\n"); return 2; }
+    if (i0.bpp != 1 || i1.bpp != 1) { fprintf(stderr, "the exhaustive search takes 8-bit images only\n"); return 2; }
+    const char *dev = getenv("MIMC3_HIP_DEVICE");
+    mimc3_ctx *ctx = nullptr;
+    auto leave = [&](int code) -> int {        // (as MIMC3_hip: no runtime teardown on the way out)
+        fflush(nullptr);
+        _exit(code);
+    };
+    if (mimc3_ctx_create(dev ? atoi(dev) : 0, &ctx) || mimc3_ctx_set_images_u8(ctx, i0.px.data(), i1.px.data(), i0.H, i0.W)) {
+        fprintf(stderr, "%s\n", mimc3_last_error());
+        return leave(3);
+    }
+    // the control-point offset, as the reference program measures it (MIMC_main.c:240-256)
+    const mimc3_vmap_params p = reference_vmap_params();
+    std::vector<uint8_t> flag(N);
+    mimc3_vmap_result r{};
+    if (mimc3_vmap_cp(ctx, xy.data(), N, dt, &p, flag.data(), &r)) { fprintf(stderr, "%s\n", mimc3_last_error()); return leave(3); }
+    int32_t offset[2] = {0, 0};
+    if (r.cp_status < 0) printf("Not enough control points: searching around the a-priori displacement alone\n");
+    else { offset[0] = r.offset_cp[0]; offset[1] = r.offset_cp[1]; }
+    printf("dt=%f days, MPP=%f; control-point offset [%d, %d] pixels (i1-i0); ocw=%d, R=%d, %d grid points\n", dt, r.mpp, offset[0],
+           offset[1], ocw, R, N);
+    std::vector<int32_t> shift(2 * (size_t)N);
+    std::vector<float> rec(8 * (size_t)N);
+    if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
+        mimc3_match_ncc_full(ctx, xy.data(), N, offset, shift.data(), ocw, R, 0, rec.data())) {
+        fprintf(stderr, "%s\n", mimc3_last_error());
+        return leave(3);
+    }
+    std::vector<float> out(10 * (size_t)N);
+    int32_t nok = 0;
+    for (int32_t g = 0; g < N; g++) {
+        for (int k = 0; k < 8; k++) out[10 * (size_t)g + k] = rec[8 * (size_t)g + k];
+        out[10 * (size_t)g + 8] = (float)xy[6 * (size_t)g + 2];
+        out[10 * (size_t)g + 9] = (float)xy[6 * (size_t)g + 3];
+        nok += rec[8 * (size_t)g + 2] >= -1.0f;
+    }
+    bool ok = save_gma(base + ".GMA", out.data(), N, 10);
+    FILE *f = fopen((base + ".txt").c_str(), "w");
+    if (f) {
+        fprintf(f, "# u du v dv snr h_uu h_vv h_uv   (du, dv include the control-point offset %d %d)\n", offset[0], offset[1]);
+        for (int32_t g = 0; g < N; g++) {
+            const float *q = rec.data() + 8 * (size_t)g;
+            if (!(q[2] >= -1.0f)) continue;
+            fprintf(f, "%d %.4f %d %.4f %.5f %.6g %.6g %.6g\n", (int)xy[6 * (size_t)g + 2], q[0] + (float)offset[0], (int)xy[6 * (size_t)g + 3],
+                    q[1] + (float)offset[1], q[4], q[5], q[7], q[6]);
+        }
+        ok = fclose(f) == 0 && ok;
+    } else ok = false;
+    if (!ok) { fprintf(stderr, "could not write the outputs under %s\n", argv[4]); return leave(4); }
+    printf("%d of %d grid points with a peak; written %s.GMA and %s.txt\n", nok, N, base.c_str(), base.c_str());
+    return leave(0);
+}

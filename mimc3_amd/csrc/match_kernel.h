@@ -48,10 +48,18 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     int32_t xy_stride, xy_col;      // see MatchArgs
     int32_t N;
     int32_t off_u, off_v;
-    const int32_t *piv_uv;
+    // (exhaustive search, launch_match_full_mx: cells s in [-full_R, full_R]^2 around uv0 + offset + full_shift[g], out [N][8]; its two
+    //  arguments share the slots of the DLC's pivots and search-area half-width, which it does not read)
+    union {
+        const int32_t *piv_uv;
+        const int32_t *full_shift;  // per-point int32 [N][2] (u, v), or null (zero)
+    };
     const int64_t *piv_off;
     int32_t ocw, swap;
-    int32_t win_half;               // 0: DLC window (|last pivot|+ocw+2, last row/column empty); > 0: full (2*win_half+1)^2 search area (CP stage)
+    union {
+        int32_t win_half;           // 0: DLC window (|last pivot|+ocw+2, last row/column empty); > 0: full (2*win_half+1)^2 search area (CP stage)
+        int32_t full_R;             // exhaustive search: 1..15
+    };
     float *out;
     int32_t *ovf_list, *ovf_count;  // points whose NCC cache overflowed: handed to the general kernel (list mode)
     const int32_t *point_list, *point_count;   // list mode: workgroup b handles point_list[b], b < *point_count (nullptr = all N points)
@@ -112,6 +120,10 @@ hipError_t launch_match_u8(MatchU8Args a, int max_abs_u, int max_abs_v, int max_
 // fits its tile and whose chip has no null, leaves the others in a.mx_rest_list for launch_match_u8 in list mode
 bool match_mx_supported(int ocw, int max_npiv, int win_half, int max_abs_u, int max_abs_v);
 hipError_t launch_match_mx(MatchU8Args a, hipStream_t stream);
+// exhaustive-search NCC offsets on the same surfaces (mimc3_match_ncc_full): every point on the matrix cores -- the clean form, then
+// the window-null and general forms over the points it flags (a.mx_flags: N bytes, zero before the call); a.full_R in 1..15,
+// a.ocw one of 7, 15, 16, 30, 32, 40; a.out [N][8]
+hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream);
 
 // max_abs_u/v: max over points of |last pivot| per axis; max_npiv: max pivots per point.
 hipError_t launch_match_f32(MatchArgs a, int max_abs_u, int max_abs_v, int max_npiv, hipStream_t stream);

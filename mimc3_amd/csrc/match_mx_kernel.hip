@@ -111,6 +111,14 @@ struct Cfg {
     static constexpr int MINW0 = GEN_ ? (CN_ ? 3 : 4) : 8;          // occupancy target, waves per SIMD (register budget) ...
     static constexpr int MINW1 = (WGS * NW) / 4 > 0 ? (WGS * NW) / 4 : 1;                   // ... never above what LDS admits anyway
     static constexpr int MINW = MINW0 < MINW1 ? MINW0 : MINW1;
+    static constexpr bool FULL = false;                 // the DLC matcher (true: FullCfg, the exhaustive search)
+};
+// Exhaustive search (mimc3_match_ncc_full): the same surface builder on the cell tile whose origin is c - R (the search centre
+// c = uv0 + offset + shift, 1 <= R <= 15: all (2R + 1)^2 cells in the tile), no never-written row / column (T4), and instead of the
+// climb, replay and fit the first-wins arg-max, the border / validity rule, the reference's fit, the SNR and the fit's Hessian
+template <int OCW_, bool GEN_, bool CN_>
+struct FullCfg : Cfg<OCW_, GEN_, CN_> {
+    static constexpr bool FULL = true;
 };
 
 // The constant band operands, one table per chip size (constant-initialised device data).  v_mfma_i32_16x16x64_i8: lane (n = lane & 15,
@@ -222,6 +230,84 @@ __device__ __forceinline__ uint32_t planes1(const v4i &R)
 #define MIMC3_MX_STATS_OUT                                                                     \
     if (p.stats && lane == 0) { _Pragma("unroll") for (int i_ = 0; i_ < 7; i_++) p.stats[kStatW * (size_t)blockIdx.x + i_] = t_ph[i_]; }
 
+// ---- full mode (FullCfg) ----------------------------------------------------------------------------------------------
+// a record without a fit: the status (-2 no finite cell, -3 invalid, -4 peak on the border) in column 2, NaN elsewhere
+__device__ __forceinline__ void full_store(float *o, float status)
+{
+    const float nanv = __builtin_nanf("");
+    o[0] = nanv; o[1] = nanv; o[2] = status;
+#pragma unroll
+    for (int i = 3; i < 8; i++) o[i] = nanv;
+}
+
+// The tail of the exhaustive search on wave 0, over the f32 surface val[y][x] (tile cell (x, y) = offset (x - R, y - R)):
+//   peak   first-wins arg-max over the finite cells in k = (su + R)(2R + 1) + (sv + R) (u outer): lane l scans k = l, l + 64, ...
+//          in ascending order (strict >: its first maximum), then the lanes (value, -k) lexicographically (argmax_row16, then
+//          across the rows);
+//   fit    the reference's 3x3 quadratic (:757-788) value by value, float / double mix as there (match_ncc_dlc_mx's fit), plus
+//          the model's value at its extremum (c5 the constant of the same least-squares fit) and its Hessian 2 c0, c1, 2 c2;
+//   snr    ncc_peak^2 / mean(NCC^2) over the finite cells outside the peak's 3x3 block (f64 partial sums per lane, then a tree).
+template <class C>
+__device__ __forceinline__ void full_tail(const MatchU8Args &p, const float *val, int gidx, int shu, int shv, int lane)
+{
+    constexpr int VP = C::VP;
+    const int R = p.full_R, S = 2 * R + 1, NC = S * S;
+    float *out = p.out + 8 * (size_t)gidx;
+    float bv = -__builtin_inff();
+    int bk = 0x7fffffff;
+    for (int k = lane; k < NC; k += 64) {
+        const int x = k / S, y = k - S * x;
+        const float v = val[y * VP + x];
+        if (__builtin_isfinite(v) && v > bv) { bv = v; bk = k; }
+    }
+    argmax_row16(bv, bk);
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bk, o, 64);
+        if (ov > bv || (ov == bv && oi < bk)) { bv = ov; bk = oi; }
+    }
+    bv = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bv)));
+    bk = __builtin_amdgcn_readfirstlane(bk);
+    if (bk == 0x7fffffff) { if (lane == 0) full_store(out, -2.0f); return; }
+    const int px = bk / S, py = bk - S * px, su = px - R, sv = py - R;
+    if (su == -R || su == R || sv == -R || sv == R) { if (lane == 0) full_store(out, -4.0f); return; }
+    double s2 = 0.0;
+    int cnt = 0;
+    for (int k = lane; k < NC; k += 64) {
+        const int x = k / S, y = k - S * x;
+        const float v = val[y * VP + x];
+        const bool near = x - px <= 1 && px - x <= 1 && y - py <= 1 && py - y <= 1;
+        if (__builtin_isfinite(v) && !near) { s2 += (double)v * (double)v; cnt++; }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { s2 += __shfl_xor(s2, o, 64); cnt += __shfl_xor(cnt, o, 64); }
+    if (lane != 0) return;
+    float n9[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) n9[3 * r + c] = val[(py - 1 + r) * VP + (px - 1 + c)];
+    const float e0 = 6 * n9[0] - 12 * n9[1] + 6 * n9[2] + 6 * n9[3] - 12 * n9[4] + 6 * n9[5] + 6 * n9[6] - 12 * n9[7] + 6 * n9[8];
+    const float e1 = 9 * n9[0] - 9 * n9[2] - 9 * n9[6] + 9 * n9[8];
+    const float e2 = 6 * n9[0] + 6 * n9[1] + 6 * n9[2] - 12 * n9[3] - 12 * n9[4] - 12 * n9[5] + 6 * n9[6] + 6 * n9[7] + 6 * n9[8];
+    const float e3 = -6 * n9[0] + 6 * n9[2] - 6 * n9[3] + 6 * n9[5] - 6 * n9[6] + 6 * n9[8];
+    const float e4 = -6 * n9[0] - 6 * n9[1] - 6 * n9[2] + 6 * n9[6] + 6 * n9[7] + 6 * n9[8];
+    const float e5 = -4 * n9[0] + 8 * n9[1] - 4 * n9[2] + 8 * n9[3] + 20 * n9[4] + 8 * n9[5] - 4 * n9[6] + 8 * n9[7] - 4 * n9[8];
+    double c0 = e0, c1 = e1, c2 = e2, c3 = e3, c4 = e4, c5 = e5;
+    c0 /= 36; c1 /= 36; c2 /= 36; c3 /= 36; c4 /= 36; c5 /= 36;
+    const float nu = (float)(-2 * c2 * c3 + c1 * c4), nv = (float)(-2 * c0 * c4 + c1 * c3);
+    const double det = 4 * c0 * c2 - c1 * c1;
+    float du = (float)((double)nu / det), dv = (float)((double)nv / det);
+    du += (float)(su + shu);
+    dv += (float)(sv + shv);
+    const double xs = (-2 * c2 * c3 + c1 * c4) / det, ys = (-2 * c0 * c4 + c1 * c3) / det;
+    const double fit = c0 * xs * xs + c1 * xs * ys + c2 * ys * ys + c3 * xs + c4 * ys + c5;
+    const double snr = cnt > 0 ? ((double)bv * (double)bv) / (s2 / (double)cnt) : (double)__builtin_nan("");
+    out[0] = du; out[1] = dv; out[2] = bv; out[3] = (float)fit; out[4] = (float)snr;
+    out[5] = (float)(2 * c0); out[6] = (float)c1; out[7] = (float)(2 * c2);
+}
+
 template <class C>
 __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p)
 {
@@ -258,8 +344,13 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     // ---- point header (as match_px_kernel.hip) ---------------------------------------------------------------------
     const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;
     const int u0 = (int)row[0], v0 = (int)row[1];
-    const int64_t pbeg = p.piv_off[gidx];
-    const int npiv = (int)(p.piv_off[gidx + 1] - pbeg);
+    // (full mode, a point that breaks the bounds mimc3_match_ncc_full refuses -- only the _dev entry can pass one: no read, all NaN)
+    if (C::FULL && (u0 - OCW < 0 || u0 + OCW >= p.W || v0 - OCW < 0 || v0 + OCW >= p.H)) {
+        if (tid == 0) full_store(p.out + 8 * (size_t)gidx, __builtin_nanf(""));
+        return;
+    }
+    const int64_t pbeg = C::FULL ? 0 : p.piv_off[gidx];
+    const int npiv = C::FULL ? 1 : (int)(p.piv_off[gidx + 1] - pbeg);
     const int32_t *pv_g = p.piv_uv + 2 * pbeg;
     // Everything the header needs from memory beyond (u, v) and the pivot range is issued together -- the last pivot, the twelve table
     // corners of the three chip-side queries (one per lane), the chip's corner pixel, this lane's pivot -- and only then waited for:
@@ -269,7 +360,9 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     typedef unsigned long long SatT;
     const SatT *sat_chip = reinterpret_cast<const SatT *>(p.swap ? p.sat1 : p.sat0);
     const SatT *sat_win = reinterpret_cast<const SatT *>(p.swap ? p.sat0 : p.sat1);
-    const int2 lastpv = *reinterpret_cast<const int2 *>(pv_g + 2 * (npiv - 1));
+    // (full mode: the point's shift in place of the last pivot)
+    const int2 lastpv = C::FULL ? (p.full_shift ? *reinterpret_cast<const int2 *>(p.full_shift + 2 * (size_t)gidx) : make_int2(0, 0))
+                                : *reinterpret_cast<const int2 *>(pv_g + 2 * (npiv - 1));
     SatT satv = 0;
     {   // lane 4 q + c: corner c of query q (0: the chip, 1: its last column, 2: its last row)
         const int q = (lane >> 2) & 3, c = lane & 3;
@@ -279,7 +372,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const uint32_t cornerv = chip_pl[(size_t)(cv0 + CW - 1) * Wp + cu0 + CW - 1];
     // the pivots (lane k of wave 0 = pivot k in the climbs): parked in LDS until the surface is there
     int2 pv_mine = make_int2(0, 0);
-    if (wave == 0 && lane < npiv && npiv <= 64) pv_mine = *reinterpret_cast<const int2 *>(pv_g + 2 * lane);
+    if (!C::FULL && wave == 0 && lane < npiv && npiv <= 64) pv_mine = *reinterpret_cast<const int2 *>(pv_g + 2 * lane);
     // ... and the first batch of the chip's pixels (aligned dwords of its rows; written to LDS once the tile is on its way)
     constexpr int CD = C::CD, CTASK = CW * CD, CNIT = (CTASK + NT - 1) / NT, CKB = CNIT < 5 ? CNIT : 5;
     const int csh = cu0 & 3;
@@ -297,13 +390,18 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     };
     chip_loads(0);
     const int lu = __builtin_amdgcn_readfirstlane(lastpv.x), lv = __builtin_amdgcn_readfirstlane(lastpv.y);
-    const int dx2 = (lu < 0 ? -lu : lu) + OCW + 2, dy2 = (lv < 0 ? -lv : lv) + OCW + 2;
+    // (full mode: the search box is the Dx2 x Dy2 window centred on c, i.e. dx2 = dy2 = R + OCW; the tile's cell s_t = s + R)
+    const int dx2 = C::FULL ? p.full_R + OCW : (lu < 0 ? -lu : lu) + OCW + 2, dy2 = C::FULL ? p.full_R + OCW : (lv < 0 ? -lv : lv) + OCW + 2;
     const int Dx2 = 2 * dx2 + 1, Dy2 = 2 * dy2 + 1;
     const int csx = Dx2 - 2 * OCW + 1, csy = Dy2 - 2 * OCW + 1;          // compact cells; a climb touches [1, cs - 2]
-    const int wu0 = u0 + p.off_u - dx2 + PAD, wv0 = v0 + p.off_v - dy2 + PAD;   // plane position of window pixel (0, 0)
+    const int wu0 = u0 + p.off_u - dx2 + PAD + (C::FULL ? lu : 0), wv0 = v0 + p.off_v - dy2 + PAD + (C::FULL ? lv : 0);   // plane position of window pixel (0, 0)
+    if (C::FULL && (wu0 < 0 || wv0 < 0 || wu0 + Dx2 > p.W + 2 * PAD || wv0 + Dy2 > p.H + 2 * PAD)) {
+        if (tid == 0) full_store(p.out + 8 * (size_t)gidx, __builtin_nanf(""));
+        return;
+    }
     // ---- what this kernel takes -----------------------------------------------------------------------------------
     // the tile: all reachable cells if they fit, else centred on the pivots' starts (a scan that leaves it hands the point on)
-    int tx0 = 1, ty0 = 1;
+    int tx0 = C::FULL ? 0 : 1, ty0 = C::FULL ? 0 : 1;
     bool fits = true;
     {
         const int c0x = dx2 - OCW, c1x = c0x + lu, c0y = dy2 - OCW, c1y = c0y + lv;
@@ -312,12 +410,16 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         if (csy - 2 > 32) { ty0 = min(max((loy + hiy) / 2 - 15, 1), csy - 2 - 31); fits = fits && loy - 1 >= ty0 && hiy + 1 <= ty0 + 31; }
     }
     // the null count of the window's written area (:869-886) and the first batch of the tile's pixels: issued now, read below
-    const int win_nulls_v = sat_nulls_u8(sat_win, p.sat_ws, wu0, wv0, 2 * dx2, 2 * dy2, lane);      // (exact for any window size)
+    const int win_nulls_v = sat_nulls_u8(sat_win, p.sat_ws, wu0, wv0, C::FULL ? Dx2 : 2 * dx2, C::FULL ? Dy2 : 2 * dy2, lane);      // (exact for any window size; full mode: the whole search box)
     constexpr int NSEG = C::SW / 16, TTASK = C::KW * NSEG;           // (tile rows >= KW and columns >= SW are only ever weighted 0: left as they are)
     constexpr int TNIT = (TTASK + NT - 1) / NT, TKB = TNIT < 4 ? TNIT : 4;
     const int tsh = (wu0 + tx0) & 3;
     const uint32_t *tgb = reinterpret_cast<const uint32_t *>(win_pl + (size_t)(wv0 + ty0) * Wp + (wu0 + tx0 - tsh));
     uint32_t td[TKB][5];
+    // (full mode: the tile reaches up to 31 - 2R rows and 50 - 2R columns past the search box, which may end at the plane's last row:
+    //  the loads are clamped to the plane; what a clamped load brings only reaches cells outside the search range)
+    const uint32_t tlim = C::FULL ? (uint32_t)(((size_t)(p.H + 2 * PAD) * (size_t)Wp - ((size_t)(wv0 + ty0) * Wp + (size_t)(wu0 + tx0 - tsh))) / 4 - 1) : 0u;
+    (void)tlim;
     auto tile_loads = [&](int it0) __attribute__((always_inline)) {
 #pragma unroll
         for (int k = 0; k < TKB; k++) {
@@ -326,7 +428,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
             const bool on = (it0 + k < TNIT) && t < TTASK;
             const uint32_t go = (uint32_t)(on ? y : 0) * (uint32_t)(Wp >> 2) + 4u * (uint32_t)(on ? q : 0);
 #pragma unroll
-            for (int j = 0; j < 5; j++) td[k][j] = tgb[go + (uint32_t)j];
+            for (int j = 0; j < 5; j++) td[k][j] = tgb[C::FULL ? min(go + (uint32_t)j, tlim) : go + (uint32_t)j];
         }
     };
     tile_loads(0);
@@ -352,7 +454,15 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const bool wn = GEN && win_nulls != 0, cn = C::CN && chip_nulls != 0;
 
     // ---- validity (a6, :605-644): nulls of the chip / of the whole Dy2 x Dx2 search area (its last row and column are never written: zeros)
-    {
+    if constexpr (C::FULL) {                                  // (the search box has no never-written row or column)
+        const float max_ratio = 0.8f;
+        const float rc = (float)chip_nulls / (float)NPX;
+        const float rw = (float)win_nulls / (float)(Dx2 * Dy2);
+        if (rc > max_ratio || rw > max_ratio) {
+            if (tid == 0) full_store(p.out + 8 * (size_t)gidx, -3.0f);
+            return;
+        }
+    } else {
         const float max_ratio = 0.8f;
         const float rc = (float)chip_nulls / (float)NPX;
         const float rw = (float)(win_nulls + Dx2 + Dy2 - 1) / (float)(Dx2 * Dy2);
@@ -399,7 +509,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     {
         // T4: the search area's last column and last row are never written (:869-886): nulls.  (What lies beyond them inside the tile
         // only reaches cells no climb can touch.)
-        const int zx = Dx2 - 1 - tx0, zy = Dy2 - 1 - ty0;
+        const int zx = C::FULL ? C::SW : Dx2 - 1 - tx0, zy = C::FULL ? C::KW : Dy2 - 1 - ty0;    // (full mode: none)
         if (zx < C::SW) for (int y = tid; y < C::KW; y += NT) { WT[y * PW + zx] = 0x80; if (C::ZPL && wn) smem[C::OFF_Z + y * PW + zx] = 0x80; }
         if (zy < C::KW) for (int x = tid; x < C::SW / 4; x += NT) {
             *reinterpret_cast<uint32_t *>(WT + zy * PW + 4 * x) = 0x80808080u;
@@ -690,8 +800,8 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         asm volatile("" : "+s"(cS), "+s"(cSS), "+s"(rS), "+s"(rSS), "+s"(SXo), "+s"(SXXo));
         // T4 in closed form unless the window's own nulls are correlated anyway (wn): the never-written column / row take the chip's
         // last column / row out of n, sx, sxx -- its non-null pixels, with a chip that holds nulls
-        const bool colT4 = !wn && cx == csx - 2;
-        const int rT4 = wn ? -1 : csy - 2 - ty0;            // tile row of the cells that reach the never-written last row
+        const bool colT4 = !C::FULL && !wn && cx == csx - 2;
+        const int rT4 = (C::FULL || wn) ? -1 : csy - 2 - ty0;            // tile row of the cells that reach the never-written last row
         const int Na = chip_nulls;
         const int cN = (int)(colQ >> kSatNullShift8), rN = (int)(rowQ >> kSatNullShift8), kN = corner == 0u ? 1 : 0;   // nulls of the chip's last column / row / corner pixel
         // (n, sx, sxx) of this lane's cells before the window's own nulls: off / on the T4 row
@@ -756,6 +866,10 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     __syncthreads();
     MIMC3_MX_STAMP(3)
     if (wave != 0) return;                                  // the sequential part needs one wave (lane k = pivot k)
+    if constexpr (C::FULL) {
+        full_tail<C>(p, val, gidx, lu, lv, lane);
+        return;
+    }
 
     // ---- the climbs (lane k = pivot k) on the complete surface; trajectories as 4-bit codes per scan -------------------------
     auto inside = [&](int pu, int pvv) __attribute__((always_inline)) -> bool {     // the reference's boundary test (:703), true = scan allowed
@@ -1039,6 +1153,35 @@ hipError_t launch_match_mx(MatchU8Args a, hipStream_t stream)
     a.point_flags = a.mx_flags;
     if (e == hipSuccess && a.mx_wn_on) { a.flag_value = kMxWn; e = launch_form<true, false>(a, stream); }
     if (e == hipSuccess && a.mx_gen_on) { a.flag_value = kMxNulls; e = launch_form<true, true>(a, stream); }
+    return e;
+}
+
+// Exhaustive search: every point on the matrix cores.  The clean form runs over all points and flags the null-ridden ones for the
+// window-null form (nulls in the search box only) or the general form (chip nulls too), which run right behind in flag mode.
+template <bool GEN, bool CN>
+static hipError_t launch_full_form(const MatchU8Args &a, hipStream_t stream)
+{
+    switch (a.ocw) {
+    case 7: return mx::launch_one<mx::FullCfg<7, GEN, CN>>(a, stream);
+    case 15: return mx::launch_one<mx::FullCfg<15, GEN, CN>>(a, stream);
+    case 16: return mx::launch_one<mx::FullCfg<16, GEN, CN>>(a, stream);
+    case 30: return mx::launch_one<mx::FullCfg<30, GEN, CN>>(a, stream);
+    case 32: return mx::launch_one<mx::FullCfg<32, GEN, CN>>(a, stream);
+    case 40: return mx::launch_one<mx::FullCfg<40, GEN, CN>>(a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream)
+{
+    if (a.N <= 0) return hipSuccess;
+    if (!a.mx_flags || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15) return hipErrorInvalidValue;
+    a.mx_wn_on = 1; a.mx_gen_on = 1; a.mx_preflag = 0;
+    a.point_list = nullptr; a.point_count = nullptr; a.point_flags = nullptr;
+    hipError_t e = launch_full_form<false, false>(a, stream);
+    a.point_flags = a.mx_flags;
+    if (e == hipSuccess) { a.flag_value = kMxWn; e = launch_full_form<true, false>(a, stream); }
+    if (e == hipSuccess) { a.flag_value = kMxNulls; e = launch_full_form<true, true>(a, stream); }
     return e;
 }
 
