@@ -69,7 +69,9 @@ struct mimc3_ctx {
     const float *d_i0 = nullptr, *d_i1 = nullptr;
     DevBuf own_i0, own_i1;              // used when images were uploaded from the host
     int32_t H = 0, W = 0;
-    DevBuf pl0, pl1, flag;              // zero-bordered u8 planes (exact-integer path) + "not 8-bit" flag
+    // The pair's plane sets, one builder each (prepare_pair, build_u8_tables, build_u16, build_f32).  A builder works on `stream` and
+    // drains it before it sets its ready flag, so a set is complete whatever stream a matcher call comes in on.
+    DevBuf pl0, pl1, flag;              // zero-bordered u8 planes (exact-integer path) + the device tests' flags
     DevBuf sat0, sat1, sat_tmp;         // packed summed-area tables of pl0 / pl1 (sum b | sum b^2 | nulls; sat_kernel.hip), built with the planes
     DevBuf hsat0, hsat1, hsz0, hsz1;    // the same for the u16 planes hpl0 / hpl1: sum q | sum q^2, and the null counts
     bool sat_u8_ok = false, sat_u16_ok = false;   // tables hold the CURRENT planes (chip-atlas contexts build them only if a call needs them)
@@ -78,21 +80,20 @@ struct mimc3_ctx {
     bool u8o_ok = false;                // integer (shift 0) u16 planes whose local range mostly fits 8 bits: try PxU8o first
     DevBuf hpl0, hpl1;                  // zero-bordered u16 planes of scaled integers (q = value * 2^shift < 4096)
     DevBuf rt0, rt1;                    // PxU8o: min | max << 16 of every 16x16-pixel tile of hpl0 / hpl1 (valid while u8o_ok)
-    bool u16_ok = false;                // the pair is scaled-integer (and not 8-bit): u16 planes are built
+    bool u16_ok = false;                // the pair is scaled-integer (and not 8-bit): its u16 planes are built with the classification
     bool hpl_valid = false;             // u16 planes hold the CURRENT pair
-    int shift0 = 0, shift1 = 0;
+    int shift0 = 0, shift1 = 0;         // scaled integers: pixel x 2^shift is the u16 plane's value (0 for an 8-bit pair)
     DevBuf fpl0, fpl1;                  // zero-bordered f32 planes (register-tiled f32 kernel), built on first use
     bool fplanes_ok = false;
     DevBuf fsat0, fsat1;                // their 16-byte summed-area tables when every pixel (x 1 or x 8) is an integer in [0, 2^20) (16-bit DN and its filtered forms)
     bool f32i_ok = false;
     int fshift0 = 0, fshift1 = 0;      // pixel x 2^shift is the integer the table sums
     int32_t Wp = 0;
-    bool u8_ok = false;                 // both images proven to be integers in [0,255]
+    bool u8_ok = false;                 // both images proven to be integers in [0,255]: the u8 planes are built with the classification
     int path_mode = 0;                  // 0 auto, 1 force the general f32 kernel, 2 no integer kernels, 3 no u8 kernel, 4 auto without the matrix-core kernel
     int last_path = -1;                 // 0 general f32/f64 kernel, 1 exact u8 kernel, ... (mimc3_hip.h), 5 matrix-core u8 kernel
     DevBuf xy, puv, poff, out;          // matcher staging for the host-buffer entry point
     DevBuf pcor, pcnt, pext;            // device pivots: corridors [N] x 24 B, counts [N], extents + total (24 B)
-    int32_t xy_stride = 6, xy_col = 2;  // where the matcher finds a point's (u, v) in its `xyuvav` argument: xyuvav rows, or (internal) a packed [N][2] array
     hipEvent_t ev_chunk[2][8] = {};     // mimc3_match_ncc_dlc_cor: "chunk uploaded + counted" / "chunk matched"
     DevBuf qm_io, qm_work;              // QM staging / workspace
     DevBuf n1_io, n1_work;              // clustering / dpf0 / dpf1 staging and workspace
@@ -114,11 +115,8 @@ struct mimc3_ctx {
     void *hslot[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // mimc3_ctx_host_workspace: pinned host scratch
     size_t hslot_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     DevBuf slot[24];                    // mimc3_ctx_workspace: named scratch the drivers built on the ABI keep across calls
-    bool no_u8o = false;                // internal (CP stage): never try the per-point-offset u8 form on this context's pairs
-    int32_t lane = 0;                   // internal (CP stage): which scratch set (overflow lists) the next matcher call uses: calls on
-    DevBuf ovf_alt[3], fail_alt[3];     // different streams of one context must not share them
-    DevBuf mxl[4];                      // matrix-core kernel: one flag byte per grid point (one buffer per `lane`)
-    int32_t win_half = 0;               // internal (CP stage): > 0 = the next matcher calls use a full (2*win_half+1)^2 search area
+    DevBuf ovf_alt[3], fail_alt[3];     // the overflow lists of matcher lanes 1..3: calls on different streams of one context must not share them
+    DevBuf mxl[4];                      // matrix-core kernel: one flag byte per grid point (one buffer per lane)
     mimc3_ctx *cp_child[4] = {nullptr, nullptr, nullptr, nullptr};   // CP stage: one context per image variant for its chip atlas (planes, kernel selection)
     DevBuf cellws;                      // general matcher: global cell-grid workspace for corridors whose cell grid outgrows LDS
     DevBuf raw_dn;                      // raw 8/16-bit DN as uploaded (mimc3_ctx_set_images_u8/_u16), widened on the device
@@ -256,18 +254,7 @@ extern "C" void mimc3_ctx_destroy(mimc3_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    c->own_i0.release(); c->own_i1.release();
-    c->rt0.release(); c->rt1.release();
-    c->pl0.release(); c->pl1.release(); c->flag.release(); c->ovf.release(); c->fail.release(); c->fpl0.release(); c->fpl1.release(); c->hpl0.release(); c->hpl1.release();
-    c->xy.release(); c->puv.release(); c->poff.release(); c->out.release();
-    c->qm_io.release(); c->qm_work.release();
-    c->n1_io.release(); c->n1_work.release();
-    c->filt0.release(); c->filt1.release(); c->conv_io.release(); c->cp_buf.release();
     for (auto &ch : c->cp_child) if (ch) { mimc3_ctx_destroy(ch); ch = nullptr; }
-    for (auto &b : c->ovf_alt) b.release();
-    for (auto &b : c->fail_alt) b.release();
-    c->raw_dn.release(); c->cellws.release();
-    for (auto &b : c->slot) b.release();
     for (auto &h : c->hslot) if (h) (void)hipHostFree(h);
     for (auto &pp : c->pin) if (pp) (void)hipHostFree(pp);
     for (auto &ev : c->ev_pin) if (ev) (void)hipEventDestroy(ev);
@@ -281,8 +268,6 @@ extern "C" void mimc3_ctx_destroy(mimc3_ctx *c)
     delete c;
 }
 
-// Build the zero-bordered u8 planes and prove (on the device) that both images are 8-bit integral.
-// Runs once per image pair; the CLI then reuses the pair for 8 matcher passes (MIMC_main.c:261-300).
 // what the tables of a context's planes cover: the whole zero-bordered plane (windows hang over the image edge), or -- chip
 // atlases of the control-point stage, whose full-square search areas stay inside a tile -- the image area alone
 static mimc3::SatRegion table_region(const mimc3_ctx *c)
@@ -292,7 +277,24 @@ static mimc3::SatRegion table_region(const mimc3_ctx *c)
     return mimc3::SatRegion{0, 0, c->Wp, c->H + 2 * pad};
 }
 
-// The summed-area tables of the u8 planes: built once per image pair, right behind the planes (enqueued on the context's stream).
+// One of the device's pixel tests over both images (launch_detect_scaled_int, launch_detect_int16): per image, the shift that makes
+// every pixel an integer the test accepts -- 0 (integers), 3 (multiples of 1/8: the Laplacian, MIMC_main.c:188-196) or -1 (neither).
+// One read-back: drains the context's stream.
+typedef hipError_t (*detect_launcher)(const float *, size_t, int *, hipStream_t);
+static int detect_shifts(mimc3_ctx *c, detect_launcher detect, int shift[2])
+{
+    int fl[2] = {3, 3};
+    HIP_TRY(c->flag.reserve(2 * sizeof(int)));
+    HIP_TRY(hipMemsetAsync(c->flag.p, 0, 2 * sizeof(int), c->stream));
+    HIP_TRY(detect(c->d_i0, (size_t)c->H * c->W, static_cast<int *>(c->flag.p), c->stream));
+    HIP_TRY(detect(c->d_i1, (size_t)c->H * c->W, static_cast<int *>(c->flag.p) + 1, c->stream));
+    HIP_TRY(hipMemcpyAsync(fl, c->flag.p, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 2; k++) shift[k] = (fl[k] & 1) == 0 ? 0 : ((fl[k] & 2) == 0 ? 3 : -1);
+    return 0;
+}
+
+// The u8 form's summed-area tables (its planes come with the classification, prepare_pair).
 static int build_u8_tables(mimc3_ctx *c)
 {
     const int Hp = c->H + 2 * mimc3::kU8Pad;
@@ -301,106 +303,131 @@ static int build_u8_tables(mimc3_ctx *c)
     HIP_TRY(c->sat_tmp.reserve(mimc3::sat_scratch_bytes(Hp, c->Wp)));
     HIP_TRY(mimc3::launch_sat_u8(static_cast<const unsigned char *>(c->pl0.p), c->Wp, table_region(c), static_cast<unsigned long long *>(c->sat0.p), c->sat_tmp.p, c->stream));
     HIP_TRY(mimc3::launch_sat_u8(static_cast<const unsigned char *>(c->pl1.p), c->Wp, table_region(c), static_cast<unsigned long long *>(c->sat1.p), c->sat_tmp.p, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));      // matcher calls may come in on any stream
+    HIP_TRY(hipStreamSynchronize(c->stream));
     c->sat_u8_ok = true;
     return 0;
 }
 
-// ... and of the u16 planes (enqueued on `s`; callers order later use on other streams themselves)
-static int build_u16_tables(mimc3_ctx *c, hipStream_t s)
+// The u16 form: zero-bordered planes of the scaled integers q = value * 2^shift, then -- when `tables` -- their summed-area tables.
+// A pair of 9-bit integers (gradients of 8-bit images: u16_ok, shift 0) also gets its per-tile ranges when the LOCAL range fits 8 bits
+// almost everywhere: the u8 kernels then run it through per-point offsets (PxU8o) and the few points that do not fit go to PxU16.
+// (Not on a chip-atlas context: over a whole 85x85 search area a gradient's range rarely fits 8 bits, and a second launch for the
+// points that do not costs a full kernel latency.)
+static int build_u16(mimc3_ctx *c, bool tables)
 {
-    const int Hp = c->H + 2 * mimc3::kU8Pad;
-    HIP_TRY(c->hsat0.reserve(mimc3::sat_bytes(Hp, c->Wp)));
-    HIP_TRY(c->hsat1.reserve(mimc3::sat_bytes(Hp, c->Wp)));
-    HIP_TRY(c->hsz0.reserve(mimc3::sat_null_bytes(Hp, c->Wp)));
-    HIP_TRY(c->hsz1.reserve(mimc3::sat_null_bytes(Hp, c->Wp)));
-    HIP_TRY(c->sat_tmp.reserve(mimc3::sat_scratch_bytes(Hp, c->Wp)));
-    HIP_TRY(mimc3::launch_sat_u16(static_cast<const unsigned short *>(c->hpl0.p), c->Wp, table_region(c), static_cast<unsigned long long *>(c->hsat0.p),
-                                  static_cast<unsigned int *>(c->hsz0.p), c->sat_tmp.p, s));
-    HIP_TRY(mimc3::launch_sat_u16(static_cast<const unsigned short *>(c->hpl1.p), c->Wp, table_region(c), static_cast<unsigned long long *>(c->hsat1.p),
-                                  static_cast<unsigned int *>(c->hsz1.p), c->sat_tmp.p, s));
-    c->sat_u16_ok = true;
+    const int pad = mimc3::kU8Pad, Hp = c->H + 2 * pad;
+    if (!c->hpl_valid) {
+        const size_t hb = sizeof(unsigned short) * (size_t)Hp * c->Wp;
+        HIP_TRY(c->hpl0.reserve(hb));
+        HIP_TRY(c->hpl1.reserve(hb));
+        HIP_TRY(hipMemsetAsync(c->hpl0.p, 0, hb, c->stream));
+        HIP_TRY(hipMemsetAsync(c->hpl1.p, 0, hb, c->stream));
+        HIP_TRY(mimc3::launch_prep_u16(c->d_i0, c->H, c->W, static_cast<unsigned short *>(c->hpl0.p), c->Wp, pad, c->shift0, c->stream));
+        HIP_TRY(mimc3::launch_prep_u16(c->d_i1, c->H, c->W, static_cast<unsigned short *>(c->hpl1.p), c->Wp, pad, c->shift1, c->stream));
+        c->u8o_ok = false;
+        if (c->u16_ok && c->shift0 == 0 && c->shift1 == 0 && !c->child) {
+            int t[4] = {0, 0, 0, 0};
+            HIP_TRY(c->flag.reserve(4 * sizeof(int)));
+            HIP_TRY(hipMemsetAsync(c->flag.p, 0, 4 * sizeof(int), c->stream));
+            HIP_TRY(mimc3::launch_range_tiles(static_cast<const unsigned short *>(c->hpl0.p), c->H, c->W, c->Wp, pad, static_cast<int *>(c->flag.p), c->stream));
+            HIP_TRY(mimc3::launch_range_tiles(static_cast<const unsigned short *>(c->hpl1.p), c->H, c->W, c->Wp, pad, static_cast<int *>(c->flag.p) + 2, c->stream));
+            HIP_TRY(hipMemcpyAsync(t, c->flag.p, sizeof(t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (2 * t[0] >= t[1] && 2 * t[2] >= t[3]) {     // per-tile ranges: the kernel bounds a point's local range from them before it scans pixels
+                const size_t tb = sizeof(uint32_t) * (size_t)((c->Wp + 15) / 16) * ((Hp + 15) / 16);
+                HIP_TRY(c->rt0.reserve(tb));
+                HIP_TRY(c->rt1.reserve(tb));
+                HIP_TRY(mimc3::launch_range_tiles16(static_cast<const unsigned short *>(c->hpl0.p), Hp, c->Wp, static_cast<uint32_t *>(c->rt0.p), c->stream));
+                HIP_TRY(mimc3::launch_range_tiles16(static_cast<const unsigned short *>(c->hpl1.p), Hp, c->Wp, static_cast<uint32_t *>(c->rt1.p), c->stream));
+                c->u8o_ok = true;
+            }
+        }
+    }
+    if (tables && !c->sat_u16_ok) {
+        HIP_TRY(c->hsat0.reserve(mimc3::sat_bytes(Hp, c->Wp)));
+        HIP_TRY(c->hsat1.reserve(mimc3::sat_bytes(Hp, c->Wp)));
+        HIP_TRY(c->hsz0.reserve(mimc3::sat_null_bytes(Hp, c->Wp)));
+        HIP_TRY(c->hsz1.reserve(mimc3::sat_null_bytes(Hp, c->Wp)));
+        HIP_TRY(c->sat_tmp.reserve(mimc3::sat_scratch_bytes(Hp, c->Wp)));
+        HIP_TRY(mimc3::launch_sat_u16(static_cast<const unsigned short *>(c->hpl0.p), c->Wp, table_region(c), static_cast<unsigned long long *>(c->hsat0.p),
+                                      static_cast<unsigned int *>(c->hsz0.p), c->sat_tmp.p, c->stream));
+        HIP_TRY(mimc3::launch_sat_u16(static_cast<const unsigned short *>(c->hpl1.p), c->Wp, table_region(c), static_cast<unsigned long long *>(c->hsat1.p),
+                                      static_cast<unsigned int *>(c->hsz1.p), c->sat_tmp.p, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->hpl_valid = true;
+    if (tables) c->sat_u16_ok = true;
     return 0;
 }
 
-static int prepare_u8(mimc3_ctx *c, bool planes_built = false)
+// The f32 form: zero-bordered f32 copies of the pair for the register-tiled f32 kernel, built on first use.  16-bit DN and its
+// filtered forms (every pixel, x 1 or x 8, an integer in [0, 2^20)) also get summed-area tables like the integer planes: the f64
+// sums of the reference are exact integers in any order.  (Not for the control-point stage's chip atlases: a few hundred
+// latency-bound points.)
+static int build_f32(mimc3_ctx *c)
 {
-    c->u8_ok = false;
-    c->fplanes_ok = false;
-    c->sat_u8_ok = false; c->sat_u16_ok = false;
+    const size_t bytes = sizeof(float) * (size_t)(c->H + 2 * mimc3::kU8Pad) * c->Wp;
+    HIP_TRY(c->fpl0.reserve(bytes));
+    HIP_TRY(c->fpl1.reserve(bytes));
+    HIP_TRY(hipMemsetAsync(c->fpl0.p, 0, bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->fpl1.p, 0, bytes, c->stream));
+    HIP_TRY(mimc3::launch_prep_f32(c->d_i0, c->H, c->W, static_cast<float *>(c->fpl0.p), c->Wp, mimc3::kU8Pad, c->stream));
+    HIP_TRY(mimc3::launch_prep_f32(c->d_i1, c->H, c->W, static_cast<float *>(c->fpl1.p), c->Wp, mimc3::kU8Pad, c->stream));
+    c->f32i_ok = false;
+    int sh[2] = {-1, -1};
+    if (!c->child) RC_TRY(detect_shifts(c, mimc3::launch_detect_int16, sh));
+    if (sh[0] >= 0 && sh[1] >= 0) {
+        c->fshift0 = sh[0]; c->fshift1 = sh[1];
+        const int Hp = c->H + 2 * mimc3::kU8Pad;
+        HIP_TRY(c->fsat0.reserve(mimc3::sat2_bytes(Hp, c->Wp)));
+        HIP_TRY(c->fsat1.reserve(mimc3::sat2_bytes(Hp, c->Wp)));
+        HIP_TRY(c->sat_tmp.reserve(mimc3::sat2_scratch_bytes(Hp, c->Wp)));
+        HIP_TRY(mimc3::launch_sat_f32i(static_cast<const float *>(c->fpl0.p), c->Wp, table_region(c), sh[0], static_cast<mimc3::Sat2 *>(c->fsat0.p), c->sat_tmp.p, c->stream));
+        HIP_TRY(mimc3::launch_sat_f32i(static_cast<const float *>(c->fpl1.p), c->Wp, table_region(c), sh[1], static_cast<mimc3::Sat2 *>(c->fsat1.p), c->sat_tmp.p, c->stream));
+        c->f32i_ok = true;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->fplanes_ok = true;
+    return 0;
+}
+
+// A new pair (or new planes of it): forget the plane sets of the previous one and classify it on the device -- 8-bit (u8_ok: the test
+// writes the u8 planes as it goes), else scaled integers (u16_ok: 12-bit DN, or what GMA_float_conv2 makes of 8-bit images:
+// integers / multiples of 1/8; the exact u16 kernel applies), else floats -- then build the sets the DLC passes will read.
+// Runs once per image pair; the CLI then reuses the pair for 8 matcher passes (MIMC_main.c:261-300).  A chip-atlas context builds
+// its tables only if a call needs them (match_dlc).
+static int prepare_pair(mimc3_ctx *c, bool planes_built = false)
+{
+    c->u8_ok = c->u16_ok = c->u8o_ok = false;
+    c->hpl_valid = c->sat_u8_ok = c->sat_u16_ok = c->fplanes_ok = false;
+    c->shift0 = c->shift1 = 0;
     const int pad = mimc3::kU8Pad;
     c->Wp = (c->W + 2 * pad + 3) & ~3;
     const size_t bytes = (size_t)(c->H + 2 * pad) * c->Wp;
     if (planes_built) {                 // raw 8-bit DN was widened straight into the planes (mimc3_ctx_set_images_u8)
-        c->u8_ok = true; c->u16_ok = false; c->hpl_valid = false; c->u8o_ok = false;
-        return c->child ? 0 : build_u8_tables(c);
-    }
-    HIP_TRY(c->pl0.reserve(bytes));
-    HIP_TRY(c->pl1.reserve(bytes));
-    HIP_TRY(c->flag.reserve(sizeof(int)));
-    HIP_TRY(hipMemsetAsync(c->pl0.p, 0, bytes, c->stream));
-    HIP_TRY(hipMemsetAsync(c->pl1.p, 0, bytes, c->stream));
-    HIP_TRY(hipMemsetAsync(c->flag.p, 0, sizeof(int), c->stream));
-    HIP_TRY(mimc3::launch_prep_u8(c->d_i0, c->H, c->W, static_cast<unsigned char *>(c->pl0.p), c->Wp, pad,
-                                  static_cast<int *>(c->flag.p), c->stream));
-    HIP_TRY(mimc3::launch_prep_u8(c->d_i1, c->H, c->W, static_cast<unsigned char *>(c->pl1.p), c->Wp, pad,
-                                  static_cast<int *>(c->flag.p), c->stream));
-    int not_u8 = 1;
-    HIP_TRY(hipMemcpyAsync(&not_u8, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->u8_ok = (not_u8 == 0);
-    c->u16_ok = false;
-    c->hpl_valid = false;
-    c->u8o_ok = false;
-    if (c->u8_ok && !c->child) RC_TRY(build_u8_tables(c));   // (a chip-atlas context: only if a call needs them, see mimc3_match_ncc_dlc_dev)
-    if (!c->u8_ok) {
-        // not 8-bit: is the pair "scaled integer" (12-bit DN, or what GMA_float_conv2 makes of 8-bit images:
-        // integers / multiples of 1/8)?  Then the exact u16 kernel applies.
-        int fl[2] = {3, 3};
-        HIP_TRY(c->flag.reserve(2 * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(c->flag.p, 0, 2 * sizeof(int), c->stream));
-        HIP_TRY(mimc3::launch_detect_scaled_int(c->d_i0, (size_t)c->H * c->W, static_cast<int *>(c->flag.p), c->stream));
-        HIP_TRY(mimc3::launch_detect_scaled_int(c->d_i1, (size_t)c->H * c->W, static_cast<int *>(c->flag.p) + 1, c->stream));
-        HIP_TRY(hipMemcpyAsync(fl, c->flag.p, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        c->u8_ok = true;
+    } else {
+        HIP_TRY(c->pl0.reserve(bytes));
+        HIP_TRY(c->pl1.reserve(bytes));
+        HIP_TRY(c->flag.reserve(sizeof(int)));
+        HIP_TRY(hipMemsetAsync(c->pl0.p, 0, bytes, c->stream));
+        HIP_TRY(hipMemsetAsync(c->pl1.p, 0, bytes, c->stream));
+        HIP_TRY(hipMemsetAsync(c->flag.p, 0, sizeof(int), c->stream));
+        HIP_TRY(mimc3::launch_prep_u8(c->d_i0, c->H, c->W, static_cast<unsigned char *>(c->pl0.p), c->Wp, pad,
+                                      static_cast<int *>(c->flag.p), c->stream));
+        HIP_TRY(mimc3::launch_prep_u8(c->d_i1, c->H, c->W, static_cast<unsigned char *>(c->pl1.p), c->Wp, pad,
+                                      static_cast<int *>(c->flag.p), c->stream));
+        int not_u8 = 1;
+        HIP_TRY(hipMemcpyAsync(&not_u8, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        auto pick = [](int f) { return (f & 1) == 0 ? 0 : ((f & 2) == 0 ? 3 : -1); };
-        const int s0 = pick(fl[0]), s1 = pick(fl[1]);
-        if (s0 >= 0 && s1 >= 0) {
-            const size_t hb = sizeof(unsigned short) * (size_t)(c->H + 2 * pad) * c->Wp;
-            HIP_TRY(c->hpl0.reserve(hb));
-            HIP_TRY(c->hpl1.reserve(hb));
-            HIP_TRY(hipMemsetAsync(c->hpl0.p, 0, hb, c->stream));
-            HIP_TRY(hipMemsetAsync(c->hpl1.p, 0, hb, c->stream));
-            HIP_TRY(mimc3::launch_prep_u16(c->d_i0, c->H, c->W, static_cast<unsigned short *>(c->hpl0.p), c->Wp, pad, s0, c->stream));
-            HIP_TRY(mimc3::launch_prep_u16(c->d_i1, c->H, c->W, static_cast<unsigned short *>(c->hpl1.p), c->Wp, pad, s1, c->stream));
-            if (!c->child) RC_TRY(build_u16_tables(c, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->shift0 = s0; c->shift1 = s1; c->u16_ok = true; c->hpl_valid = true;
-            // 9-bit integers (gradients of 8-bit images): does the LOCAL range fit 8 bits almost everywhere?  Then the
-            // u8 kernels can run them through per-point offsets (PxU8o); the few points that do not fit go to PxU16.
-            c->u8o_ok = false;
-            if (s0 == 0 && s1 == 0 && !c->no_u8o && !getenv("MIMC3_NO_U8O")) {
-                int t[4] = {0, 0, 0, 0};
-                HIP_TRY(c->flag.reserve(4 * sizeof(int)));
-                HIP_TRY(hipMemsetAsync(c->flag.p, 0, 4 * sizeof(int), c->stream));
-                HIP_TRY(mimc3::launch_range_tiles(static_cast<const unsigned short *>(c->hpl0.p), c->H, c->W, c->Wp, pad, static_cast<int *>(c->flag.p), c->stream));
-                HIP_TRY(mimc3::launch_range_tiles(static_cast<const unsigned short *>(c->hpl1.p), c->H, c->W, c->Wp, pad, static_cast<int *>(c->flag.p) + 2, c->stream));
-                HIP_TRY(hipMemcpyAsync(t, c->flag.p, sizeof(t), hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                c->u8o_ok = 2 * t[0] >= t[1] && 2 * t[2] >= t[3];
-                if (c->u8o_ok) {        // per-tile ranges: the kernel bounds a point's local range from them before it scans pixels
-                    const int Hp = c->H + 2 * pad;
-                    const size_t tb = sizeof(uint32_t) * (size_t)((c->Wp + 15) / 16) * ((Hp + 15) / 16);
-                    HIP_TRY(c->rt0.reserve(tb));
-                    HIP_TRY(c->rt1.reserve(tb));
-                    HIP_TRY(mimc3::launch_range_tiles16(static_cast<const unsigned short *>(c->hpl0.p), Hp, c->Wp, static_cast<uint32_t *>(c->rt0.p), c->stream));
-                    HIP_TRY(mimc3::launch_range_tiles16(static_cast<const unsigned short *>(c->hpl1.p), Hp, c->Wp, static_cast<uint32_t *>(c->rt1.p), c->stream));
-                    HIP_TRY(hipStreamSynchronize(c->stream));
-                }
-            }
-        }
+        c->u8_ok = (not_u8 == 0);
     }
-    return 0;
+    if (c->u8_ok) return c->child ? 0 : build_u8_tables(c);
+    int sh[2];
+    RC_TRY(detect_shifts(c, mimc3::launch_detect_scaled_int, sh));
+    if (sh[0] < 0 || sh[1] < 0) return 0;
+    c->shift0 = sh[0]; c->shift1 = sh[1]; c->u16_ok = true;
+    return build_u16(c, !c->child);
 }
 
 extern "C" int mimc3_ctx_set_path(mimc3_ctx *c, int32_t mode)
@@ -425,7 +452,7 @@ extern "C" int mimc3_ctx_set_images(mimc3_ctx *c, const float *i0, const float *
     c->d_i0 = c->raw_i0 = static_cast<const float *>(c->own_i0.p);
     c->d_i1 = c->raw_i1 = static_cast<const float *>(c->own_i1.p);
     c->H = H; c->W = W; c->filt_live = false;
-    return prepare_u8(c);
+    return prepare_pair(c);
 }
 
 // Raw DN entry points: what the TIFF holds crosses PCIe (1 or 2 bytes per pixel instead of 4) and the widening to f32
@@ -454,7 +481,7 @@ extern "C" int mimc3_ctx_set_images_u8(mimc3_ctx *c, const uint8_t *i0, const ui
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->d_i0 = c->raw_i0 = static_cast<const float *>(c->own_i0.p);
     c->d_i1 = c->raw_i1 = static_cast<const float *>(c->own_i1.p);
-    return prepare_u8(c, true);
+    return prepare_pair(c, true);
 }
 
 extern "C" int mimc3_ctx_set_images_u16(mimc3_ctx *c, const uint16_t *i0, const uint16_t *i1, int32_t H, int32_t W)
@@ -473,7 +500,7 @@ extern "C" int mimc3_ctx_set_images_u16(mimc3_ctx *c, const uint16_t *i0, const 
     c->d_i0 = c->raw_i0 = static_cast<const float *>(c->own_i0.p);
     c->d_i1 = c->raw_i1 = static_cast<const float *>(c->own_i1.p);
     c->H = H; c->W = W; c->filt_live = false;
-    return prepare_u8(c);              // 16-bit files may still hold 8- or 12-bit DN: classified on the device as usual
+    return prepare_pair(c);              // 16-bit files may still hold 8- or 12-bit DN: classified on the device as usual
 }
 
 static int set_images_dev_impl(mimc3_ctx *c, const float *d_i0, const float *d_i1, int32_t H, int32_t W, bool producer_unknown)
@@ -481,7 +508,7 @@ static int set_images_dev_impl(mimc3_ctx *c, const float *d_i0, const float *d_i
     c->d_i0 = c->raw_i0 = d_i0; c->d_i1 = c->raw_i1 = d_i1; c->H = H; c->W = W; c->filt_live = false;
     HIP_TRY(hipSetDevice(c->device));
     if (producer_unknown) HIP_TRY(hipDeviceSynchronize());   // make the pixels visible whatever stream produced them
-    return prepare_u8(c);
+    return prepare_pair(c);
 }
 
 extern "C" int mimc3_ctx_set_images_dev(mimc3_ctx *c, const float *d_i0, const float *d_i1, int32_t H, int32_t W)
@@ -509,42 +536,152 @@ extern "C" int mimc3_ctx_last_kernel_ms(mimc3_ctx *c, float *ms)
 // ---------------------------------------------------------------------------------------------
 // matcher
 // ---------------------------------------------------------------------------------------------
-// zero-bordered f32 copies of the pair for the register-tiled f32 kernel, once per image pair (enqueued on `s`)
-static int build_f32_planes(mimc3_ctx *c, hipStream_t s)
+// The reference reads the chip without any bounds check (MIMC_module.c:852): refuse a grid point g0 <= g < g1 of the xyuvav rows
+// whose chip leaves the image instead of reproducing undefined behaviour.  With `uv`, the points' (u, v) are packed there in the
+// same pass ([N][2], indexed by g).
+static int check_chips(const mimc3_ctx *c, const double *xyuvav, int32_t g0, int32_t g1, int32_t ocw, const char *entry, double *uv = nullptr)
 {
-    if (c->fplanes_ok) return 0;
-    const size_t bytes = sizeof(float) * (size_t)(c->H + 2 * mimc3::kU8Pad) * c->Wp;
-    HIP_TRY(c->fpl0.reserve(bytes));
-    HIP_TRY(c->fpl1.reserve(bytes));
-    HIP_TRY(hipMemsetAsync(c->fpl0.p, 0, bytes, s));
-    HIP_TRY(hipMemsetAsync(c->fpl1.p, 0, bytes, s));
-    HIP_TRY(mimc3::launch_prep_f32(c->d_i0, c->H, c->W, static_cast<float *>(c->fpl0.p), c->Wp, mimc3::kU8Pad, s));
-    HIP_TRY(mimc3::launch_prep_f32(c->d_i1, c->H, c->W, static_cast<float *>(c->fpl1.p), c->Wp, mimc3::kU8Pad, s));
-    c->fplanes_ok = true;
-    // 16-bit DN and its filtered forms (every pixel, x 1 or x 8, an integer in [0, 2^20)): the f64 sums of the reference are exact integers in any order, and the
-    // planes get summed-area tables like the integer planes (one read-back per image pair)
-    c->f32i_ok = false;
-    if (!getenv("MIMC3_NO_F32_TABLES") && !c->child) {     // (not for the control-point stage's chip atlases: a few hundred latency-bound points)
-        int fl[2] = {3, 3};
-        HIP_TRY(c->flag.reserve(2 * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(c->flag.p, 0, 2 * sizeof(int), s));
-        HIP_TRY(mimc3::launch_detect_int16(c->d_i0, (size_t)c->H * c->W, static_cast<int *>(c->flag.p), s));
-        HIP_TRY(mimc3::launch_detect_int16(c->d_i1, (size_t)c->H * c->W, static_cast<int *>(c->flag.p) + 1, s));
-        HIP_TRY(hipMemcpyAsync(fl, c->flag.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        auto pick = [](int f) { return (f & 1) == 0 ? 0 : ((f & 2) == 0 ? 3 : -1); };      // integers, or multiples of 1/8 (the Laplacian, MIMC_main.c:188-196)
-        const int s0 = pick(fl[0]), s1 = pick(fl[1]);
-        if (s0 >= 0 && s1 >= 0) {
-            c->fshift0 = s0; c->fshift1 = s1;
-            const int Hp = c->H + 2 * mimc3::kU8Pad;
-            HIP_TRY(c->fsat0.reserve(mimc3::sat2_bytes(Hp, c->Wp)));
-            HIP_TRY(c->fsat1.reserve(mimc3::sat2_bytes(Hp, c->Wp)));
-            HIP_TRY(c->sat_tmp.reserve(mimc3::sat2_scratch_bytes(Hp, c->Wp)));
-            HIP_TRY(mimc3::launch_sat_f32i(static_cast<const float *>(c->fpl0.p), c->Wp, table_region(c), s0, static_cast<mimc3::Sat2 *>(c->fsat0.p), c->sat_tmp.p, s));
-            HIP_TRY(mimc3::launch_sat_f32i(static_cast<const float *>(c->fpl1.p), c->Wp, table_region(c), s1, static_cast<mimc3::Sat2 *>(c->fsat1.p), c->sat_tmp.p, s));
-            c->f32i_ok = true;
+    for (int32_t g = g0; g < g1; ++g) {
+        const double gu = xyuvav[6 * (size_t)g + 2], gv = xyuvav[6 * (size_t)g + 3];
+        const int32_t u0 = (int32_t)gu, v0 = (int32_t)gv;
+        if (u0 - ocw < 0 || u0 + ocw >= c->W || v0 - ocw < 0 || v0 + ocw >= c->H)
+            return mimc3::fail(MIMC3_EBOUNDS, std::string(entry) + ": grid point " + std::to_string(g) + " chip leaves the image");
+        if (uv) { uv[2 * (size_t)g] = gu; uv[2 * (size_t)g + 1] = gv; }
+    }
+    return 0;
+}
+
+// the MatchU8Args fields the DLC and exhaustive-search entries share: plane geometry and the grid
+static mimc3::MatchU8Args u8_args(const mimc3_ctx *c, const double *d_xy, int32_t xy_stride, int32_t xy_col, int32_t N, int32_t off_u, int32_t off_v,
+                                  int32_t ocw, int32_t swap, float *d_out)
+{
+    mimc3::MatchU8Args u{};
+    u.Wp = c->Wp; u.pad = mimc3::kU8Pad; u.H = c->H; u.W = c->W; u.thr = min_dn_threshold();
+    u.xyuvav = d_xy; u.xy_stride = xy_stride; u.xy_col = xy_col; u.N = N; u.off_u = off_u; u.off_v = off_v;
+    u.ocw = ocw; u.swap = swap ? 1 : 0; u.out = d_out;
+    return u;
+}
+
+// The kernel path of one matcher call (the last_path codes of mimc3_hip.h), from the pair's classification, the path mode and the
+// launch's extents; builds and launches nothing.  A tiled kernel is only chosen when the launch's largest window fits its LDS carve
+// (a long corridor on a big chip does not: 4 B/px at ocw 40 stops fitting at |last pivot| ~47 px); what does not fit takes the next
+// policy down to the general kernel, which can read the window from L2 -- the reference handles every such input.
+static int choose_path(const mimc3_ctx *c, int32_t ocw, int32_t max_npiv, int32_t max_abs_piv_u, int32_t max_abs_piv_v, int32_t reach_u,
+                       int32_t reach_v, int32_t win_half, bool tables_needed)
+{
+    typedef hipError_t (*px_launcher)(mimc3::MatchU8Args, int, int, int, hipStream_t);
+    auto fits = [&](px_launcher fn) {
+        mimc3::MatchU8Args probe{};
+        probe.ocw = ocw; probe.dry_run = 1; probe.win_half = win_half;
+        return fn(probe, max_abs_piv_u, max_abs_piv_v, max_npiv, nullptr) == hipSuccess;
+    };
+    const bool px_ok = mimc3::match_u8_supported(ocw, reach_u, reach_v);
+    const bool auto_mode = c->path_mode == 0 || c->path_mode == 4;
+    if (auto_mode && c->u8_ok && px_ok && fits(mimc3::launch_match_u8))
+        return tables_needed && c->path_mode == 0 && mimc3::match_mx_supported(ocw, max_npiv, win_half, max_abs_piv_u, max_abs_piv_v) ? 5 : 1;
+    // (path mode 3, for tests: 8-bit pairs are scaled integers too, shift 0)
+    if (((auto_mode && c->u16_ok) || (c->path_mode == 3 && (c->u16_ok || c->u8_ok))) && px_ok && fits(mimc3::launch_match_u16))
+        return auto_mode && c->u8o_ok ? 4 : 3;
+    if (c->path_mode != 1 && mimc3::match_f32x_supported(ocw, reach_u, reach_v) && fits(mimc3::launch_match_f32x)) return 2;
+    return 0;
+}
+
+// mimc3_match_ncc_dlc_dev with its call options: where the points' (u, v) sit in `d_xy` (xyuvav rows: 6, 2; packed [N][2]: 2, 0), the
+// lane (0..3: the overflow lists and matrix-core flags of the call -- calls on different streams of one context take different
+// lanes) and the search area (win_half > 0: the full (2*win_half+1)^2 square of the control-point stage)
+static int match_dlc(mimc3_ctx *c, const double *d_xy, int32_t xy_stride, int32_t xy_col, int32_t N, int32_t off_u, int32_t off_v,
+                     const int32_t *d_piv_uv, const int64_t *d_piv_off, int32_t max_npiv, int32_t max_abs_piv_u, int32_t max_abs_piv_v,
+                     int32_t ocw, int32_t swap, float *d_out, hipStream_t s, int lane, int32_t win_half)
+{
+    if (!c || !d_xy || !d_piv_uv || !d_piv_off || !d_out || N <= 0 || max_npiv < 1 || max_abs_piv_u < 0 || max_abs_piv_v < 0)
+        return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_dlc_dev: bad argument");
+    if (ocw < 1) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_dlc_dev: ocw must be >= 1");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_dlc_dev: images not set");
+    if (c->child && win_half <= 0) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_dlc_dev: a chip-atlas context only matches full-square search areas");   // (its tables cover the image area only)
+    HIP_TRY(hipSetDevice(c->device));
+    const int reach_u = max_abs_piv_u + (off_u < 0 ? -off_u : off_u), reach_v = max_abs_piv_v + (off_v < 0 ? -off_v : off_v);
+    // the many-pivot kernel forms (the control-point stage's 21x21 pivot set on its two chip sizes) read no tables
+    const bool tables_needed = !(max_npiv > 64 && (ocw == 15 || ocw == 30));
+    const int path = choose_path(c, ocw, max_npiv, max_abs_piv_u, max_abs_piv_v, reach_u, reach_v, win_half, tables_needed);
+    // that path's plane set, if this pair has not got it yet (complete when the builder returns: see mimc3_ctx)
+    if ((path == 5 || path == 1) && tables_needed && !c->sat_u8_ok) RC_TRY(build_u8_tables(c));
+    if ((path == 4 || path == 3) && (!c->hpl_valid || (tables_needed && !c->sat_u16_ok))) RC_TRY(build_u16(c, tables_needed));
+    if (path == 2 && !c->fplanes_ok) RC_TRY(build_f32(c));
+
+    mimc3::MatchArgs a{};
+    a.i0 = c->d_i0; a.i1 = c->d_i1; a.H = c->H; a.W = c->W;
+    a.xyuvav = d_xy; a.xy_stride = xy_stride; a.xy_col = xy_col; a.N = N; a.off_u = off_u; a.off_v = off_v;
+    a.piv_uv = d_piv_uv; a.piv_off = d_piv_off; a.ocw = ocw; a.swap = swap ? 1 : 0;
+    a.thr = min_dn_threshold();
+    a.out = d_out;
+    a.win_half = win_half;
+    {   // the general kernel (the last resort of every policy) keeps the cell grid in a global workspace when it outgrows LDS
+        const size_t ws = mimc3::match_f32_workspace_bytes(ocw, max_abs_piv_u, max_abs_piv_v, max_npiv, win_half);
+        if (ws) {
+            HIP_TRY(c->cellws.reserve(ws));
+            a.cell_ws = static_cast<unsigned char *>(c->cellws.p); a.cell_ws_bytes = c->cellws.cap;
         }
     }
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    hipError_t e = hipSuccess;
+    if (path != 0) {
+        mimc3::MatchU8Args u = u8_args(c, d_xy, xy_stride, xy_col, N, off_u, off_v, ocw, swap, d_out);
+        u.piv_uv = d_piv_uv; u.piv_off = d_piv_off; u.win_half = win_half;
+        // points whose per-point NCC cache overflows (very long climbs) are appended to a device list and
+        // redone by the general kernel right behind, in list mode: no host round trip
+        DevBuf &ovf = lane ? c->ovf_alt[lane - 1] : c->ovf;
+        HIP_TRY(ovf.reserve(sizeof(int32_t) * ((size_t)N + 1)));
+        HIP_TRY(hipMemsetAsync(ovf.p, 0, sizeof(int32_t), s));
+        u.ovf_count = static_cast<int32_t *>(ovf.p);
+        u.ovf_list = u.ovf_count + 1;
+        if (path == 5 || path == 1) {
+            u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
+            u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
+            if (path == 5) {
+                // dense correlation surfaces on the matrix cores first; the points that kernel does not take (chips with nulls,
+                // corridors wider than its tile, ...) are redone by the register-tiled kernel in list mode, no host round trip
+                DevBuf &ml = c->mxl[lane];
+                HIP_TRY(ml.reserve((size_t)N));
+                HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
+                u.mx_flags = static_cast<uint8_t *>(ml.p);
+                u.mx_preflag = (max_abs_piv_u > 29 || max_abs_piv_v > 29) ? 1 : 0;      // some corridors may be wider than the kernel's tile
+                e = mimc3::launch_match_mx(u, s);
+                u.point_flags = u.mx_flags; u.flag_value = mimc3::kMxRest;
+            }
+            if (e == hipSuccess) e = mimc3::launch_match_u8(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
+        } else if (path == 4 || path == 3) {
+            u.p0 = static_cast<const unsigned char *>(c->hpl0.p); u.p1 = static_cast<const unsigned char *>(c->hpl1.p);
+            u.scale0 = 1.0 / (double)(1 << c->shift0); u.scale1 = 1.0 / (double)(1 << c->shift1);
+            u.sat0 = c->hsat0.p; u.sat1 = c->hsat1.p; u.satz0 = c->hsz0.p; u.satz1 = c->hsz1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
+            if (path == 4) {
+                // u8 machinery through per-point offsets first; what does not fit is redone by the u16 kernel in list mode
+                DevBuf &failb = lane ? c->fail_alt[lane - 1] : c->fail;
+                HIP_TRY(failb.reserve(sizeof(int32_t) * ((size_t)N + 1)));
+                HIP_TRY(hipMemsetAsync(failb.p, 0, sizeof(int32_t), s));
+                u.fail_count = static_cast<int32_t *>(failb.p);
+                u.fail_list = u.fail_count + 1;
+                if (!getenv("MIMC3_NO_RANGE_TILES")) { u.rt0 = static_cast<const uint32_t *>(c->rt0.p); u.rt1 = static_cast<const uint32_t *>(c->rt1.p); u.rt_tw = (c->Wp + 15) / 16; }
+                e = mimc3::launch_match_u8o(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
+                u.rt0 = u.rt1 = nullptr;
+                u.point_count = u.fail_count; u.point_list = u.fail_list;
+                u.fail_count = nullptr; u.fail_list = nullptr;
+            }
+            if (e == hipSuccess) e = mimc3::launch_match_u16(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
+        } else {
+            u.p0 = static_cast<const unsigned char *>(c->fpl0.p); u.p1 = static_cast<const unsigned char *>(c->fpl1.p);
+            if (c->f32i_ok) {
+                u.sat0 = c->fsat0.p; u.sat1 = c->fsat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
+                u.scale0 = 1.0 / (double)(1 << c->fshift0); u.scale1 = 1.0 / (double)(1 << c->fshift1);
+            }
+            e = mimc3::launch_match_f32x(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
+        }
+        a.point_count = u.ovf_count;
+        a.point_list = u.ovf_list;
+    }
+    if (e == hipSuccess) e = mimc3::launch_match_f32(a, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "match kernel launch");
+    c->last_path = path;
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
     return 0;
 }
 
@@ -553,144 +690,8 @@ extern "C" int mimc3_match_ncc_dlc_dev(mimc3_ctx *c, const double *d_xyuvav, int
                                        int32_t max_abs_piv_u, int32_t max_abs_piv_v, int32_t ocw, int32_t swap,
                                        float *d_out, void *stream)
 {
-    if (!c || !d_xyuvav || !d_piv_uv || !d_piv_off || !d_out || N <= 0 || max_npiv < 1 || max_abs_piv_u < 0 || max_abs_piv_v < 0)
-        return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_dlc_dev: bad argument");
-    if (ocw < 1) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_dlc_dev: ocw must be >= 1");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_dlc_dev: images not set");
-    if (c->child && c->win_half <= 0) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_dlc_dev: a chip-atlas context only matches full-square search areas");   // (its tables cover the image area only)
-    HIP_TRY(hipSetDevice(c->device));
-    mimc3::MatchArgs a{};
-    a.i0 = c->d_i0; a.i1 = c->d_i1; a.H = c->H; a.W = c->W;
-    a.xyuvav = d_xyuvav; a.xy_stride = c->xy_stride; a.xy_col = c->xy_col; a.N = N; a.off_u = off_u; a.off_v = off_v;
-    a.piv_uv = d_piv_uv; a.piv_off = d_piv_off; a.ocw = ocw; a.swap = swap ? 1 : 0;
-    a.thr = min_dn_threshold();
-    a.out = d_out;
-    a.win_half = c->win_half;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    {   // the general kernel (the last resort of every policy) keeps the cell grid in a global workspace when it outgrows LDS
-        const size_t ws = mimc3::match_f32_workspace_bytes(ocw, max_abs_piv_u, max_abs_piv_v, max_npiv, c->win_half);
-        if (ws) {
-            HIP_TRY(c->cellws.reserve(ws));
-            a.cell_ws = static_cast<unsigned char *>(c->cellws.p); a.cell_ws_bytes = c->cellws.cap;
-        }
-    }
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    const int reach_u = max_abs_piv_u + (off_u < 0 ? -off_u : off_u), reach_v = max_abs_piv_v + (off_v < 0 ? -off_v : off_v);
-    hipError_t e;
-    // a tiled kernel is only chosen when the launch's largest window fits its LDS carve (a long corridor on a big chip
-    // does not: 4 B/px at ocw 40 stops fitting at |last pivot| ~47 px); what does not fit takes the next policy down
-    // to the general kernel, which can read the window from L2 -- the reference handles every such input
-    typedef hipError_t (*px_launcher)(mimc3::MatchU8Args, int, int, int, hipStream_t);
-    auto fits = [&](px_launcher fn) {
-        mimc3::MatchU8Args probe{};
-        probe.ocw = ocw; probe.dry_run = 1; probe.win_half = c->win_half;
-        return fn(probe, max_abs_piv_u, max_abs_piv_v, max_npiv, nullptr) == hipSuccess;
-    };
-    const bool px_ok = mimc3::match_u8_supported(ocw, reach_u, reach_v);
-    const bool auto_mode = c->path_mode == 0 || c->path_mode == 4;
-    const bool want_u8 = auto_mode && c->u8_ok && px_ok && fits(mimc3::launch_match_u8);
-    bool want_u16 = !want_u8 && (auto_mode || c->path_mode == 3) && px_ok && fits(mimc3::launch_match_u16);
-    if (want_u16 && !c->u16_ok) {
-        if (c->u8_ok && c->path_mode == 3 && !c->hpl_valid) {  // tests: 8-bit pairs are scaled integers too (shift 0)
-            const size_t hb = sizeof(unsigned short) * (size_t)(c->H + 2 * mimc3::kU8Pad) * c->Wp;
-            HIP_TRY(c->hpl0.reserve(hb));
-            HIP_TRY(c->hpl1.reserve(hb));
-            HIP_TRY(hipMemsetAsync(c->hpl0.p, 0, hb, s));
-            HIP_TRY(hipMemsetAsync(c->hpl1.p, 0, hb, s));
-            HIP_TRY(mimc3::launch_prep_u16(c->d_i0, c->H, c->W, static_cast<unsigned short *>(c->hpl0.p), c->Wp, mimc3::kU8Pad, 0, s));
-            HIP_TRY(mimc3::launch_prep_u16(c->d_i1, c->H, c->W, static_cast<unsigned short *>(c->hpl1.p), c->Wp, mimc3::kU8Pad, 0, s));
-            RC_TRY(build_u16_tables(c, s));
-            c->shift0 = c->shift1 = 0;
-            c->hpl_valid = true;
-        }
-        want_u16 = c->u8_ok && c->path_mode == 3;
-    }
-    const bool want_f32x = !want_u8 && !want_u16 && c->path_mode != 1 && mimc3::match_f32x_supported(ocw, reach_u, reach_v) &&
-                           fits(mimc3::launch_match_f32x);
-    if (want_u8 || want_u16 || want_f32x) {
-        mimc3::MatchU8Args u{};
-        u.Wp = c->Wp; u.pad = mimc3::kU8Pad; u.H = c->H; u.W = c->W; u.thr = a.thr;
-        u.xyuvav = d_xyuvav; u.xy_stride = c->xy_stride; u.xy_col = c->xy_col; u.N = N; u.off_u = off_u; u.off_v = off_v;
-        u.piv_uv = d_piv_uv; u.piv_off = d_piv_off; u.ocw = ocw; u.swap = swap ? 1 : 0; u.out = d_out;
-        u.win_half = c->win_half;
-        // points whose per-point NCC cache overflows (very long climbs) are appended to a device list and
-        // redone by the general kernel right behind, in list mode: no host round trip
-        DevBuf &ovf = c->lane ? c->ovf_alt[c->lane - 1] : c->ovf;
-        DevBuf &failb = c->lane ? c->fail_alt[c->lane - 1] : c->fail;
-        HIP_TRY(ovf.reserve(sizeof(int32_t) * ((size_t)N + 1)));
-        HIP_TRY(hipMemsetAsync(ovf.p, 0, sizeof(int32_t), s));
-        u.ovf_count = static_cast<int32_t *>(ovf.p);
-        u.ovf_list = u.ovf_count + 1;
-        // the many-pivot kernel forms (the control-point stage's 21x21 pivot set on its two chip sizes) read no tables
-        const bool tables_needed = !(max_npiv > 64 && (ocw == 15 || ocw == 30));
-        if (want_u8 && tables_needed && !c->sat_u8_ok) RC_TRY(build_u8_tables(c));
-        if (want_u16 && tables_needed && !c->sat_u16_ok) { RC_TRY(build_u16_tables(c, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
-        if (want_u8) {
-            u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
-            u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
-            if (tables_needed && c->path_mode == 0 && mimc3::match_mx_supported(ocw, max_npiv, c->win_half, max_abs_piv_u, max_abs_piv_v)) {
-                // dense correlation surfaces on the matrix cores first; the points that kernel does not take (chips with nulls,
-                // corridors wider than its tile, ...) are redone by the register-tiled kernel in list mode, no host round trip
-                DevBuf &ml = c->mxl[c->lane];
-                HIP_TRY(ml.reserve((size_t)N));
-                HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
-                u.mx_flags = static_cast<uint8_t *>(ml.p);
-                u.mx_preflag = (max_abs_piv_u > 29 || max_abs_piv_v > 29) ? 1 : 0;      // some corridors may be wider than the kernel's tile
-                e = mimc3::launch_match_mx(u, s);
-                if (e == hipSuccess) {
-                    u.point_flags = u.mx_flags; u.flag_value = mimc3::kMxRest;
-                    e = mimc3::launch_match_u8(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-                }
-                c->last_path = 5;
-            } else {
-            e = mimc3::launch_match_u8(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-            c->last_path = 1;
-            }
-        } else if (want_u16) {
-            u.p0 = static_cast<const unsigned char *>(c->hpl0.p); u.p1 = static_cast<const unsigned char *>(c->hpl1.p);
-            u.scale0 = 1.0 / (double)(1 << c->shift0); u.scale1 = 1.0 / (double)(1 << c->shift1);
-            u.sat0 = c->hsat0.p; u.sat1 = c->hsat1.p; u.satz0 = c->hsz0.p; u.satz1 = c->hsz1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
-            if (c->u8o_ok && c->u16_ok && auto_mode) {
-                // u8 machinery through per-point offsets first; what does not fit is redone by the u16 kernel in list mode
-                HIP_TRY(failb.reserve(sizeof(int32_t) * ((size_t)N + 1)));
-                HIP_TRY(hipMemsetAsync(failb.p, 0, sizeof(int32_t), s));
-                u.fail_count = static_cast<int32_t *>(failb.p);
-                u.fail_list = u.fail_count + 1;
-                if (!getenv("MIMC3_NO_RANGE_TILES")) { u.rt0 = static_cast<const uint32_t *>(c->rt0.p); u.rt1 = static_cast<const uint32_t *>(c->rt1.p); u.rt_tw = (c->Wp + 15) / 16; }
-                e = mimc3::launch_match_u8o(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-                u.rt0 = u.rt1 = nullptr;
-                if (e == hipSuccess) {
-                    u.point_count = u.fail_count; u.point_list = u.fail_list;
-                    u.fail_count = nullptr; u.fail_list = nullptr;
-                    e = mimc3::launch_match_u16(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-                }
-                c->last_path = 4;
-            } else {
-                e = mimc3::launch_match_u16(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-                c->last_path = 3;
-            }
-        } else {
-            RC_TRY(build_f32_planes(c, s));
-            u.p0 = static_cast<const unsigned char *>(c->fpl0.p); u.p1 = static_cast<const unsigned char *>(c->fpl1.p);
-            if (c->f32i_ok) {
-                u.sat0 = c->fsat0.p; u.sat1 = c->fsat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
-                u.scale0 = 1.0 / (double)(1 << c->fshift0); u.scale1 = 1.0 / (double)(1 << c->fshift1);
-            }
-            e = mimc3::launch_match_f32x(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-            c->last_path = 2;
-        }
-        if (e == hipSuccess) {
-            a.point_count = u.ovf_count;
-            a.point_list = u.ovf_list;
-            e = mimc3::launch_match_f32(a, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-        }
-    } else {
-        e = mimc3::launch_match_f32(a, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-        c->last_path = 0;
-    }
-    if (e != hipSuccess) return mimc3::hip_fail(e, "match kernel launch");
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
+    return match_dlc(c, d_xyuvav, 6, 2, N, off_u, off_v, d_piv_uv, d_piv_off, max_npiv, max_abs_piv_u, max_abs_piv_v, ocw, swap, d_out,
+                     static_cast<hipStream_t>(stream), 0, 0);
 }
 
 extern "C" int mimc3_match_ncc_dlc(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2],
@@ -699,13 +700,8 @@ extern "C" int mimc3_match_ncc_dlc(mimc3_ctx *c, const double *xyuvav, int32_t N
     if (!c || !xyuvav || !offset || !piv_uv || !piv_off || !out || N <= 0)
         return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_dlc: bad argument");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_dlc: images not set");
-    // The reference reads the chip without any bounds check (MIMC_module.c:852) and overflows on an
-    // empty pivot list (:589-591).  Refuse those inputs instead of reproducing undefined behaviour.
-    for (int32_t g = 0; g < N; ++g) {
-        const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
-        if (u0 - ocw < 0 || u0 + ocw >= c->W || v0 - ocw < 0 || v0 + ocw >= c->H)
-            return mimc3::fail(MIMC3_EBOUNDS, "mimc3_match_ncc_dlc: grid point " + std::to_string(g) + " chip leaves the image");
-    }
+    // the reference also overflows on an empty pivot list (:589-591): mimc3_pivot_extent refuses that
+    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, "mimc3_match_ncc_dlc"));
     int32_t mn = 0, mu = 0, mv = 0;
     int rc = mimc3_pivot_extent(piv_uv, piv_off, N, &mn, &mu, &mv);
     if (rc) return rc;
@@ -742,14 +738,12 @@ extern "C" int mimc3_match_ncc_full_dev(mimc3_ctx *c, const double *d_xyuvav, in
     if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, "mimc3_match_ncc_full_dev: the pair is not 8-bit (u8 planes only)");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));         // (enqueued on the context's stream and drained before the kernels read them)
-    mimc3::MatchU8Args u{};
-    u.Wp = c->Wp; u.pad = mimc3::kU8Pad; u.H = c->H; u.W = c->W; u.thr = min_dn_threshold();
-    u.xyuvav = d_xyuvav; u.xy_stride = c->xy_stride; u.xy_col = c->xy_col; u.N = N; u.off_u = off_u; u.off_v = off_v;
-    u.full_shift = d_shift; u.full_R = R; u.ocw = ocw; u.swap = swap ? 1 : 0; u.out = d_out;
+    if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
+    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
+    u.full_shift = d_shift; u.full_R = R;
     u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
     u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
-    DevBuf &ml = c->mxl[c->lane];
+    DevBuf &ml = c->mxl[0];
     HIP_TRY(ml.reserve((size_t)N));
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
@@ -770,11 +764,10 @@ extern "C" int mimc3_match_ncc_full(mimc3_ctx *c, const double *xyuvav, int32_t 
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_full: images not set");
     if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, "mimc3_match_ncc_full: the pair is not 8-bit (u8 planes only)");
     // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
+    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, "mimc3_match_ncc_full"));
     const int64_t pad = mimc3::kU8Pad;
     for (int32_t g = 0; g < N; ++g) {
         const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
-        if (u0 - ocw < 0 || u0 + ocw >= c->W || v0 - ocw < 0 || v0 + ocw >= c->H)
-            return mimc3::fail(MIMC3_EBOUNDS, "mimc3_match_ncc_full: grid point " + std::to_string(g) + " chip leaves the image");
         const int64_t cu = (int64_t)u0 + offset[0] + (shift ? shift[2 * (size_t)g] : 0), cv = (int64_t)v0 + offset[1] + (shift ? shift[2 * (size_t)g + 1] : 0);
         const int64_t h = R + ocw;
         if (cu - h < -pad || cu + h >= c->W + pad || cv - h < -pad || cv + h >= c->H + pad)
@@ -916,14 +909,9 @@ static int match_cor_impl(mimc3_ctx *c, const double *xyuvav, const void *cor, i
     auto upload = [&](int k) -> int {
         const size_t g0 = (size_t)lo[k], n = (size_t)(lo[k + 1] - lo[k]);
         if (produce) (*produce)(lo[k], lo[k + 1]);
-        for (int32_t g = lo[k]; g < lo[k + 1]; ++g) {
-            const double gu = xyuvav[6 * (size_t)g + 2], gv = xyuvav[6 * (size_t)g + 3];
-            const int32_t u0 = (int32_t)gu, v0 = (int32_t)gv;
-            if (u0 - ocw < 0 || u0 + ocw >= c->W || v0 - ocw < 0 || v0 + ocw >= c->H) {
-                (void)hipStreamSynchronize(up);
-                return mimc3::fail(MIMC3_EBOUNDS, "mimc3_match_ncc_dlc_cor: grid point " + std::to_string(g) + " chip leaves the image");
-            }
-            huv[2 * (size_t)g] = gu; huv[2 * (size_t)g + 1] = gv;
+        if (const int rc = check_chips(c, xyuvav, lo[k], lo[k + 1], ocw, "mimc3_match_ncc_dlc_cor", huv)) {
+            (void)hipStreamSynchronize(up);
+            return rc;
         }
         HIP_TRY(hipMemcpyAsync(d_uv + 2 * g0, huv + 2 * g0, 16 * n, hipMemcpyHostToDevice, up));
         HIP_TRY(hipMemcpyAsync(d_cor + sizeof(mimc3::CorridorPOD) * g0, hc + g0, sizeof(mimc3::CorridorPOD) * n, hipMemcpyHostToDevice, up));
@@ -937,17 +925,15 @@ static int match_cor_impl(mimc3_ctx *c, const double *xyuvav, const void *cor, i
     // ---- the context's stream: lists + matcher of a chunk; second copy stream: its results down
     int rc = 0;
     int64_t uv_base = 0;
-    const int32_t keep_stride = c->xy_stride, keep_col = c->xy_col;
-    c->xy_stride = 2; c->xy_col = 0;
-    // chunks alternate between two streams (and two sets of per-call scratch: c->lane), so that the first launches of chunk k+1 run
+    // chunks alternate between two streams (and two matcher lanes of per-call scratch), so that the first launches of chunk k+1 run
     // under the tail of chunk k's last one
     static const int two_env = getenv("MIMC3_IO_TWO_STREAMS") ? atoi(getenv("MIMC3_IO_TWO_STREAMS")) : 1;      // tuning / A-B
     const bool two = two_env != 0 && K > 1 && c->aux[2] != nullptr;
     auto process = [&](int k) -> int {
         const size_t g0 = (size_t)lo[k];
         const int32_t n = lo[k + 1] - lo[k];
-        hipStream_t s = (two && (k & 1)) ? c->aux[2] : c->stream;
-        c->lane = (two && (k & 1)) ? 1 : 0;
+        const int lane = (two && (k & 1)) ? 1 : 0;
+        hipStream_t s = lane ? c->aux[2] : c->stream;
         hipError_t e = hipEventSynchronize(c->ev_chunk[0][k]);
         if (e != hipSuccess) { rc = mimc3::hip_fail(e, "chunk upload"); return rc; }
         const int32_t *h = hext + 16 * k;
@@ -969,12 +955,12 @@ static int match_cor_impl(mimc3_ctx *c, const double *xyuvav, const void *cor, i
         e = hipStreamWaitEvent(s, c->ev_chunk[0][k], 0);
         // (the general kernel's global cell workspace -- windows that outgrow LDS altogether -- is one per context: such a chunk waits
         //  for its predecessor on the other stream)
-        if (e == hipSuccess && two && k > 0 && mimc3::match_f32_workspace_bytes(ocw, h[1], h[2], h[0], c->win_half) != 0)
+        if (e == hipSuccess && two && k > 0 && mimc3::match_f32_workspace_bytes(ocw, h[1], h[2], h[0], 0) != 0)
             e = hipStreamWaitEvent(s, c->ev_chunk[1][k - 1], 0);
         if (e == hipSuccess) e = mimc3::launch_pivot_fill(reinterpret_cast<const mimc3::CorridorDev *>(d_cor) + g0, off, n, swap ? nullptr : uv, swap ? uv : nullptr, s);
         if (e != hipSuccess) { rc = mimc3::hip_fail(e, "pivot lists"); return rc; }
         float *d_out = static_cast<float *>(c->out.p) + 3 * g0;
-        rc = mimc3_match_ncc_dlc_dev(c, d_uv + 2 * g0, n, offset[0], offset[1], uv, off, h[0], h[1], h[2], ocw, swap, d_out, s);
+        rc = match_dlc(c, d_uv + 2 * g0, 2, 0, n, offset[0], offset[1], uv, off, h[0], h[1], h[2], ocw, swap, d_out, s, lane, 0);
         if (rc) return rc;
         e = hipEventRecord(c->ev_chunk[1][k], s);
         if (e == hipSuccess) e = hipStreamWaitEvent(down, c->ev_chunk[1][k], 0);
@@ -991,8 +977,6 @@ static int match_cor_impl(mimc3_ctx *c, const double *xyuvav, const void *cor, i
         if (k + 1 < K) rc = upload(k + 1);
         if (!rc) rc = process(k);
     }
-    c->xy_stride = keep_stride; c->xy_col = keep_col;
-    c->lane = 0;
     lap("chunks enqueued");
     // every stream drains before the buffers are reused (also on the error paths)
     hipError_t e1 = hipStreamSynchronize(up), e2 = hipStreamSynchronize(s), e3 = hipStreamSynchronize(down);
@@ -1309,7 +1293,7 @@ extern "C" int mimc3_ctx_filter_images(mimc3_ctx *c, const float *kernel, int32_
     if (!kernel) {                                   // back to the pair as handed over; the next filter starts from fresh planes
         c->d_i0 = c->raw_i0; c->d_i1 = c->raw_i1;
         c->filt_live = false;
-        return prepare_u8(c);
+        return prepare_pair(c);
     }
     const size_t bytes = sizeof(float) * (size_t)c->H * c->W;
     HIP_TRY(c->filt0.reserve(bytes));
@@ -1332,7 +1316,7 @@ extern "C" int mimc3_ctx_filter_images(mimc3_ctx *c, const float *kernel, int32_
     HIP_TRY(hipStreamSynchronize(s));
     c->d_i0 = static_cast<const float *>(c->filt0.p);
     c->d_i1 = static_cast<const float *>(c->filt1.p);
-    return prepare_u8(c);
+    return prepare_pair(c);
 }
 
 extern "C" int mimc3_ctx_get_images(mimc3_ctx *c, float *i0, float *i1)
@@ -1443,15 +1427,7 @@ static int cp_slice(mimc3_ctx *c, const mimc3_cp_params *p, const CpGeom &g, con
         for (int v = 0; v < 4; v++) {
             mimc3_ctx *ch = c->cp_child[v];
             ch->path_mode = c->path_mode;
-            // gradients go straight to the u16 kernel: over a whole 85x85 search area their range rarely fits the 8 bits
-            // of the per-point-offset form, and a second launch for the points that do not costs a full kernel latency
-            ch->no_u8o = true;
             RC_TRY(set_images_dev_impl(ch, d_a0[v], d_a1[v], n * cs, cs, false));
-            ch->win_half = ocw_chip;
-            if (!ch->u8_ok && !ch->u16_ok) {       // float / 16-bit atlas: the f32 planes are built lazily by the first match
-                RC_TRY(build_f32_planes(ch, ch->stream));   // -- here the four matches start on four streams, so build them first
-                HIP_TRY(hipStreamSynchronize(ch->stream));
-            }
             for (int c3 = 1; c3 < 3; c3++) {
                 const int ocw = p->vec_ocw[c3];
                 const int32_t slot = (c3 - 1) * 8 + v * 2;
@@ -1460,10 +1436,7 @@ static int cp_slice(mimc3_ctx *c, const mimc3_cp_params *p, const CpGeom &g, con
                     const int lane_id = (c3 - 1) * 2 + sw;                     // 0..3
                     hipStream_t ms = lane_id == 0 ? s : c->side[lane_id - 1];
                     float *o = d_dp + (size_t)(slot + sw) * n * 3;
-                    ch->lane = lane_id;
-                    int rc = mimc3_match_ncc_dlc_dev(ch, d_xy, n, 0, 0, d_piv, d_poff, npiv, reach, reach, ocw, sw, o, ms);
-                    ch->lane = 0;
-                    if (rc) return rc;
+                    RC_TRY(match_dlc(ch, d_xy, 6, 2, n, 0, 0, d_piv, d_poff, npiv, reach, reach, ocw, sw, o, ms, lane_id, ocw_chip));
                     if (sw) HIP_TRY(mimc3::launch_negate_uv(o, n, ms));         // :376-377
                 }
             }
@@ -1471,7 +1444,6 @@ static int cp_slice(mimc3_ctx *c, const mimc3_cp_params *p, const CpGeom &g, con
         return 0;
     };
     const int mrc = matches();
-    for (auto &ch : c->cp_child) ch->win_half = 0;
     for (auto &st : c->side) HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipStreamSynchronize(s));
     if (mrc) return mrc;
