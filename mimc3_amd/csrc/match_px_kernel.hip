@@ -2157,7 +2157,10 @@ __global__ void prep_f32_plane(const float *img, int H, int W, float *plane, int
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= W || y >= H) return;
-    plane[(size_t)(y + pad) * Wp + (x + pad)] = img[(size_t)y * W + x];
+    // -0.0 -> +0.0: a null either way (:622, :723), but the integer policy (PxF32i) reads its chips unsanitised and tells a pixel
+    // from an unused slot by its bits (au != 0)
+    const float v = img[(size_t)y * W + x];
+    plane[(size_t)(y + pad) * Wp + (x + pad)] = (v == 0.0f) ? 0.0f : v;
 }
 
 hipError_t launch_prep_f32(const float *img, int H, int W, float *plane, int Wp, int pad, hipStream_t s)
