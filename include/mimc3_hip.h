@@ -76,8 +76,8 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *       chip sizes it is built for; the points it does not take (null pixels in the window or chip, corridors wider than
  *       its 32 x 32 cell tile, ...) are flagged and done by kernel 1 right behind;
  *   0 = general f32 kernel (any ocw, any window size) otherwise;
- *   6 = the exhaustive search (mimc3_match_ncc_full): the matrix-core kernel's surfaces, every point on the matrix cores
- *       (it does not depend on the mode).
+ *   6 = the exhaustive search (mimc3_match_ncc_full, mimc3_match_ncc_pyramid): the matrix-core kernel's surfaces, every point
+ *       on the matrix cores (it does not depend on the mode).
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -154,6 +154,40 @@ int mimc3_match_ncc_full(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const 
  * The caller guarantees the bounds the host entry checks (a point that breaks them gets an all-NaN record and no read). */
 int mimc3_match_ncc_full_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                              const int32_t *d_shift, int32_t ocw, int32_t R, int32_t swap, float *d_out, void *stream);
+
+/* ---- Coarse-to-fine exhaustive search over an image pyramid (no reference counterpart: the reach of mimc3_match_ncc_full, +-R
+ *      around uv0 + offset + shift, made about R (2^L - 1) px by searching a reduced pair first -- the offset trackers' standard).
+ *
+ *   Inputs: those of mimc3_match_ncc_full, plus levels L, 1 <= L <= 5; the pair must be 8-bit (u8 planes).  For grid point i:
+ *     starting displacement  (u0, v0) = ((int)xyuvav[i][2], (int)xyuvav[i][3]);  D = offset + shift[i] (shift NULL = zero).
+ *     levels     level 0 is the resident pair; level l has H_l = H_{l-1} >> 1, W_l = W_{l-1} >> 1 (an odd last row or column is
+ *                dropped), and its pixel (x, y) comes from the 2 x 2 block I_{l-1}[2y..2y+1][2x..2x+1]: with n the number of its
+ *                non-zero (non-null) pixels and s their sum, (s + n/2) / n in integer arithmetic (nearest, ties up), or 0 when n = 0.
+ *                A level pixel stays in 0..255 and is null exactly when its whole block is.  The point sits at p_l = (u0 >> l, v0 >> l).
+ *     coarsest   d_{L-1} = floor((D + 2^{L-2}) / 2^{L-1}) per axis (arithmetic shift); for L = 1, d_0 = D.
+ *     l = L-1 .. 1  the exhaustive search of mimc3_match_ncc_full on the level-l pair at p_l, with offset 0, shift d_l and the same
+ *                ocw, R and swap (its validity and first-wins arg-max rules unchanged).  If it has an arg-max cell (su, sv) -- a peak
+ *                on the border (status -4) included: it still points the way -- d_{l-1} = 2 (d_l + (su, sv)); otherwise (status -3,
+ *                -2, a chip that leaves the level image, a search box beyond the level planes' 256-px zero border) d_{l-1} = 2 d_l.
+ *     level 0    the [N][8] record of the exhaustive search at uv0 with the caller's offset and shift_out[i] = d_0 - offset: bit for
+ *                bit what mimc3_match_ncc_full(ctx, xyuvav, N, offset, shift_out, ocw, R, swap) returns wherever that call accepts
+ *                the input.  A point whose derived level-0 search box leaves the 256-px zero border gets the all-NaN record (the
+ *                _dev entry's contract); the call is not refused.
+ *   Output: out [N][8] as mimc3_match_ncc_full; shift_out [N][2] (optional): d_0 - offset, the shift of the level-0 search.
+ *   Refusals: levels outside 1..5, a level-(L-1) image smaller than a chip (min(H_{L-1}, W_{L-1}) < 2 ocw + 1), a starting
+ *   displacement (offset, or offset + shift[i]) beyond +-2^24 on an axis, and every refusal of mimc3_match_ncc_full for ocw and R:
+ *   MIMC3_EINVAL; a chip that leaves the level-0 image: MIMC3_EBOUNDS; a pair that is not 8-bit: MIMC3_EUNSUPPORTED.
+ *   mimc3_ctx_last_path reports 6.  The levels are built on the first call that needs them and kept until the pair changes; all L
+ *   searches and the steps between them run on one stream, with no host round trip between levels. */
+int mimc3_match_ncc_pyramid(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                            const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t levels, int32_t swap,
+                            float *out /*[N][8] host*/, int32_t *shift_out /*[N][2] host or NULL*/);
+/* Device-resident variant: d_xyuvav [N][6], d_shift [N][2] or NULL, d_out [N][8], d_shift_out [N][2] or NULL device pointers;
+ * enqueues on `stream`, no sync (a first call on a pair builds its levels on the context's stream and drains it first).  The caller
+ * guarantees the chip and displacement bounds the host entry checks. */
+int mimc3_match_ncc_pyramid_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t swap,
+                                float *d_out, int32_t *d_shift_out /*or NULL*/, void *stream);
 /* Host helper: the a-priori displacement as whole pixels, get_uv_pivot's sign convention (:559-598):
  *   shift[i] = (floor(vx dt / 365 / mpp + 0.5), floor(-vy dt / 365 / mpp + 0.5))   (f64, vx = xyuvav[i][4], vy = xyuvav[i][5]) */
 int mimc3_prior_shift(const double *xyuvav, int32_t N, float dt, float mpp, int32_t *shift /*[N][2]*/);

@@ -50,6 +50,9 @@ _lib.mimc3_match_ncc_dlc_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int
                                          C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
 _lib.mimc3_match_ncc_full.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, _f32p]
 _lib.mimc3_match_ncc_full_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
+_lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
+_lib.mimc3_match_ncc_pyramid_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             _vp, _vp, _vp]
 _lib.mimc3_prior_shift.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, _i32p]
 _lib.mimc3_pivot_corridors.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _vp]
 _lib.mimc3_get_uv_pivot_dev.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _vp]
@@ -455,6 +458,29 @@ class Context:
         """Device-pointer variant (enqueue only): d_xyuvav [n][6] f64, d_shift [n][2] int32 or 0, d_out [n][8] f32."""
         _check(_lib.mimc3_match_ncc_full_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                              1 if swap else 0, d_out, stream), "match_ncc_full_dev")
+
+    def match_ncc_pyramid(self, xyuvav, offset, ocw, radius, levels, shift=None, swap=False):
+        """Coarse-to-fine exhaustive search over an image pyramid (mimc3_match_ncc_pyramid) on the resident 8-bit pair ->
+        (float32[N][8] record as match_ncc_full, int32[N][2] shift_out).  The search at +-radius runs on the pair reduced levels - 1
+        times first, then each finer level around twice the coarser result; the record is match_ncc_full's with shift = shift_out."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        out = np.empty((n, 8), np.float32)
+        sh_out = np.empty((n, 2), np.int32)
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_pyramid: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_pyramid(self._h, xy, n, np.ascontiguousarray(offset, np.int32), None if sh is None else sh.ctypes.data,
+                                            ocw, radius, levels, 1 if swap else 0, out, sh_out), "match_ncc_pyramid")
+        return out, sh_out
+
+    def match_ncc_pyramid_dev(self, d_xyuvav, n, offset, ocw, radius, levels, d_out, d_shift=0, d_shift_out=0, stream=0, swap=False):
+        """Device-pointer variant (enqueue only): d_xyuvav [n][6] f64, d_shift [n][2] int32 or 0, d_out [n][8] f32,
+        d_shift_out [n][2] int32 or 0."""
+        _check(_lib.mimc3_match_ncc_pyramid_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius, levels,
+                                                1 if swap else 0, d_out, d_shift_out or None, stream), "match_ncc_pyramid_dev")
 
     # -- QM -----------------------------------------------------------------------------------
     def get_dpf_pseudosmoothing(self, dpf, dpf_dx, dpf_dy, ruv, mvn, nclus, xyuvav, max_sweeps=101):

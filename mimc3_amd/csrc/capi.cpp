@@ -120,6 +120,11 @@ struct mimc3_ctx {
     mimc3_ctx *cp_child[4] = {nullptr, nullptr, nullptr, nullptr};   // CP stage: one context per image variant for its chip atlas (planes, kernel selection)
     DevBuf cellws;                      // general matcher: global cell-grid workspace for corridors whose cell grid outgrows LDS
     DevBuf raw_dn;                      // raw 8/16-bit DN as uploaded (mimc3_ctx_set_images_u8/_u16), widened on the device
+    // coarse-to-fine search (mimc3_match_ncc_pyramid): pyramid levels 1..4 of the u8 pair, each a zero-bordered plane pair (kU8Pad border,
+    // prepare_pair's pitch rule) with its tables; levels 1..pyr_levels hold the CURRENT pair (built on first use by build_levels)
+    struct PyrLevel { DevBuf pl0, pl1, sat0, sat1; int32_t H = 0, W = 0, Wp = 0; } pyr[4];
+    int pyr_levels = 0;
+    DevBuf pyr_pos, pyr_peak, pyr_sh;   // per point: position on the level (f64 [N][2]), arg-max cell, search shift (the host entry's)
 };
 
 static constexpr size_t kPinChunk = 4u << 20;
@@ -400,6 +405,7 @@ static int prepare_pair(mimc3_ctx *c, bool planes_built = false)
 {
     c->u8_ok = c->u16_ok = c->u8o_ok = false;
     c->hpl_valid = c->sat_u8_ok = c->sat_u16_ok = c->fplanes_ok = false;
+    c->pyr_levels = 0;
     c->shift0 = c->shift1 = 0;
     const int pad = mimc3::kU8Pad;
     c->Wp = (c->W + 2 * pad + 3) & ~3;
@@ -470,6 +476,7 @@ extern "C" int mimc3_ctx_set_images_u8(mimc3_ctx *c, const uint8_t *i0, const ui
     RC_TRY(h2d_copy(c, r1, i1, npx));
     const int pad = mimc3::kU8Pad;
     c->H = H; c->W = W; c->filt_live = false;
+    c->pyr_levels = 0;                   // (level 0 is overwritten below, before prepare_pair)
     c->Wp = (W + 2 * pad + 3) & ~3;
     const size_t pbytes = (size_t)(H + 2 * pad) * c->Wp;
     HIP_TRY(c->pl0.reserve(pbytes));
@@ -786,6 +793,133 @@ extern "C" int mimc3_match_ncc_full(mimc3_ctx *c, const double *xyuvav, int32_t 
     const int rc = mimc3_match_ncc_full_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, swap,
                                             static_cast<float *>(c->out.p), c->stream);
     if (rc) return rc;
+    return d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N);
+}
+
+// ---------------------------------------------------------------------------------------------
+// coarse-to-fine exhaustive search over an image pyramid (pyramid_kernel.hip; every level's search is the full mode of
+// match_mx_kernel.hip): the levels of the u8 pair, the per-level searches and the chaining between them on one stream
+// ---------------------------------------------------------------------------------------------
+// Pyramid levels pyr_levels + 1 .. L - 1 of the u8 pair, each from the level above by the 2 x 2 null-aware reduction, with their
+// tables.  Like every plane-set builder: enqueued on the context's stream and drained before the levels count as built.
+static int build_levels(mimc3_ctx *c, int L)
+{
+    const int pad = mimc3::kU8Pad;
+    for (int l = c->pyr_levels + 1; l < L; ++l) {
+        mimc3_ctx::PyrLevel &d = c->pyr[l - 1];
+        const bool top = l == 1;
+        const void *s0 = top ? c->pl0.p : c->pyr[l - 2].pl0.p, *s1 = top ? c->pl1.p : c->pyr[l - 2].pl1.p;
+        const int Hs = top ? c->H : c->pyr[l - 2].H, Ws = top ? c->W : c->pyr[l - 2].W, Wps = top ? c->Wp : c->pyr[l - 2].Wp;
+        d.H = Hs >> 1; d.W = Ws >> 1; d.Wp = (d.W + 2 * pad + 3) & ~3;
+        const int Hp = d.H + 2 * pad;
+        const size_t bytes = (size_t)Hp * d.Wp;
+        HIP_TRY(d.pl0.reserve(bytes));
+        HIP_TRY(d.pl1.reserve(bytes));
+        HIP_TRY(d.sat0.reserve(mimc3::sat_bytes(Hp, d.Wp)));
+        HIP_TRY(d.sat1.reserve(mimc3::sat_bytes(Hp, d.Wp)));
+        HIP_TRY(c->sat_tmp.reserve(mimc3::sat_scratch_bytes(Hp, d.Wp)));
+        HIP_TRY(hipMemsetAsync(d.pl0.p, 0, bytes, c->stream));
+        HIP_TRY(hipMemsetAsync(d.pl1.p, 0, bytes, c->stream));
+        HIP_TRY(mimc3::launch_pyr_reduce(static_cast<const unsigned char *>(s0), Hs, Ws, Wps, static_cast<unsigned char *>(d.pl0.p), d.H, d.W, d.Wp, pad, c->stream));
+        HIP_TRY(mimc3::launch_pyr_reduce(static_cast<const unsigned char *>(s1), Hs, Ws, Wps, static_cast<unsigned char *>(d.pl1.p), d.H, d.W, d.Wp, pad, c->stream));
+        const mimc3::SatRegion rg{0, 0, d.Wp, Hp};
+        HIP_TRY(mimc3::launch_sat_u8(static_cast<const unsigned char *>(d.pl0.p), d.Wp, rg, static_cast<unsigned long long *>(d.sat0.p), c->sat_tmp.p, c->stream));
+        HIP_TRY(mimc3::launch_sat_u8(static_cast<const unsigned char *>(d.pl1.p), d.Wp, rg, static_cast<unsigned long long *>(d.sat1.p), c->sat_tmp.p, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (L - 1 > c->pyr_levels) c->pyr_levels = L - 1;
+    return 0;
+}
+
+// the refusals both pyramid entries make before anything runs (those of the exhaustive search, levels, the coarsest level's size)
+static int pyramid_check(const mimc3_ctx *c, int32_t ocw, int32_t R, int32_t levels, const char *entry)
+{
+    const std::string e(entry);
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, e + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, e + ": R must be in 1..15");
+    if (levels < 1 || levels > 5) return mimc3::fail(MIMC3_EINVAL, e + ": levels must be in 1..5");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, e + ": images not set");
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, e + ": not on a chip-atlas context");
+    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, e + ": the pair is not 8-bit (u8 planes only)");
+    if (std::min(c->H >> (levels - 1), c->W >> (levels - 1)) < 2 * ocw + 1)
+        return mimc3::fail(MIMC3_EINVAL, e + ": level " + std::to_string(levels - 1) + " is smaller than a chip");
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_pyramid_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                           const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t swap, float *d_out,
+                                           int32_t *d_shift_out, void *stream)
+{
+    if (!c || !d_xyuvav || !d_out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_pyramid_dev: bad argument");
+    RC_TRY(pyramid_check(c, ocw, R, levels, "mimc3_match_ncc_pyramid_dev"));
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
+    if (c->pyr_levels < levels - 1) RC_TRY(build_levels(c, levels));
+    DevBuf &ml = c->mxl[0];
+    HIP_TRY(ml.reserve((size_t)N));
+    HIP_TRY(c->pyr_pos.reserve(sizeof(double) * 2 * (size_t)N));
+    HIP_TRY(c->pyr_peak.reserve(sizeof(int32_t) * (size_t)N));
+    if (!d_shift_out) HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
+    int32_t *sh = d_shift_out ? d_shift_out : static_cast<int32_t *>(c->pyr_sh.p);
+    double *pos = static_cast<double *>(c->pyr_pos.p);
+    int32_t *peak = static_cast<int32_t *>(c->pyr_peak.p);
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    // the coarsest level's displacement d_{L-1} and positions p_{L-1} (for L = 1: shift_out = shift)
+    HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, d_shift, nullptr, R, levels - 1, true, sh, pos, s));
+    for (int l = levels - 1; l >= 0; --l) {
+        mimc3::MatchU8Args u = u8_args(c, l ? pos : d_xyuvav, l ? 2 : 6, l ? 0 : 2, N, l ? 0 : off_u, l ? 0 : off_v, ocw, swap, d_out);
+        u.full_shift = sh; u.full_R = R;
+        if (l == 0) {
+            u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
+            u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
+        } else {                        // level l: its planes, tables and geometry, and the arg-max cells for the step to level l - 1
+            const mimc3_ctx::PyrLevel &d = c->pyr[l - 1];
+            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
+            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
+            u.sat0 = d.sat0.p; u.sat1 = d.sat1.p; u.sat_ws = mimc3::sat_pitch(d.Wp);
+            u.full_peak = peak;
+        }
+        HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
+        u.mx_flags = static_cast<uint8_t *>(ml.p);
+        const hipError_t e = mimc3::launch_match_full_mx(u, s);
+        if (e != hipSuccess) return mimc3::hip_fail(e, "pyramid-level search launch");
+        if (l) HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, nullptr, peak, R, l - 1, false, sh, pos, s));
+    }
+    c->last_path = 6;
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_pyramid(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                       int32_t ocw, int32_t R, int32_t levels, int32_t swap, float *out, int32_t *shift_out)
+{
+    if (!c || !xyuvav || !offset || !out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_pyramid: bad argument");
+    RC_TRY(pyramid_check(c, ocw, R, levels, "mimc3_match_ncc_pyramid"));
+    // the chip inside the level-0 image (a point whose derived search box leaves the zero border gets the all-NaN record); the starting
+    // displacement within +-2^24 per axis, so that every level's shifts stay exact int32
+    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, "mimc3_match_ncc_pyramid"));
+    const int64_t lim = (int64_t)1 << 24;
+    for (int32_t g = 0; g < N; ++g) {
+        const int64_t du = (int64_t)offset[0] + (shift ? shift[2 * (size_t)g] : 0), dv = (int64_t)offset[1] + (shift ? shift[2 * (size_t)g + 1] : 0);
+        if (offset[0] < -lim || offset[0] > lim || offset[1] < -lim || offset[1] > lim || du < -lim || du > lim || dv < -lim || dv > lim)
+            return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_pyramid: grid point " + std::to_string(g) + " starting displacement beyond +-2^24");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
+    HIP_TRY(c->out.reserve(sizeof(float) * 8 * (size_t)N));
+    HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
+    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
+    const int32_t *d_shift = nullptr;
+    if (shift) {
+        HIP_TRY(c->puv.reserve(sizeof(int32_t) * 2 * (size_t)N));
+        RC_TRY(h2d_copy(c, c->puv.p, shift, sizeof(int32_t) * 2 * (size_t)N));
+        d_shift = static_cast<const int32_t *>(c->puv.p);
+    }
+    const int rc = mimc3_match_ncc_pyramid_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, levels, swap,
+                                               static_cast<float *>(c->out.p), static_cast<int32_t *>(c->pyr_sh.p), c->stream);
+    if (rc) return rc;
+    if (shift_out) RC_TRY(d2h_copy(c, shift_out, c->pyr_sh.p, sizeof(int32_t) * 2 * (size_t)N));
     return d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N);
 }
 

@@ -1,13 +1,15 @@
 // MIMC3_hip_offsets -- exhaustive-search NCC offsets with peak quality over libmimc3_hip.so (MI355X): the AMPCOR-style table that
 // MIMC_single_match.c:1-27 describes.
 //
-//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15]
+//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1]
 //
 // Inputs as for MIMC3_hip (the file names start with YYYYMMDDhhmmss; dt from the two timestamps); both images 8-bit.  Steps: the
 // control-point offset (mimc3_vmap_cp, as the reference program measures it), the a-priori shift of every grid point
-// (mimc3_prior_shift), then every offset in [-R, R]^2 around uv0 + offset + shift (mimc3_match_ncc_full).  Outputs in <outdir>:
-//   offsets_<t0>_<t1>.GMA  f32 [N][10]: the [N][8] record of mimc3_match_ncc_full (du, dv, ncc_peak / status, ncc_fit, snr, h_uu,
-//                          h_uv, h_vv) and u, v of the grid point
+// (mimc3_prior_shift), then every offset in [-R, R]^2 around uv0 + offset + shift (mimc3_match_ncc_full), or -- levels > 1 -- the
+// coarse-to-fine search that starts there on a pair reduced levels - 1 times (mimc3_match_ncc_pyramid: a reach of about
+// R (2^levels - 1) px).  Outputs in <outdir>:
+//   offsets_<t0>_<t1>.GMA  f32 [N][10]: the [N][8] record of mimc3_match_ncc_full / _pyramid (du, dv, ncc_peak / status, ncc_fit, snr,
+//                          h_uu, h_uv, h_vv) and u, v of the grid point
 //   offsets_<t0>_<t1>.txt  the points with a non-negative status, one per line, AMPCOR's column order: u du v dv snr h_uu h_vv h_uv;
 //                          du, dv there are the whole displacement (the control-point offset added); a first comment line names
 //                          the columns and the offset
@@ -25,11 +27,11 @@
 int main(int argc, char *argv[])
 {
     printf("MIMC3_hip_offsets -- MI355X build (%s)\n", mimc3_version());
-    if (argc < 5 || argc > 7) {
-        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15]\n", argv[0]);
+    if (argc < 5 || argc > 8) {
+        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1]\n", argv[0]);
         return 2;
     }
-    const int32_t ocw = argc > 5 ? atoi(argv[5]) : 15, R = argc > 6 ? atoi(argv[6]) : 15;
+    const int32_t ocw = argc > 5 ? atoi(argv[5]) : 15, R = argc > 6 ? atoi(argv[6]) : 15, levels = argc > 7 ? atoi(argv[7]) : 1;
     char t0[15], t1[15];
     if (!timestamp_of(argv[1], t0) || !timestamp_of(argv[2], t1)) {
         fprintf(stderr, "image paths must contain a '/' and the file names must start with YYYYMMDDhhmmss\n");
@@ -64,10 +66,12 @@ int main(int argc, char *argv[])
     else { offset[0] = r.offset_cp[0]; offset[1] = r.offset_cp[1]; }
     printf("dt=%f days, MPP=%f; control-point offset [%d, %d] pixels (i1-i0); ocw=%d, R=%d, %d grid points\n", dt, r.mpp, offset[0],
            offset[1], ocw, R, N);
+    if (levels != 1) printf("coarse-to-fine over %d pyramid levels\n", levels);
     std::vector<int32_t> shift(2 * (size_t)N);
     std::vector<float> rec(8 * (size_t)N);
     if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
-        mimc3_match_ncc_full(ctx, xy.data(), N, offset, shift.data(), ocw, R, 0, rec.data())) {
+        (levels == 1 ? mimc3_match_ncc_full(ctx, xy.data(), N, offset, shift.data(), ocw, R, 0, rec.data())
+                     : mimc3_match_ncc_pyramid(ctx, xy.data(), N, offset, shift.data(), ocw, R, levels, 0, rec.data(), nullptr))) {
         fprintf(stderr, "%s\n", mimc3_last_error());
         return leave(3);
     }

@@ -54,7 +54,10 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
         const int32_t *piv_uv;
         const int32_t *full_shift;  // per-point int32 [N][2] (u, v), or null (zero)
     };
-    const int64_t *piv_off;
+    union {
+        const int64_t *piv_off;
+        int32_t *full_peak;         // exhaustive search, optional: per point the arg-max cell k, or -1 without one (pyramid levels)
+    };
     int32_t ocw, swap;
     union {
         int32_t win_half;           // 0: DLC window (|last pivot|+ocw+2, last row/column empty); > 0: full (2*win_half+1)^2 search area (CP stage)
@@ -122,8 +125,20 @@ bool match_mx_supported(int ocw, int max_npiv, int win_half, int max_abs_u, int 
 hipError_t launch_match_mx(MatchU8Args a, hipStream_t stream);
 // exhaustive-search NCC offsets on the same surfaces (mimc3_match_ncc_full): every point on the matrix cores -- the clean form, then
 // the window-null and general forms over the points it flags (a.mx_flags: N bytes, zero before the call); a.full_R in 1..15,
-// a.ocw one of 7, 15, 16, 30, 32, 40; a.out [N][8]
+// a.ocw one of 7, 15, 16, 30, 32, 40; a.out [N][8]; a.full_peak (optional, int32 [N]) gets every point's arg-max cell k = (su + R)(2R + 1)
+// + (sv + R), also at status -4, or -1 without one (status -3 / -2, the NaN record of a point outside the image or the zero border)
 hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream);
+// The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
+// above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all
+// zero; Hd = Hs >> 1, Wd = Ws >> 1 (the destination plane pre-zeroed, border pad in both)
+hipError_t launch_pyr_reduce(const unsigned char *src, int Hs, int Ws, int Wps, unsigned char *dst, int Hd, int Wd, int Wpd, int pad,
+                             hipStream_t s);
+// Per point before the search of level `lnext`: its starting displacement D = (off_u, off_v) + shift[g] (shift null = 0) scaled to the
+// coarsest level (first: d = floor((D + 2^(L-2)) / 2^(L-1)), L = lnext + 1), or the step d = 2 (d_l + s) / 2 d_l from the level just
+// searched (d_l = sh[g], s its arg-max peak[g]); writes sh[g] = d, or d - (off_u, off_v) when lnext == 0, and the level's
+// grid-point position pos[g] = (u0 >> lnext, v0 >> lnext) (f64, lnext > 0)
+hipError_t launch_pyr_step(const double *xyuvav, int N, int off_u, int off_v, const int32_t *shift, const int32_t *peak, int R, int lnext,
+                           bool first, int32_t *sh, double *pos, hipStream_t s);
 
 // max_abs_u/v: max over points of |last pivot| per axis; max_npiv: max pivots per point.
 hipError_t launch_match_f32(MatchArgs a, int max_abs_u, int max_abs_v, int max_npiv, hipStream_t stream);

@@ -112,6 +112,7 @@ struct Cfg {
     static constexpr int MINW1 = (WGS * NW) / 4 > 0 ? (WGS * NW) / 4 : 1;                   // ... never above what LDS admits anyway
     static constexpr int MINW = MINW0 < MINW1 ? MINW0 : MINW1;
     static constexpr bool FULL = false;                 // the DLC matcher (true: FullCfg, the exhaustive search)
+    static constexpr bool PEAK = false;                 // full mode: also write the arg-max cell to full_peak (FullPeakCfg)
 };
 // Exhaustive search (mimc3_match_ncc_full): the same surface builder on the cell tile whose origin is c - R (the search centre
 // c = uv0 + offset + shift, 1 <= R <= 15: all (2R + 1)^2 cells in the tile), no never-written row / column (T4), and instead of the
@@ -119,6 +120,12 @@ struct Cfg {
 template <int OCW_, bool GEN_, bool CN_>
 struct FullCfg : Cfg<OCW_, GEN_, CN_> {
     static constexpr bool FULL = true;
+};
+// ... and for a level of the coarse-to-fine search (mimc3_match_ncc_pyramid): the same record, plus every point's arg-max cell k (or -1)
+// in full_peak, where the next level's search centre comes from
+template <int OCW_, bool GEN_, bool CN_>
+struct FullPeakCfg : FullCfg<OCW_, GEN_, CN_> {
+    static constexpr bool PEAK = true;
 };
 
 // The constant band operands, one table per chip size (constant-initialised device data).  v_mfma_i32_16x16x64_i8: lane (n = lane & 15,
@@ -248,6 +255,12 @@ __device__ __forceinline__ void full_store(float *o, float status)
 //          the model's value at its extremum (c5 the constant of the same least-squares fit) and its Hessian 2 c0, c1, 2 c2;
 //   snr    ncc_peak^2 / mean(NCC^2) over the finite cells outside the peak's 3x3 block (f64 partial sums per lane, then a tree).
 template <class C>
+__device__ __forceinline__ void full_peak_store(const MatchU8Args &p, int gidx, int k)
+{
+    if constexpr (C::PEAK) p.full_peak[gidx] = k;
+}
+
+template <class C>
 __device__ __forceinline__ void full_tail(const MatchU8Args &p, const float *val, int gidx, int shu, int shv, int lane)
 {
     constexpr int VP = C::VP;
@@ -269,9 +282,9 @@ __device__ __forceinline__ void full_tail(const MatchU8Args &p, const float *val
     }
     bv = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bv)));
     bk = __builtin_amdgcn_readfirstlane(bk);
-    if (bk == 0x7fffffff) { if (lane == 0) full_store(out, -2.0f); return; }
+    if (bk == 0x7fffffff) { if (lane == 0) { full_store(out, -2.0f); full_peak_store<C>(p, gidx, -1); } return; }
     const int px = bk / S, py = bk - S * px, su = px - R, sv = py - R;
-    if (su == -R || su == R || sv == -R || sv == R) { if (lane == 0) full_store(out, -4.0f); return; }
+    if (su == -R || su == R || sv == -R || sv == R) { if (lane == 0) { full_store(out, -4.0f); full_peak_store<C>(p, gidx, bk); } return; }
     double s2 = 0.0;
     int cnt = 0;
     for (int k = lane; k < NC; k += 64) {
@@ -306,6 +319,7 @@ __device__ __forceinline__ void full_tail(const MatchU8Args &p, const float *val
     const double snr = cnt > 0 ? ((double)bv * (double)bv) / (s2 / (double)cnt) : (double)__builtin_nan("");
     out[0] = du; out[1] = dv; out[2] = bv; out[3] = (float)fit; out[4] = (float)snr;
     out[5] = (float)(2 * c0); out[6] = (float)c1; out[7] = (float)(2 * c2);
+    full_peak_store<C>(p, gidx, bk);
 }
 
 template <class C>
@@ -346,7 +360,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const int u0 = (int)row[0], v0 = (int)row[1];
     // (full mode, a point that breaks the bounds mimc3_match_ncc_full refuses -- only the _dev entry can pass one: no read, all NaN)
     if (C::FULL && (u0 - OCW < 0 || u0 + OCW >= p.W || v0 - OCW < 0 || v0 + OCW >= p.H)) {
-        if (tid == 0) full_store(p.out + 8 * (size_t)gidx, __builtin_nanf(""));
+        if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); }
         return;
     }
     const int64_t pbeg = C::FULL ? 0 : p.piv_off[gidx];
@@ -396,7 +410,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const int csx = Dx2 - 2 * OCW + 1, csy = Dy2 - 2 * OCW + 1;          // compact cells; a climb touches [1, cs - 2]
     const int wu0 = u0 + p.off_u - dx2 + PAD + (C::FULL ? lu : 0), wv0 = v0 + p.off_v - dy2 + PAD + (C::FULL ? lv : 0);   // plane position of window pixel (0, 0)
     if (C::FULL && (wu0 < 0 || wv0 < 0 || wu0 + Dx2 > p.W + 2 * PAD || wv0 + Dy2 > p.H + 2 * PAD)) {
-        if (tid == 0) full_store(p.out + 8 * (size_t)gidx, __builtin_nanf(""));
+        if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); }
         return;
     }
     // ---- what this kernel takes -----------------------------------------------------------------------------------
@@ -459,7 +473,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         const float rc = (float)chip_nulls / (float)NPX;
         const float rw = (float)win_nulls / (float)(Dx2 * Dy2);
         if (rc > max_ratio || rw > max_ratio) {
-            if (tid == 0) full_store(p.out + 8 * (size_t)gidx, -3.0f);
+            if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, -3.0f); full_peak_store<C>(p, gidx, -1); }
             return;
         }
     } else {
@@ -1158,18 +1172,29 @@ hipError_t launch_match_mx(MatchU8Args a, hipStream_t stream)
 
 // Exhaustive search: every point on the matrix cores.  The clean form runs over all points and flags the null-ridden ones for the
 // window-null form (nulls in the search box only) or the general form (chip nulls too), which run right behind in flag mode.
-template <bool GEN, bool CN>
+// (FC: FullCfg, or FullPeakCfg when the caller wants the arg-max cells)
+template <template <int, bool, bool> class FC, bool GEN, bool CN>
 static hipError_t launch_full_form(const MatchU8Args &a, hipStream_t stream)
 {
     switch (a.ocw) {
-    case 7: return mx::launch_one<mx::FullCfg<7, GEN, CN>>(a, stream);
-    case 15: return mx::launch_one<mx::FullCfg<15, GEN, CN>>(a, stream);
-    case 16: return mx::launch_one<mx::FullCfg<16, GEN, CN>>(a, stream);
-    case 30: return mx::launch_one<mx::FullCfg<30, GEN, CN>>(a, stream);
-    case 32: return mx::launch_one<mx::FullCfg<32, GEN, CN>>(a, stream);
-    case 40: return mx::launch_one<mx::FullCfg<40, GEN, CN>>(a, stream);
+    case 7: return mx::launch_one<FC<7, GEN, CN>>(a, stream);
+    case 15: return mx::launch_one<FC<15, GEN, CN>>(a, stream);
+    case 16: return mx::launch_one<FC<16, GEN, CN>>(a, stream);
+    case 30: return mx::launch_one<FC<30, GEN, CN>>(a, stream);
+    case 32: return mx::launch_one<FC<32, GEN, CN>>(a, stream);
+    case 40: return mx::launch_one<FC<40, GEN, CN>>(a, stream);
     default: return hipErrorInvalidValue;
     }
+}
+
+template <template <int, bool, bool> class FC>
+static hipError_t launch_full_forms(MatchU8Args a, hipStream_t stream)
+{
+    hipError_t e = launch_full_form<FC, false, false>(a, stream);
+    a.point_flags = a.mx_flags;
+    if (e == hipSuccess) { a.flag_value = kMxWn; e = launch_full_form<FC, true, false>(a, stream); }
+    if (e == hipSuccess) { a.flag_value = kMxNulls; e = launch_full_form<FC, true, true>(a, stream); }
+    return e;
 }
 
 hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream)
@@ -1178,11 +1203,7 @@ hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream)
     if (!a.mx_flags || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15) return hipErrorInvalidValue;
     a.mx_wn_on = 1; a.mx_gen_on = 1; a.mx_preflag = 0;
     a.point_list = nullptr; a.point_count = nullptr; a.point_flags = nullptr;
-    hipError_t e = launch_full_form<false, false>(a, stream);
-    a.point_flags = a.mx_flags;
-    if (e == hipSuccess) { a.flag_value = kMxWn; e = launch_full_form<true, false>(a, stream); }
-    if (e == hipSuccess) { a.flag_value = kMxNulls; e = launch_full_form<true, true>(a, stream); }
-    return e;
+    return a.full_peak ? launch_full_forms<mx::FullPeakCfg>(a, stream) : launch_full_forms<mx::FullCfg>(a, stream);
 }
 
 }  // namespace mimc3
