@@ -116,7 +116,8 @@ struct mimc3_ctx {
     size_t hslot_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     DevBuf slot[24];                    // mimc3_ctx_workspace: named scratch the drivers built on the ABI keep across calls
     DevBuf ovf_alt[3], fail_alt[3];     // the overflow lists of matcher lanes 1..3: calls on different streams of one context must not share them
-    DevBuf mxl[4];                      // matrix-core kernel: one flag byte per grid point (one buffer per lane)
+    DevBuf mxl[4];                      // matrix-core kernel: one class byte per grid point (one buffer per lane)
+    DevBuf u8l[4];                      // u8_classify: the clean and rest lists of a call with their counts (int32; one buffer per lane)
     mimc3_ctx *cp_child[4] = {nullptr, nullptr, nullptr, nullptr};   // CP stage: one context per image variant for its chip atlas (planes, kernel selection)
     DevBuf cellws;                      // general matcher: global cell-grid workspace for corridors whose cell grid outgrows LDS
     DevBuf raw_dn;                      // raw 8/16-bit DN as uploaded (mimc3_ctx_set_images_u8/_u16), widened on the device
@@ -609,7 +610,7 @@ static int match_dlc(mimc3_ctx *c, const double *d_xy, int32_t xy_stride, int32_
     const int reach_u = max_abs_piv_u + (off_u < 0 ? -off_u : off_u), reach_v = max_abs_piv_v + (off_v < 0 ? -off_v : off_v);
     // the many-pivot kernel forms (the control-point stage's 21x21 pivot set on its two chip sizes) read no tables
     const bool tables_needed = !(max_npiv > 64 && (ocw == 15 || ocw == 30));
-    const int path = choose_path(c, ocw, max_npiv, max_abs_piv_u, max_abs_piv_v, reach_u, reach_v, win_half, tables_needed);
+    int path = choose_path(c, ocw, max_npiv, max_abs_piv_u, max_abs_piv_v, reach_u, reach_v, win_half, tables_needed);
     // that path's plane set, if this pair has not got it yet (complete when the builder returns: see mimc3_ctx)
     if ((path == 5 || path == 1) && tables_needed && !c->sat_u8_ok) RC_TRY(build_u8_tables(c));
     if ((path == 4 || path == 3) && (!c->hpl_valid || (tables_needed && !c->sat_u16_ok))) RC_TRY(build_u16(c, tables_needed));
@@ -638,22 +639,28 @@ static int match_dlc(mimc3_ctx *c, const double *d_xy, int32_t xy_stride, int32_
         // redone by the general kernel right behind, in list mode: no host round trip
         DevBuf &ovf = lane ? c->ovf_alt[lane - 1] : c->ovf;
         HIP_TRY(ovf.reserve(sizeof(int32_t) * ((size_t)N + 1)));
-        HIP_TRY(hipMemsetAsync(ovf.p, 0, sizeof(int32_t), s));
+        if (path != 5) HIP_TRY(hipMemsetAsync(ovf.p, 0, sizeof(int32_t), s));      // (path 5: u8_classify zeroes it)
         u.ovf_count = static_cast<int32_t *>(ovf.p);
         u.ovf_list = u.ovf_count + 1;
         if (path == 5 || path == 1) {
             u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
             u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
             if (path == 5) {
-                // dense correlation surfaces on the matrix cores first; the points that kernel does not take (chips with nulls,
-                // corridors wider than its tile, ...) are redone by the register-tiled kernel in list mode, no host round trip
-                DevBuf &ml = c->mxl[lane];
+                // u8_classify sorts the points once (class bytes, a clean and a rest list in point order); dense correlation surfaces
+                // on the matrix cores over the clean list; the register-tiled kernel over the rest list (chips or windows with nulls,
+                // corridors wider than the tile, and what the matrix-core launch appended) right behind: no memset, no host round trip
+                DevBuf &ml = c->mxl[lane], &ul = c->u8l[lane];
                 HIP_TRY(ml.reserve((size_t)N));
-                HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
+                HIP_TRY(ul.reserve(sizeof(int32_t) * (mimc3::kU8ListHead + 2 * (size_t)N + mimc3::u8_classify_scratch_ints(N))));
+                int32_t *lists = static_cast<int32_t *>(ul.p);
                 u.mx_flags = static_cast<uint8_t *>(ml.p);
-                u.mx_preflag = (max_abs_piv_u > 29 || max_abs_piv_v > 29) ? 1 : 0;      // some corridors may be wider than the kernel's tile
-                e = mimc3::launch_match_mx(u, s);
-                u.point_flags = u.mx_flags; u.flag_value = mimc3::kMxRest;
+                e = mimc3::launch_match_mx(u, lists, s);
+                if (e == hipSuccess) {
+                    u.point_count = lists + 1; u.point_list = lists + mimc3::kU8ListHead + (size_t)N;
+                } else {                // the register-tiled kernel alone, over all points
+                    path = 1;
+                    e = hipMemsetAsync(ovf.p, 0, sizeof(int32_t), s);
+                }
             }
             if (e == hipSuccess) e = mimc3::launch_match_u8(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
         } else if (path == 4 || path == 3) {

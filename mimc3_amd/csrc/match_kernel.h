@@ -66,12 +66,17 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     float *out;
     int32_t *ovf_list, *ovf_count;  // points whose NCC cache overflowed: handed to the general kernel (list mode)
     const int32_t *point_list, *point_count;   // list mode: workgroup b handles point_list[b], b < *point_count (nullptr = all N points)
-    int32_t *fail_list, *fail_count;           // PxU8o only: points whose chip or window does not fit a local 8-bit range
-    // matrix-core kernel (match_mx_kernel.hip): one byte per grid point, zero before the first launch -- kMxNulls = handed from its clean
-    // form to its window-null form, kMxRest = neither form takes the point (plain stores: a shared list counter serialises ~100,000
-    // same-address atomics per launch, measured 1.0 ms)
+    // PxU8o: points whose chip or window does not fit a local 8-bit range.  Matrix-core DLC kernel behind u8_classify: the rest list --
+    // a point the kernel meets but does not take (a climb that leaves the tile or outlasts the recorded scans: a few dozen per launch)
+    // is appended with one atomicAdd, and the register-tiled kernel runs over that list right behind
+    union { int32_t *fail_list; int32_t *rest_list; };
+    union { int32_t *fail_count; int32_t *rest_count; };
+    // matrix-core kernel (match_mx_kernel.hip): one class byte per grid point -- 0 = its clean form takes the point, kMxWn / kMxNulls =
+    // its window-null / general form does, kMxRest = none does.  The DLC path gets every byte from u8_classify (u8_classify_kernel.hip)
+    // before the first launch; the exhaustive search zeroes them and lets the clean form classify (plain stores: a shared list counter
+    // serialises ~100,000 same-address atomics per launch, measured 1.0 ms)
     uint8_t *mx_flags;
-    int32_t mx_preflag;             // the launch may hold corridors wider than the tile: a pre-pass has flagged those points (kMxRest), the kernel leaves them at once
+    int32_t mx_classified;          // DLC path: mx_flags and the point lists come from u8_classify; the clean form runs over point_list and appends what it hands on to rest_list
     int32_t mx_gen_on, mx_wn_on;    // which of its forms for null-ridden points run behind the clean form (general / window nulls only); the others' points get kMxRest
     // flag mode of every kernel of the family: workgroup b handles point b only if point_flags[b] == flag_value
     const uint8_t *point_flags;
@@ -94,6 +99,28 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     int32_t dry_run;                // launcher only: compute the LDS carve and return hipSuccess / hipErrorInvalidValue (does not fit
                                     // 160 KB) without launching -- the C ABI asks this before it commits to a kernel policy
 };
+
+// ---- what the matrix-core DLC kernel takes: shared by its header and by u8_classify, so that the two cannot drift apart ----------
+// The 32 x 32 cell tile of a point whose last pivot is (lu, lv) and whose compact cell grid is csx x csy (a climb touches [1, cs - 2]):
+// all reachable cells if they fit (origin tile0), else centred on the pivots' starts; false = the pivot set is wider than the tile
+__device__ __forceinline__ bool mx_tile_fit(int lu, int lv, int ocw, int dx2, int dy2, int csx, int csy, int tile0, int &tx0, int &ty0)
+{
+    tx0 = tile0; ty0 = tile0;
+    bool fits = true;
+    const int c0x = dx2 - ocw, c1x = c0x + lu, c0y = dy2 - ocw, c1y = c0y + lv;
+    const int lox = min(c0x, c1x), hix = max(c0x, c1x), loy = min(c0y, c1y), hiy = max(c0y, c1y);
+    if (csx - 2 > 32) { tx0 = min(max((lox + hix) / 2 - 15, 1), csx - 2 - 31); fits = fits && lox - 1 >= tx0 && hix + 1 <= tx0 + 31; }
+    if (csy - 2 > 32) { ty0 = min(max((loy + hiy) / 2 - 15, 1), csy - 2 - 31); fits = fits && loy - 1 >= ty0 && hiy + 1 <= ty0 + 31; }
+    return fits;
+}
+// no form of the kernel takes a point with more pivots than a wave has lanes (or none) or a pivot set wider than the tile
+__device__ __forceinline__ bool mx_takes(int npiv, bool fits) { return npiv >= 1 && npiv <= 64 && fits; }
+// the class of a point the kernel could take, from the null counts of the window's written area and of the chip (0 = the clean form's)
+__device__ __forceinline__ uint8_t mx_null_class(int win_nulls, int chip_nulls, int wn_on, int gen_on)
+{
+    if (win_nulls == 0 && chip_nulls == 0) return 0;
+    return (chip_nulls == 0 && wn_on) ? kMxWn : (gen_on ? kMxNulls : kMxRest);
+}
 
 // f32 image -> zero-bordered u8 plane (plane must be pre-zeroed); *d_flag is set to 1 if any pixel
 // is not an integer in [0,255] (then the u8 path must not be used for this image).
@@ -120,9 +147,16 @@ bool match_f32x_supported(int ocw, int max_reach_u, int max_reach_v);
 hipError_t launch_match_f32x(MatchU8Args a, int max_abs_u, int max_abs_v, int max_npiv, hipStream_t stream);
 hipError_t launch_match_u8(MatchU8Args a, int max_abs_u, int max_abs_v, int max_npiv, hipStream_t stream);
 // dense correlation surfaces on the matrix cores (8-bit planes with tables; match_mx_kernel.hip): takes the points whose cell grid
-// fits its tile and whose chip has no null, leaves the others in a.mx_rest_list for launch_match_u8 in list mode
+// fits its tile and whose chip and window have no null.  u8_classify runs first (one thread per point, once per call): it writes every
+// point's class byte and the two index lists in ascending point order -- `lists`: [0] clean count, [1] rest count, [kU8ListHead, + N) the
+// clean list, then N words of rest list and u8_classify_scratch_ints(N) of scratch -- and zeroes a.ovf_count.  The clean form then runs
+// over the clean list and appends what it hands on to the rest list, which is launch_match_u8's in list mode right behind.
 bool match_mx_supported(int ocw, int max_npiv, int win_half, int max_abs_u, int max_abs_v);
-hipError_t launch_match_mx(MatchU8Args a, hipStream_t stream);
+constexpr int kU8ListHead = 4;
+size_t u8_classify_scratch_ints(int N);
+hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream);
+// (u8_classify_kernel.hip; wn_on / gen_on: which forms for null-ridden points run behind the clean form)
+hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, hipStream_t stream);
 // exhaustive-search NCC offsets on the same surfaces (mimc3_match_ncc_full): every point on the matrix cores -- the clean form, then
 // the window-null and general forms over the points it flags (a.mx_flags: N bytes, zero before the call); a.full_R in 1..15,
 // a.ocw one of 7, 15, 16, 30, 32, 40; a.out [N][8]; a.full_peak (optional, int32 [N]) gets every point's arg-max cell k = (su + R)(2R + 1)

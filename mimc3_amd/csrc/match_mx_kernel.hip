@@ -26,10 +26,14 @@
 //     for the cells within 2^13 f64 ulps of an f32 rounding boundary) -> one f32 surface in LDS;
 //   * the climb of every pivot on the complete surface (lane k = pivot k), the exact replay of the reference's sequential
 //     visited-set semantics (:691-753) and the 3x3 fit (:757-788) as in match_px_kernel.hip -- on wave 0, wave 1 has left by then.
-// What this kernel does not take it hands on through a flag byte per grid point (no host round trip, no shared counter: same-address
-// atomics of 100,000 points serialise into a millisecond): a point with nulls in its window or chip, more than 64 pivots, a pivot
-// set wider than the tile, a climb that leaves the tile or outlasts the 16 recorded scans is flagged for the register-tiled kernel
-// (match_px_kernel.hip), which runs right behind in flag mode (or for this kernel's other forms, when they are switched on).
+// What this kernel does not take goes to the register-tiled kernel (match_px_kernel.hip) without a host round trip.  A point with nulls
+// in its window or chip, more than 64 pivots or a pivot set wider than the tile is known from table queries before any kernel runs:
+// u8_classify (u8_classify_kernel.hip, one thread per point, once per call) writes the class byte of every point and two index lists
+// in ascending point order, and this kernel's DLC launch runs over the clean list only -- a point it does not take never issues a
+// tile or chip load.  A climb that leaves the tile or outlasts the 16 recorded scans (a few dozen points per launch) is only known
+// here: such a point is appended to the rest list with one atomicAdd, and the register-tiled kernel runs over that list right behind.
+// (The exhaustive search classifies in the clean form's header and hands on through the class byte alone: every one of its points
+// stays on this kernel's forms, which run behind in flag mode.)
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <mutex>
@@ -337,8 +341,11 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     int gidx = blockIdx.x;
-    if (p.point_list) {                                      // list mode: the points another kernel handed over
-        if (gidx >= *p.point_count) return;
+    if (p.point_list) {                                      // list mode: the clean list of u8_classify (the launch is sized for all N points)
+        const int cnt = *p.point_count;
+        if (gidx >= cnt) return;
+        const int per = cnt >> 3;
+        if (gidx < per * 8) gidx = (gidx & 7) * per + (gidx >> 3);              // XCD-contiguous order of the list positions
         gidx = p.point_list[gidx];
     } else {
         const int nb = gridDim.x, per = nb >> 3;
@@ -346,9 +353,11 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     }
     if (gidx >= p.N) return;
     if (p.point_flags && p.point_flags[gidx] != (uint8_t)p.flag_value) return;      // flag mode: the points another kernel handed over
-    if (p.mx_preflag && p.mx_flags[gidx] == kMxRest) return;                         // flagged by mx_preflag_kernel: corridor wider than the tile
     auto hand_on = [&](uint8_t to) __attribute__((always_inline)) {
-        if (tid == 0) p.mx_flags[gidx] = to;
+        if (tid == 0) {
+            p.mx_flags[gidx] = to;
+            if (!C::FULL && p.mx_classified && to == kMxRest) p.rest_list[atomicAdd(p.rest_count, 1)] = gidx;
+        }
     };
 
     const unsigned char *chip_pl = p.swap ? p.p1 : p.p0;
@@ -415,14 +424,8 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     }
     // ---- what this kernel takes -----------------------------------------------------------------------------------
     // the tile: all reachable cells if they fit, else centred on the pivots' starts (a scan that leaves it hands the point on)
-    int tx0 = C::FULL ? 0 : 1, ty0 = C::FULL ? 0 : 1;
-    bool fits = true;
-    {
-        const int c0x = dx2 - OCW, c1x = c0x + lu, c0y = dy2 - OCW, c1y = c0y + lv;
-        const int lox = min(c0x, c1x), hix = max(c0x, c1x), loy = min(c0y, c1y), hiy = max(c0y, c1y);
-        if (csx - 2 > 32) { tx0 = min(max((lox + hix) / 2 - 15, 1), csx - 2 - 31); fits = fits && lox - 1 >= tx0 && hix + 1 <= tx0 + 31; }
-        if (csy - 2 > 32) { ty0 = min(max((loy + hiy) / 2 - 15, 1), csy - 2 - 31); fits = fits && loy - 1 >= ty0 && hiy + 1 <= ty0 + 31; }
-    }
+    int tx0, ty0;
+    const bool fits = mx_tile_fit(lu, lv, OCW, dx2, dy2, csx, csy, C::FULL ? 0 : 1, tx0, ty0);
     // the null count of the window's written area (:869-886) and the first batch of the tile's pixels: issued now, read below
     const int win_nulls_v = sat_nulls_u8(sat_win, p.sat_ws, wu0, wv0, C::FULL ? Dx2 : 2 * dx2, C::FULL ? Dy2 : 2 * dy2, lane);      // (exact for any window size; full mode: the whole search box)
     constexpr int NSEG = C::SW / 16, TTASK = C::KW * NSEG;           // (tile rows >= KW and columns >= SW are only ever weighted 0: left as they are)
@@ -458,10 +461,14 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
 
     const int chip_nulls = (int)(chipQ >> kSatNullShift8);
     const int win_nulls = __builtin_amdgcn_readfirstlane(win_nulls_v);
-    if (npiv > 64 || !fits) { hand_on(kMxRest); return; }
-    if (!GEN && (win_nulls != 0 || chip_nulls != 0)) {
-        hand_on((chip_nulls == 0 && p.mx_wn_on) ? kMxWn : (p.mx_gen_on ? kMxNulls : kMxRest));
-        return;
+    // (behind u8_classify these two tests never fire on a listed point -- they are its own, from the same helpers; they stay as the
+    //  guard of a launch whose list did not come from it.  The guard decides who computes the point, it does not protect the loads
+    //  above: the last pivot was read at pv_g + 2 (npiv - 1) before it, so a point without pivots has already read 8 bytes in front
+    //  of its range, as it always did -- the C ABI refuses empty pivot lists, and the classifier tests npiv before it reads)
+    if (!mx_takes(npiv, fits)) { hand_on(kMxRest); return; }
+    if (!GEN) {
+        const uint8_t cls = mx_null_class(win_nulls, chip_nulls, p.mx_wn_on, p.mx_gen_on);
+        if (cls != 0) { hand_on(cls); return; }
     }
     // general form: wn = the written area of the window holds nulls (then the never-written last row / column are nulls like any other,
     // else they are applied in closed form as in the clean form); cn = the chip holds nulls
@@ -1051,28 +1058,6 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     MIMC3_MX_STATS_OUT
 }
 
-// Pre-pass for launches whose longest corridor exceeds the tile (one thread per grid point): flags the points the kernel below would
-// hand on for that reason -- the same placement test as in its header -- so that they cost it one byte load instead of a header's
-// two memory round trips (BASELINE C4, where every point is such a point: 161.1 -> 159.9 ms per pass).
-__global__ __launch_bounds__(256) void mx_preflag_kernel(MatchU8Args p)
-{
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= p.N) return;
-    const int64_t pbeg = p.piv_off[g];
-    const int npiv = (int)(p.piv_off[g + 1] - pbeg);
-    if (npiv < 1) return;
-    const int OCW = p.ocw;
-    const int lu = p.piv_uv[2 * (pbeg + npiv - 1)], lv = p.piv_uv[2 * (pbeg + npiv - 1) + 1];
-    const int dx2 = (lu < 0 ? -lu : lu) + OCW + 2, dy2 = (lv < 0 ? -lv : lv) + OCW + 2;
-    const int csx = 2 * dx2 + 1 - 2 * OCW + 1, csy = 2 * dy2 + 1 - 2 * OCW + 1;
-    bool fits = true;
-    const int c0x = dx2 - OCW, c1x = c0x + lu, c0y = dy2 - OCW, c1y = c0y + lv;
-    const int lox = min(c0x, c1x), hix = max(c0x, c1x), loy = min(c0y, c1y), hiy = max(c0y, c1y);
-    if (csx - 2 > 32) { const int tx0 = min(max((lox + hix) / 2 - 15, 1), csx - 2 - 31); fits = fits && lox - 1 >= tx0 && hix + 1 <= tx0 + 31; }
-    if (csy - 2 > 32) { const int ty0 = min(max((loy + hiy) / 2 - 15, 1), csy - 2 - 31); fits = fits && loy - 1 >= ty0 && hiy + 1 <= ty0 + 31; }
-    if (npiv > 64 || !fits) p.mx_flags[g] = kMxRest;
-}
-
 template <class C>
 static hipError_t launch_one(MatchU8Args a, hipStream_t stream)
 {
@@ -1115,6 +1100,25 @@ static hipError_t launch_one(MatchU8Args a, hipStream_t stream)
     return hipGetLastError();
 }
 
+// diagnostics (MIMC3_MX_STATS): the classes and list lengths as u8_classify left them, before any matcher launch touches them
+static hipError_t classify_stats(const MatchU8Args &a, const int32_t *lists, hipStream_t stream)
+{
+    static const bool want_stats = getenv("MIMC3_MX_STATS") != nullptr;
+    if (!want_stats) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    unsigned char *hf = (unsigned char *)malloc((size_t)a.N);
+    int32_t head[2] = {0, 0};
+    (void)hipMemcpy(hf, a.mx_flags, (size_t)a.N, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(head, lists, sizeof(head), hipMemcpyDeviceToHost);
+    int n[4] = {0, 0, 0, 0};
+    for (int i = 0; i < a.N; i++) n[hf[i] & 3]++;
+    free(hf);
+    fprintf(stderr, "[mimc3 mx stats] u8_classify: classes clean %d rest %d nulls %d window-nulls %d; lists clean %d rest %d\n", n[0], n[kMxRest],
+            n[kMxNulls], n[kMxWn], head[0], head[1]);
+    return hipSuccess;
+}
+
 }  // namespace mx
 
 bool match_mx_supported(int ocw, int max_npiv, int win_half, int max_abs_u, int max_abs_v)
@@ -1124,9 +1128,9 @@ bool match_mx_supported(int ocw, int max_npiv, int win_half, int max_abs_u, int 
     if (win_half > 0) return false;                   // full-square search areas (control-point stage): many pivots, not this kernel
     // A point whose pivots (with the ring of cells their first scans touch) do not fit the 32 x 32 tile is flagged for the
     // register-tiled kernel by the kernel itself, point by point: a velocity field with a few fast points keeps its slow ones here.
-    // (A launch whose every corridor is too long -- BASELINE C4: 31 pivots -- only passes through: mx_preflag_kernel marks such points
-    // beforehand and the kernel leaves them after one byte load; 158.0 -> 159.9 ms per pass at C4, 161.1 without the pre-pass.)  The launch's
-    // maxima still size the register-tiled kernel's LDS carve, as without this kernel.
+    // (A launch whose every corridor is too long -- BASELINE C4: 31 pivots -- only passes through: u8_classify puts every point on the
+    // rest list and this kernel's workgroups leave after one scalar load.)  The launch's maxima still size the register-tiled kernel's
+    // LDS carve, as without this kernel.
     (void)max_abs_u; (void)max_abs_v;
     if (max_npiv > 64) return false;                  // (the many-pivot kernel forms: no tables)
     return ocw == 7 || ocw == 15 || ocw == 16 || ocw == 30 || ocw == 32 || ocw == 40;
@@ -1146,12 +1150,12 @@ static hipError_t launch_form(const MatchU8Args &a, hipStream_t stream)
     }
 }
 
-// Up to three launches: the clean form over all points (or the caller's list), then the forms for the points it flagged.  Points none
-// takes carry kMxRest in mx_flags afterwards.
-hipError_t launch_match_mx(MatchU8Args a, hipStream_t stream)
+// u8_classify, then up to three launches: the clean form over the clean list, then the forms for the other classes in flag mode.  Points
+// none takes are on the rest list afterwards (and carry kMxRest in mx_flags).
+hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
-    if (!a.mx_flags || !a.sat0 || !a.sat1) return hipErrorInvalidValue;
+    if (!a.mx_flags || !a.sat0 || !a.sat1 || !lists || !a.ovf_count) return hipErrorInvalidValue;
     // Which null-ridden points stay on the matrix cores: none by default.  Both forms for them are built, tested and bit-identical at
     // every chip size, but measured at BASELINE C2 (ns per point; the register-tiled kernel's sparse corrections: 18 at ocw 16, 66 at
     // ocw 40) the window-null form (null-free chip: four correlations) costs 16 and leaves that kernel the chip-null points alone, which
@@ -1162,8 +1166,14 @@ hipError_t launch_match_mx(MatchU8Args a, hipStream_t stream)
     static const int gen_env = getenv("MIMC3_MX_GEN") ? atoi(getenv("MIMC3_MX_GEN")) : 0;
     a.mx_wn_on = wn_env > 0 ? 1 : 0;
     a.mx_gen_on = gen_env != 0 ? 1 : 0;
-    if (a.mx_preflag) hipLaunchKernelGGL(mx::mx_preflag_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, stream, a);
-    hipError_t e = launch_form<false, false>(a, stream);
+    a.mx_classified = 1;
+    a.point_flags = nullptr;
+    a.point_count = lists; a.point_list = lists + kU8ListHead;
+    a.rest_count = lists + 1; a.rest_list = lists + kU8ListHead + (size_t)a.N;
+    hipError_t e = launch_u8_classify(a, lists, stream);
+    if (e == hipSuccess) e = mx::classify_stats(a, lists, stream);
+    if (e == hipSuccess) e = launch_form<false, false>(a, stream);
+    a.point_list = nullptr; a.point_count = nullptr;
     a.point_flags = a.mx_flags;
     if (e == hipSuccess && a.mx_wn_on) { a.flag_value = kMxWn; e = launch_form<true, false>(a, stream); }
     if (e == hipSuccess && a.mx_gen_on) { a.flag_value = kMxNulls; e = launch_form<true, true>(a, stream); }
@@ -1201,7 +1211,7 @@ hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
     if (!a.mx_flags || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15) return hipErrorInvalidValue;
-    a.mx_wn_on = 1; a.mx_gen_on = 1; a.mx_preflag = 0;
+    a.mx_wn_on = 1; a.mx_gen_on = 1; a.mx_classified = 0;
     a.point_list = nullptr; a.point_count = nullptr; a.point_flags = nullptr;
     return a.full_peak ? launch_full_forms<mx::FullPeakCfg>(a, stream) : launch_full_forms<mx::FullCfg>(a, stream);
 }

@@ -738,8 +738,14 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
     constexpr int OCW = C::OCW, CW = C::CW, GPR = C::GPR, NT = C::NT, NW = C::NW;
 
     int gidx = blockIdx.x;
-    if (p.point_list) {                                      // list mode: the points another kernel handed over
-        if (gidx >= *p.point_count) return;
+    // list mode: the points another kernel handed over (u8_classify's rest list, the matrix-core kernel's hand-on list, PxU8o's fail
+    // list into PxU16, ...).  Every such launch is sized for all N points, and every one gets the permutation below: it is a bijection on
+    // [0, 8 (cnt >> 3)), so a list in atomic-append order is merely walked in another order
+    if (p.point_list) {
+        const int cnt = *p.point_count;
+        if (gidx >= cnt) return;
+        const int per = cnt >> 3;
+        if (gidx < per * 8) gidx = (gidx & 7) * per + (gidx >> 3);              // XCD-contiguous order of the list positions
         gidx = p.point_list[gidx];
     } else {
         const int nb = gridDim.x, per = nb >> 3;

@@ -67,4 +67,15 @@ __device__ __forceinline__ int sat_nulls_u8(const unsigned long long *__restrict
     return cnt;
 }
 
+// the same count by one thread alone (u8_classify: one point per thread); the same cut into sub-boxes, summed serially
+__device__ __forceinline__ int sat_nulls_u8_thread(const unsigned long long *__restrict__ S, int Ws, int x, int y, int w, int h)
+{
+    if (w * h <= 8224) return (int)(sat_box(S, Ws, x, y, w, h) >> kSatNullShift8);
+    int cnt = 0;
+    for (int j = 0; j < h; j += 64)
+        for (int i = 0; i < w; i += 64)
+            cnt += (int)(sat_box(S, Ws, x + i, y + j, w - i < 64 ? w - i : 64, h - j < 64 ? h - j : 64) >> kSatNullShift8);
+    return cnt;
+}
+
 }  // namespace mimc3

@@ -1,0 +1,126 @@
+// u8_classify_kernel.hip -- which kernel takes which grid point of a DLC matcher call on an 8-bit pair, decided once per call.
+//
+// The matrix-core kernel (match_mx_kernel.hip) takes a point whose pivot set fits its 32 x 32 cell tile and whose chip and window hold
+// no null pixel; the register-tiled kernel (match_px_kernel.hip) takes the rest.  All of that follows from the point's pivots and two
+// table queries, so it is evaluated here by one thread per point -- with the helpers the matrix-core kernel's header uses
+// (mx_tile_fit, mx_takes, mx_null_class in match_kernel.h; the packed tables of sat_kernel.h) -- instead of by a 128-thread workgroup
+// per point that has already issued its first tile and chip loads.  Two launches:
+//   u8_classify_count   the class byte of every point (this store replaces the memset of the bytes) and, per block of 256 points,
+//                       how many are clean (class 0) and how many are the register-tiled kernel's (kMxRest); zeroes the overflow counter
+//   u8_classify_fill    the two index lists in ascending point order: a block sums the counts of the blocks before it (a few hundred
+//                       words), ranks its own points by ballot, and writes them; the last block writes the two list lengths
+// No same-address atomic per point (100,000 of them serialise into a millisecond) and no spinning on another block: the order inside
+// both lists is the point order, whatever the order the blocks run in.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "match_kernel.h"
+#include "sat_kernel.h"
+
+namespace mimc3 {
+
+namespace {
+
+constexpr int kClsThreads = 256, kClsWaves = kClsThreads / 64;
+
+__device__ __forceinline__ uint8_t classify_point(const MatchU8Args &p, int g)
+{
+    const int OCW = p.ocw, CW = 2 * OCW + 1, PAD = p.pad;
+    typedef unsigned long long SatT;
+    const SatT *sat_chip = reinterpret_cast<const SatT *>(p.swap ? p.sat1 : p.sat0);
+    const SatT *sat_win = reinterpret_cast<const SatT *>(p.swap ? p.sat0 : p.sat1);
+    // the loads that depend on nothing but g go out together, the chip's query (as the matrix-core header issues it for every point it
+    // meets) behind the point row and beside the last pivot: three memory round trips per point, not four
+    const int64_t pbeg = p.piv_off[g];
+    const int npiv = (int)(p.piv_off[g + 1] - pbeg);
+    const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)g + p.xy_col;
+    const int u0 = (int)row[0], v0 = (int)row[1];
+    int2 last = make_int2(0, 0);
+    if (npiv >= 1) last = *reinterpret_cast<const int2 *>(p.piv_uv + 2 * (pbeg + npiv - 1));      // (no pivot: nothing to read the search area from)
+    const int chip_nulls = (int)(sat_box(sat_chip, p.sat_ws, u0 - OCW + PAD, v0 - OCW + PAD, CW, CW) >> kSatNullShift8);
+    if (npiv < 1 || npiv > 64) return kMxRest;
+    const int lu = last.x, lv = last.y;
+    const int dx2 = (lu < 0 ? -lu : lu) + OCW + 2, dy2 = (lv < 0 ? -lv : lv) + OCW + 2;
+    const int csx = 2 * dx2 + 1 - 2 * OCW + 1, csy = 2 * dy2 + 1 - 2 * OCW + 1;
+    int tx0, ty0;
+    if (!mx_takes(npiv, mx_tile_fit(lu, lv, OCW, dx2, dy2, csx, csy, 1, tx0, ty0))) return kMxRest;
+    // the window's written area (its last row and column are never written, MIMC_module.c:869-886)
+    const int win_nulls = sat_nulls_u8_thread(sat_win, p.sat_ws, u0 + p.off_u - dx2 + PAD, v0 + p.off_v - dy2 + PAD, 2 * dx2, 2 * dy2);
+    return mx_null_class(win_nulls, chip_nulls, p.mx_wn_on, p.mx_gen_on);
+}
+
+// the block's number of set predicates, in every thread (wave ballots, one LDS word per wave); *before = those of the lower threads
+__device__ __forceinline__ int block_rank(bool on, int *wsum, int *before)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(on);
+    if (lane == 0) wsum[wave] = __popcll(m);
+    __syncthreads();
+    int total = 0, lower = 0;
+#pragma unroll
+    for (int w = 0; w < kClsWaves; w++) { const int c = wsum[w]; total += c; lower += w < wave ? c : 0; }
+    *before = lower + __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();
+    return total;
+}
+
+__global__ __launch_bounds__(kClsThreads) void u8_classify_count(MatchU8Args p, int32_t *blk)
+{
+    __shared__ int wsum[kClsWaves];
+    const int g = blockIdx.x * kClsThreads + threadIdx.x;
+    uint8_t cls = 0xff;
+    if (g < p.N) { cls = classify_point(p, g); p.mx_flags[g] = cls; }
+    int before;
+    const int nclean = block_rank(cls == 0, wsum, &before);
+    const int nrest = block_rank(cls == kMxRest, wsum, &before);
+    if (threadIdx.x == 0) {
+        blk[2 * blockIdx.x] = nclean; blk[2 * blockIdx.x + 1] = nrest;
+        if (blockIdx.x == 0) *p.ovf_count = 0;
+    }
+}
+
+__global__ __launch_bounds__(kClsThreads) void u8_classify_fill(MatchU8Args p, const int32_t *blk, int32_t *lists)
+{
+    __shared__ int wsum[kClsWaves];
+    __shared__ int base[2];
+    const int g = blockIdx.x * kClsThreads + threadIdx.x;
+    if (threadIdx.x < 2) base[threadIdx.x] = 0;
+    __syncthreads();
+    {   // the counts of the blocks before this one
+        int c0 = 0, c1 = 0;
+        for (int b = threadIdx.x; b < (int)blockIdx.x; b += kClsThreads) { c0 += blk[2 * b]; c1 += blk[2 * b + 1]; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_xor(c0, o, 64); c1 += __shfl_xor(c1, o, 64); }
+        if ((threadIdx.x & 63) == 0 && (c0 | c1)) { atomicAdd(&base[0], c0); atomicAdd(&base[1], c1); }      // (LDS, integer: any order gives the same sum)
+    }
+    __syncthreads();
+    const int b0 = base[0], b1 = base[1];
+    const uint8_t cls = g < p.N ? p.mx_flags[g] : 0xff;
+    int *clean = lists + kU8ListHead, *rest = lists + kU8ListHead + (size_t)p.N;
+    int r;
+    const int nclean = block_rank(cls == 0, wsum, &r);
+    if (cls == 0) clean[b0 + r] = g;
+    const int nrest = block_rank(cls == kMxRest, wsum, &r);
+    if (cls == kMxRest) rest[b1 + r] = g;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) { lists[0] = b0 + nclean; lists[1] = b1 + nrest; }
+}
+
+}  // namespace
+
+static inline unsigned classify_blocks(int N) { return (unsigned)((N + kClsThreads - 1) / kClsThreads); }
+
+size_t u8_classify_scratch_ints(int N) { return 2 * (size_t)classify_blocks(N); }
+
+hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, hipStream_t stream)
+{
+    if (a.N <= 0) return hipSuccess;
+    if (!a.mx_flags || !a.sat0 || !a.sat1 || !a.ovf_count || !lists || !a.piv_uv || !a.piv_off) return hipErrorInvalidValue;
+    int32_t *blk = lists + kU8ListHead + 2 * (size_t)a.N;
+    const unsigned nb = classify_blocks(a.N);
+    hipLaunchKernelGGL(u8_classify_count, dim3(nb), dim3(kClsThreads), 0, stream, a, blk);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(u8_classify_fill, dim3(nb), dim3(kClsThreads), 0, stream, a, static_cast<const int32_t *>(blk), lists);
+    return hipGetLastError();
+}
+
+}  // namespace mimc3
