@@ -338,10 +338,15 @@ static void quadfit_origin(const int32_t *xy, const double *z, const double *w, 
 /* In place on dpf/dpf_dx/dpf_dy ([dimy][dimx]).  mvn: padded [N][Kmax][5]; nclus[N].
  * max_sweeps: the reference's loop bound is NOI<=100, i.e. up to 101 sweeps (pass 101 to mirror).
  * stats[0]=sweeps run (the reference's NOI at exit), stats[1]=points processed in total,
- * stats[2]=points skipped by the T7 definition (NaN fit / no candidate). */
-int orc_qm_pseudosmooth(int32_t dimy, int32_t dimx, int32_t *dpf, float *dpf_dx, float *dpf_dy,
-                        const int32_t *ruv, int32_t nn, const float *mvn, int32_t Kmax,
-                        const int32_t *nclus, const double *xyuvav, int32_t max_sweeps, int64_t *stats)
+ * stats[2]=points skipped by the T7 definition (NaN fit / no candidate),
+ * stats[3]=why the loop ended: 0 no point changed in the last sweep, 1 fluctuation (the next mask equals an earlier
+ * one, :2237-2268), 2 the sweep cap; stats[4]/stats[5]=highest/lowest index of an earlier mask equal to the next
+ * one at a fluctuation stop, else -1.  orc_qm_pseudosmooth_fit additionally writes the last (fit0, fit1) of every
+ * point that reached the fit (NaN elsewhere) to fit_out [N][2] when it is not NULL. */
+int orc_qm_pseudosmooth_fit(int32_t dimy, int32_t dimx, int32_t *dpf, float *dpf_dx, float *dpf_dy,
+                            const int32_t *ruv, int32_t nn, const float *mvn, int32_t Kmax,
+                            const int32_t *nclus, const double *xyuvav, int32_t max_sweeps, int64_t *stats,
+                            double *fit_out)
 {
     const int32_t N = dimx * dimy;
     const double eig0 = 1500.0 / 300.0, eig1 = eig0 / 3.0;
@@ -352,7 +357,8 @@ int orc_qm_pseudosmooth(int32_t dimy, int32_t dimx, int32_t *dpf, float *dpf_dx,
     int32_t *nxy = (int32_t *)malloc(sizeof(int32_t) * 2 * nn);
     double *nz = (double *)malloc(sizeof(double) * 2 * nn), *nw = (double *)malloc(sizeof(double) * nn);
     const float nanv = sqrt(-1.0);
-    int64_t processed = 0, skipped = 0;
+    int64_t processed = 0, skipped = 0, cause = 0, hit_hi = -1, hit_lo = -1;
+    if (fit_out) for (int32_t i = 0; i < 2 * N; i++) fit_out[i] = nanv;
     for (int32_t i = 0; i < N; i++) {                                   /* :2029-2055 */
         int32_t id = dpf[i];
         mask0[i] = (id >= 0 && !(mvn[((size_t)i * Kmax + id) * 5 + 4] >= 0.6)) ? 1 : 0;
@@ -390,6 +396,7 @@ int orc_qm_pseudosmooth(int32_t dimy, int32_t dimx, int32_t *dpf, float *dpf_dx,
                                   itm3 * nxy[2 * o + 1] * nxy[2 * o + 1]));
                 double fit[2];
                 quadfit_origin(nxy, nz, nw, n, fit);
+                if (fit_out) { fit_out[2 * (size_t)idx] = fit[0]; fit_out[2 * (size_t)idx + 1] = fit[1]; }
                 const int32_t id = dpf[idx], nc = nclus[idx];
                 const float *cl = mvn + (size_t)idx * Kmax * 5;
                 double dmin = 1E+37; int32_t best = -1;
@@ -414,17 +421,26 @@ int orc_qm_pseudosmooth(int32_t dimy, int32_t dimx, int32_t *dpf, float *dpf_dx,
                 bx[i] = nanv; by[i] = nanv; bid[i] = -1;
             }
         int fluct = 0;                                                  /* :2237-2268 */
-        for (int32_t s = noi - 1; s >= 0 && !fluct; s--)
-            if (memcmp(stack[s], next, N) == 0) fluct = 1;
-        if (fluct) { noi--; break; }
+        for (int32_t s = noi - 1; s >= 0; s--)          /* the decision needs one match; every index is looked at for stats */
+            if (memcmp(stack[s], next, N) == 0) { if (!fluct) hit_hi = s; hit_lo = s; fluct = 1; }
+        if (fluct) { noi--; cause = 1; break; }
         stack[noi] = (uint8_t *)malloc(N); memcpy(stack[noi], next, N);
         memcpy(mask, next, N);
     }
-    if (stats) { stats[0] = noi; stats[1] = processed; stats[2] = skipped; }
+    if (cause == 0 && any) cause = 2;
+    if (stats) { stats[0] = noi; stats[1] = processed; stats[2] = skipped; stats[3] = cause; stats[4] = hit_hi; stats[5] = hit_lo; }
     for (int32_t s = 0; s <= max_sweeps + 1; s++) free(stack[s]);
     free(stack); free(mask0); free(mask); free(next); free(bx); free(by); free(bid);
     free(nxy); free(nz); free(nw);
     return 0;
+}
+
+/* stats: int64[6] */
+int orc_qm_pseudosmooth(int32_t dimy, int32_t dimx, int32_t *dpf, float *dpf_dx, float *dpf_dy,
+                        const int32_t *ruv, int32_t nn, const float *mvn, int32_t Kmax,
+                        const int32_t *nclus, const double *xyuvav, int32_t max_sweeps, int64_t *stats)
+{
+    return orc_qm_pseudosmooth_fit(dimy, dimx, dpf, dpf_dx, dpf_dy, ruv, nn, mvn, Kmax, nclus, xyuvav, max_sweeps, stats, NULL);
 }
 
 int orc_num_threads(void)
@@ -518,9 +534,11 @@ void orc_get_dpf0(const float *mvn, const int32_t *nclus, int32_t N, int32_t Kma
 }
 
 /* get_dpf1 (:1330-1718): a-priori-scaled neighbour interpolation of the unassigned points (Jacobi sweeps),
- * 3x3 smoothing, snap to the nearest cluster.  dpf in/out, dx/dy out.  Returns the sweep count (NOI). */
-int32_t orc_get_dpf1(int32_t dimy, int32_t dimx, int32_t *dpf, float *dx, float *dy, const int32_t *ruv, int32_t nn,
-                     const float *mvn, int32_t Kmax, const int32_t *nclus, const double *xyuvav, float dt, float mpp)
+ * 3x3 smoothing, snap to the nearest cluster.  dpf in/out, dx/dy out.  Returns the sweep count (NOI: every pass
+ * over the grid, the last, empty one of each level included); orc_get_dpf1_sweeps also stores it in *sweeps_out. */
+int32_t orc_get_dpf1_sweeps(int32_t dimy, int32_t dimx, int32_t *dpf, float *dx, float *dy, const int32_t *ruv, int32_t nn,
+                            const float *mvn, int32_t Kmax, const int32_t *nclus, const double *xyuvav, float dt, float mpp,
+                            int32_t *sweeps_out)
 {
     const int32_t N = dimx * dimy;
     const float nanv = sqrt(-1.0);
@@ -638,7 +656,14 @@ int32_t orc_get_dpf1(int32_t dimy, int32_t dimx, int32_t *dpf, float *dx, float 
         dpf[g] = id; dx[g] = m[5 * id]; dy[g] = m[5 * id + 1];
     }
     free(bx); free(by); free(noi); free(v);
+    if (sweeps_out) *sweeps_out = NOI;
     return NOI;
+}
+
+int32_t orc_get_dpf1(int32_t dimy, int32_t dimx, int32_t *dpf, float *dx, float *dy, const int32_t *ruv, int32_t nn,
+                     const float *mvn, int32_t Kmax, const int32_t *nclus, const double *xyuvav, float dt, float mpp)
+{
+    return orc_get_dpf1_sweeps(dimy, dimx, dpf, dx, dy, ruv, nn, mvn, Kmax, nclus, xyuvav, dt, mpp, NULL);
 }
 
 /* =======================================================================================

@@ -54,6 +54,13 @@ class Oracle:
             self._qm.restype = C.c_int
             self._qm.argtypes = [C.c_int32, C.c_int32, _i32p, _f32p, _f32p, _i32p, C.c_int32, _f32p, C.c_int32,
                                  _i32p, _f64p, C.c_int32, _i64p]
+            self._qm_fit = self.lib.orc_qm_pseudosmooth_fit
+            self._qm_fit.restype = C.c_int
+            self._qm_fit.argtypes = self._qm.argtypes + [_f64p]
+            self._d1s = self.lib.orc_get_dpf1_sweeps
+            self._d1s.restype = C.c_int32
+            self._d1s.argtypes = [C.c_int32, C.c_int32, _i32p, _f32p, _f32p, _i32p, C.c_int32, _f32p, C.c_int32, _i32p,
+                                  _f64p, C.c_float, C.c_float, C.POINTER(C.c_int32)]
         else:
             self._qm = self.lib.ref_get_dpf_pseudosmoothing
             self._qm.restype = C.c_int
@@ -130,8 +137,13 @@ class Oracle:
         return np.ascontiguousarray(ruv[:nn])
 
     # -- a9/a10 -----------------------------------------------------------------------------
-    def qm(self, dpf, dpf_dx, dpf_dy, ruv, mvn, nclus, xyuvav, max_sweeps=101):
-        """Returns (dpf, dx, dy, stats) -- copies; inputs untouched. stats is None for the reference."""
+    QM_STOP_UNCHANGED, QM_STOP_FLUCTUATION, QM_STOP_CAP = 0, 1, 2
+
+    def qm(self, dpf, dpf_dx, dpf_dy, ruv, mvn, nclus, xyuvav, max_sweeps=101, fit=False):
+        """Returns (dpf, dx, dy, stats) -- copies; inputs untouched. stats is None for the reference, else int64[6]:
+        sweeps, points processed, points skipped by T7, stop cause (QM_STOP_*), highest and lowest index of the earlier
+        mask that the next one equalled at a fluctuation stop (-1 otherwise).  fit=True (port only) appends the last
+        fitted (fit0, fit1) per point [dimy][dimx][2], NaN where no fit was made."""
         dimy, dimx = dpf.shape
         d = np.array(dpf, np.int32, order="C")
         x = np.array(dpf_dx, np.float32, order="C")
@@ -142,7 +154,11 @@ class Oracle:
         xy = np.ascontiguousarray(xyuvav, np.float64)
         kmax = mvn.shape[1]
         if self.kind == "port":
-            stats = np.zeros(3, np.int64)
+            stats = np.zeros(6, np.int64)
+            if fit:
+                f = np.zeros((dimy, dimx, 2), np.float64)
+                self._qm_fit(dimy, dimx, d, x, y, ruv, ruv.shape[0], mvn, kmax, nclus, xy, max_sweeps, stats, f)
+                return d, x, y, stats, f
             self._qm(dimy, dimx, d, x, y, ruv, ruv.shape[0], mvn, kmax, nclus, xy, max_sweeps, stats)
             return d, x, y, stats
         self._qm(dimy, dimx, d, x, y, ruv, ruv.shape[0], mvn, kmax, nclus, xy)
@@ -170,16 +186,23 @@ class Oracle:
             self._d0(mvn, nclus, dimx, dimy, mvn.shape[1], min_ratio, dpf)
         return dpf.reshape(dimy, dimx)
 
-    def get_dpf1(self, dpf0, ruv, mvn, nclus, xyuvav, dt, mpp):
-        """get_dpf1 (:1330-1718) -> (dpf, dx, dy); inputs untouched."""
+    def get_dpf1(self, dpf0, ruv, mvn, nclus, xyuvav, dt, mpp, sweeps=False):
+        """get_dpf1 (:1330-1718) -> (dpf, dx, dy); inputs untouched.  sweeps=True (port only) appends the number of
+        passes over the grid (the reference's NOI; the library's get_dpf1 reports the same count)."""
         dimy, dimx = dpf0.shape
         d = np.array(dpf0, np.int32, order="C")
         x = np.zeros((dimy, dimx), np.float32)
         y = np.zeros((dimy, dimx), np.float32)
         ruv = np.ascontiguousarray(ruv, np.int32)
         mvn = np.ascontiguousarray(mvn, np.float32)
-        self._d1(dimy, dimx, d.reshape(-1), x.reshape(-1), y.reshape(-1), ruv, ruv.shape[0], mvn, mvn.shape[1],
-                 np.ascontiguousarray(nclus, np.int32), np.ascontiguousarray(xyuvav, np.float64), dt, mpp)
+        args = (dimy, dimx, d.reshape(-1), x.reshape(-1), y.reshape(-1), ruv, ruv.shape[0], mvn, mvn.shape[1],
+                np.ascontiguousarray(nclus, np.int32), np.ascontiguousarray(xyuvav, np.float64), dt, mpp)
+        if sweeps:
+            assert self.kind == "port"
+            n = C.c_int32(-1)
+            self._d1s(*args, C.byref(n))
+            return d, x, y, n.value
+        self._d1(*args)
         return d, x, y
 
     # -- N2 ---------------------------------------------------------------------------------

@@ -103,12 +103,12 @@ def test_dpf1_vs_oracle(api, ctx, oracle, dims):
     mvn, nclus = oracle.cluster_candidates(dp, kmax=k)
     d0 = oracle.get_dpf0(mvn, nclus, dimx, dimy, 0.6)
     ruv = api.get_ruv_neighbor(xy, dimx, dimy, mps, radius)
-    rd, rx, ry = oracle.get_dpf1(d0, ruv, mvn, nclus, xy, 16.0, 15.0)
+    rd, rx, ry, ref_sweeps = oracle.get_dpf1(d0, ruv, mvn, nclus, xy, 16.0, 15.0, sweeps=True)
     d, x, y, sweeps = ctx.get_dpf1(d0, ruv, mvn, nclus, xy, 16.0, 15.0)
     assert (d0 < 0).sum() > (rd < 0).sum()
     assert np.array_equal(d, rd)
     assert_bits_equal(x, rx, "dx"); assert_bits_equal(y, ry, "dy")
-    assert sweeps >= 1
+    assert sweeps >= 1 and sweeps == ref_sweeps
 
 
 def test_dpf1_nothing_to_fill(api, ctx, oracle):
@@ -121,7 +121,7 @@ def test_dpf1_nothing_to_fill(api, ctx, oracle):
     d0 = oracle.get_dpf0(mvn, nclus, dimx, dimy, 0.6)
     assert (d0 >= 0).all()
     ruv = api.get_ruv_neighbor(xy, dimx, dimy, mps, 3.0)
-    rd, rx, ry = oracle.get_dpf1(d0, ruv, mvn, nclus, xy, 16.0, 15.0)
+    rd, rx, ry, ref_sweeps = oracle.get_dpf1(d0, ruv, mvn, nclus, xy, 16.0, 15.0, sweeps=True)
     d, x, y, sweeps = ctx.get_dpf1(d0, ruv, mvn, nclus, xy, 16.0, 15.0)
     assert np.array_equal(d, rd); assert_bits_equal(x, rx); assert_bits_equal(y, ry)
-    assert sweeps == 1
+    assert sweeps == 1 and sweeps == ref_sweeps

@@ -89,6 +89,21 @@ def test_vs_oracle(api, oracle, dims):
         assert_bits_equal(y2, oy)
 
 
+def test_cap_below_a_long_run(api, oracle):
+    """max_sweeps=2 on an input whose uncapped run is far longer (39 sweeps): the cap itself decides.  (One of
+    test_vs_oracle's inputs stops by itself before sweep 2, so its capped leg does not reach the cap.)"""
+    import postprocess_edge_common as pe
+    a = pe.qm_domino(200, 5, chain=40).arrays()
+    full = oracle.qm(*a)
+    od, ox, oy, ost = oracle.qm(*a, max_sweeps=2)
+    assert full[3][0] > 2 and ost[0] == 2 and ost[3] == pe.QM_STOP_CAP and (od != full[0]).any()
+    with api.Context(0) as ctx:
+        d2, x2, y2, s2 = ctx.get_dpf_pseudosmoothing(*a, max_sweeps=2)
+    assert np.array_equal(d2, od) and s2 == ost[0]
+    assert_bits_equal(x2, ox)
+    assert_bits_equal(y2, oy)
+
+
 def test_nan_and_unassigned_points(api, oracle):
     """dpf == -1 / NaN displacements are skipped as neighbours and never investigated (:2035, :2116)."""
     xy, mvn, nclus, dpf, dx, dy = qm_inputs(40, 36, 9, 60.0)
