@@ -76,7 +76,7 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *       chip sizes it is built for; the points it does not take (null pixels in the window or chip, corridors wider than
  *       its 32 x 32 cell tile, ...) are flagged and done by kernel 1 right behind;
  *   0 = general f32 kernel (any ocw, any window size) otherwise;
- *   6 = the exhaustive search (mimc3_match_ncc_full, mimc3_match_ncc_pyramid): the matrix-core kernel's surfaces, every point
+ *   6 = the exhaustive search (mimc3_match_ncc_full, mimc3_match_ncc_full_multi, mimc3_match_ncc_pyramid): the matrix-core kernel's surfaces, every point
  *       on the matrix cores (it does not depend on the mode).
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
@@ -154,6 +154,41 @@ int mimc3_match_ncc_full(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const 
  * The caller guarantees the bounds the host entry checks (a point that breaks them gets an all-NaN record and no read). */
 int mimc3_match_ncc_full_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                              const int32_t *d_shift, int32_t ocw, int32_t R, int32_t swap, float *d_out, void *stream);
+
+/* ---- Exhaustive search with candidates: the K best correlation peaks of every point, in the layout the post-matcher chain reads
+ *      (mimc3_cluster_candidates -> dpf0 -> dpf1 -> QM, mimc3_postprocess: dp [ndp][N][3] with ndp = npeaks, or several calls'
+ *      candidates stacked, ndp <= 64).
+ *
+ *   Inputs, surface, validity and the [N][8] record `out`: exactly mimc3_match_ncc_full's -- the same code computes the record, bit
+ *     for bit, the SNR included.  1 <= npeaks <= 8.
+ *   Local maximum: a cell s = (su, sv) with
+ *     |su| < R and |sv| < R (a border cell is never a candidate, but it takes part as a neighbour);
+ *     NCC(s) finite;
+ *     for each of its 8 neighbours t: NCC(t) is not finite, or NCC(s) > NCC(t), or NCC(s) == NCC(t) and k(s) < k(t), with
+ *     k = (su + R)(2R + 1) + (sv + R) as in the arg-max rule (a flat top yields one local maximum: its lowest k).
+ *   Rank: the local maxima by NCC descending, ties by ascending k; candidate j is the j-th of them.
+ *   Output cand, f32 [npeaks][N][3], pass-major: cand[j][i] = (du, dv, ncc) of point i's candidate j:
+ *     ncc     the cell's f32 NCC;
+ *     du, dv  the reference's 3x3 fit around that cell, the float/double expression sequence of the record's fit, plus
+ *             (float)(su + shift_u), (float)(sv + shift_v); a non-finite neighbour makes the fit NaN, as in the record.
+ *   Slots without a peak:
+ *     fewer than npeaks local maxima: the remaining slots are (NaN, NaN, -2);
+ *     status -3 (validity): every slot is (NaN, NaN, -3), the DLC matcher's invalid match;
+ *     a point that gets the all-NaN record (the _dev entry's contract): every slot all NaN.
+ *     None of these passes clustering's ncc > 0.1 test.
+ *   Consequences:
+ *     where the record has a fit (its peak is interior), candidate 0 equals the record's columns 0-2 bit for bit;
+ *     where the record has status -4 (peak on the border), the candidates are the interior local maxima that exist;
+ *     status -2 (no finite cell): no local maximum, every slot (NaN, NaN, -2);
+ *     at R = 1 there is one interior cell, so at most one candidate.
+ *   Refusals: npeaks outside 1..8: MIMC3_EINVAL; every refusal of mimc3_match_ncc_full, unchanged.  mimc3_ctx_last_path reports 6. */
+int mimc3_match_ncc_full_multi(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                               const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap,
+                               float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host*/);
+/* Device-resident variant: as mimc3_match_ncc_full_dev, plus d_cand [npeaks][N][3]; enqueues on `stream`, no sync. */
+int mimc3_match_ncc_full_multi_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                   const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                                   float *d_cand, void *stream);
 
 /* ---- Coarse-to-fine exhaustive search over an image pyramid (no reference counterpart: the reach of mimc3_match_ncc_full, +-R
  *      around uv0 + offset + shift, made about R (2^L - 1) px by searching a reduced pair first -- the offset trackers' standard).

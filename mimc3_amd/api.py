@@ -50,6 +50,9 @@ _lib.mimc3_match_ncc_dlc_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int
                                          C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
 _lib.mimc3_match_ncc_full.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, _f32p]
 _lib.mimc3_match_ncc_full_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
+_lib.mimc3_match_ncc_full_multi.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p]
+_lib.mimc3_match_ncc_full_multi_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                _vp, _vp, _vp]
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
 _lib.mimc3_match_ncc_pyramid_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
@@ -458,6 +461,30 @@ class Context:
         """Device-pointer variant (enqueue only): d_xyuvav [n][6] f64, d_shift [n][2] int32 or 0, d_out [n][8] f32."""
         _check(_lib.mimc3_match_ncc_full_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                              1 if swap else 0, d_out, stream), "match_ncc_full_dev")
+
+    def match_ncc_full_multi(self, xyuvav, offset, ocw, radius, npeaks, shift=None, swap=False):
+        """The exhaustive search with candidates (mimc3_match_ncc_full_multi) -> (float32[N][8] record, exactly match_ncc_full's,
+        float32[npeaks][N][3] candidates): per point the best npeaks (1..8) local maxima of its correlation surface as (du, dv, ncc),
+        by NCC descending, pass-major -- the dp that cluster_candidates / mimc2_postprocess read.  Slots without a peak are
+        (NaN, NaN, -2), or (NaN, NaN, -3) at an invalid point."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((max(int(npeaks), 0), n, 3), np.float32)
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_full_multi: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_full_multi(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
+                                               None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, out,
+                                               cand.reshape(-1) if cand.size else np.empty(1, np.float32)), "match_ncc_full_multi")
+        return out, cand
+
+    def match_ncc_full_multi_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand, d_shift=0, stream=0, swap=False):
+        """Device-pointer variant (enqueue only): as match_ncc_full_dev, plus d_cand [npeaks][n][3] f32."""
+        _check(_lib.mimc3_match_ncc_full_multi_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                   npeaks, 1 if swap else 0, d_out, d_cand, stream), "match_ncc_full_multi_dev")
 
     def match_ncc_pyramid(self, xyuvav, offset, ocw, radius, levels, shift=None, swap=False):
         """Coarse-to-fine exhaustive search over an image pyramid (mimc3_match_ncc_pyramid) on the resident 8-bit pair ->

@@ -126,6 +126,7 @@ struct mimc3_ctx {
     struct PyrLevel { DevBuf pl0, pl1, sat0, sat1; int32_t H = 0, W = 0, Wp = 0; } pyr[4];
     int pyr_levels = 0;
     DevBuf pyr_pos, pyr_peak, pyr_sh;   // per point: position on the level (f64 [N][2]), arg-max cell, search shift (the host entry's)
+    DevBuf full_cand;                   // mimc3_match_ncc_full_multi's host entry: the candidates, f32 [npeaks][N][3]
 };
 
 static constexpr size_t kPinChunk = 4u << 20;
@@ -741,20 +742,24 @@ extern "C" int mimc3_match_ncc_dlc(mimc3_ctx *c, const double *xyuvav, int32_t N
 // ---------------------------------------------------------------------------------------------
 static bool full_ocw_ok(int32_t ocw) { return ocw == 7 || ocw == 15 || ocw == 16 || ocw == 30 || ocw == 32 || ocw == 40; }
 
-extern "C" int mimc3_match_ncc_full_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                        const int32_t *d_shift, int32_t ocw, int32_t R, int32_t swap, float *d_out, void *stream)
+// the device entry of the exhaustive search, without (d_cand null) or with the candidates of its best npeaks local maxima
+static int full_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
+                    int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream, const char *entry)
 {
-    if (!c || !d_xyuvav || !d_out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full_dev: bad argument");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full_dev: ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full_dev: R must be in 1..15");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_full_dev: images not set");
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_full_dev: not on a chip-atlas context");
-    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, "mimc3_match_ncc_full_dev: the pair is not 8-bit (u8 planes only)");
+    const std::string en(entry);
+    if (!c || !d_xyuvav || !d_out || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
+    if (d_cand && (npeaks < 1 || npeaks > mimc3::kFullMaxPeaks)) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 1..8");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
     mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
     u.full_shift = d_shift; u.full_R = R;
+    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
     u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
     u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
     DevBuf &ml = c->mxl[0];
@@ -769,27 +774,45 @@ extern "C" int mimc3_match_ncc_full_dev(mimc3_ctx *c, const double *d_xyuvav, in
     return 0;
 }
 
-extern "C" int mimc3_match_ncc_full(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                    int32_t ocw, int32_t R, int32_t swap, float *out)
+extern "C" int mimc3_match_ncc_full_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                        const int32_t *d_shift, int32_t ocw, int32_t R, int32_t swap, float *d_out, void *stream)
 {
-    if (!c || !xyuvav || !offset || !out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full: bad argument");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full: ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full: R must be in 1..15");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, "mimc3_match_ncc_full: images not set");
-    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, "mimc3_match_ncc_full: the pair is not 8-bit (u8 planes only)");
+    return full_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, 0, swap, d_out, nullptr, stream, "mimc3_match_ncc_full_dev");
+}
+
+extern "C" int mimc3_match_ncc_full_multi_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                              const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                                              float *d_cand, void *stream)
+{
+    if (!d_cand) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full_multi_dev: bad argument");
+    return full_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream, "mimc3_match_ncc_full_multi_dev");
+}
+
+// the host entry of the exhaustive search: its checks, the uploads, the device entry and the copies back (cand null: the record alone)
+static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
+                     int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry)
+{
+    const std::string en(entry);
+    if (!c || !xyuvav || !offset || !out || N <= 0 || (multi && !cand)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
+    if (multi && (npeaks < 1 || npeaks > mimc3::kFullMaxPeaks)) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 1..8");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
     // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
-    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, "mimc3_match_ncc_full"));
+    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
     const int64_t pad = mimc3::kU8Pad;
     for (int32_t g = 0; g < N; ++g) {
         const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
         const int64_t cu = (int64_t)u0 + offset[0] + (shift ? shift[2 * (size_t)g] : 0), cv = (int64_t)v0 + offset[1] + (shift ? shift[2 * (size_t)g + 1] : 0);
         const int64_t h = R + ocw;
         if (cu - h < -pad || cu + h >= c->W + pad || cv - h < -pad || cv + h >= c->H + pad)
-            return mimc3::fail(MIMC3_EBOUNDS, "mimc3_match_ncc_full: grid point " + std::to_string(g) + " search box leaves the zero border");
+            return mimc3::fail(MIMC3_EBOUNDS, en + ": grid point " + std::to_string(g) + " search box leaves the zero border");
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
     HIP_TRY(c->out.reserve(sizeof(float) * 8 * (size_t)N));
+    if (multi) HIP_TRY(c->full_cand.reserve(sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
     RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
     const int32_t *d_shift = nullptr;
     if (shift) {
@@ -797,10 +820,25 @@ extern "C" int mimc3_match_ncc_full(mimc3_ctx *c, const double *xyuvav, int32_t 
         RC_TRY(h2d_copy(c, c->puv.p, shift, sizeof(int32_t) * 2 * (size_t)N));
         d_shift = static_cast<const int32_t *>(c->puv.p);
     }
-    const int rc = mimc3_match_ncc_full_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, swap,
-                                            static_cast<float *>(c->out.p), c->stream);
+    const int rc = full_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
+                            static_cast<float *>(c->out.p), multi ? static_cast<float *>(c->full_cand.p) : nullptr, c->stream,
+                            multi ? "mimc3_match_ncc_full_multi_dev" : "mimc3_match_ncc_full_dev");
     if (rc) return rc;
-    return d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N);
+    RC_TRY(d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N));
+    if (multi) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_full(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                    int32_t ocw, int32_t R, int32_t swap, float *out)
+{
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, 0, swap, out, nullptr, false, "mimc3_match_ncc_full");
+}
+
+extern "C" int mimc3_match_ncc_full_multi(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                          int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand)
+{
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, true, "mimc3_match_ncc_full_multi");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // MIMC3_hip_offsets -- exhaustive-search NCC offsets with peak quality over libmimc3_hip.so (MI355X): the AMPCOR-style table that
 // MIMC_single_match.c:1-27 describes.
 //
-//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1]
+//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1]
 //
 // Inputs as for MIMC3_hip (the file names start with YYYYMMDDhhmmss; dt from the two timestamps); both images 8-bit.  Steps: the
 // control-point offset (mimc3_vmap_cp, as the reference program measures it), the a-priori shift of every grid point
@@ -13,6 +13,9 @@
 //   offsets_<t0>_<t1>.txt  the points with a non-negative status, one per line, AMPCOR's column order: u du v dv snr h_uu h_vv h_uv;
 //                          du, dv there are the whole displacement (the control-point offset added); a first comment line names
 //                          the columns and the offset
+//   candidates_<t0>_<t1>.GMA  peaks = K > 1 (with levels = 1 only): f32 [K N][3], pass-major -- row j N + i = candidate j of grid point i,
+//                          (du, dv, ncc) of its j-th best correlation peak (mimc3_match_ncc_full_multi): the dp of the post-matcher chain.
+//                          peaks = 1 writes exactly the two files above
 // Environment: MIMC3_HIP_DEVICE (default 0), MIMC3_CP_SEED (as for MIMC3_hip).
 #include <cstdint>
 #include <cstdio>
@@ -27,11 +30,16 @@
 int main(int argc, char *argv[])
 {
     printf("MIMC3_hip_offsets -- MI355X build (%s)\n", mimc3_version());
-    if (argc < 5 || argc > 8) {
-        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1]\n", argv[0]);
+    if (argc < 5 || argc > 9) {
+        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1]\n", argv[0]);
         return 2;
     }
     const int32_t ocw = argc > 5 ? atoi(argv[5]) : 15, R = argc > 6 ? atoi(argv[6]) : 15, levels = argc > 7 ? atoi(argv[7]) : 1;
+    const int32_t peaks = argc > 8 ? atoi(argv[8]) : 1;
+    if (peaks != 1 && levels != 1) {
+        fprintf(stderr, "peaks > 1 needs levels = 1: candidates on a pyramid's level 0 are not supported\n");
+        return 2;
+    }
     char t0[15], t1[15];
     if (!timestamp_of(argv[1], t0) || !timestamp_of(argv[2], t1)) {
         fprintf(stderr, "image paths must contain a '/' and the file names must start with YYYYMMDDhhmmss\n");
@@ -69,9 +77,12 @@ int main(int argc, char *argv[])
     if (levels != 1) printf("coarse-to-fine over %d pyramid levels\n", levels);
     std::vector<int32_t> shift(2 * (size_t)N);
     std::vector<float> rec(8 * (size_t)N);
+    std::vector<float> cand(peaks != 1 ? 3 * (size_t)(peaks > 0 ? peaks : 0) * (size_t)N : 0);
+    if (peaks != 1) printf("the %d best correlation peaks of every grid point as candidates\n", peaks);
     if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
-        (levels == 1 ? mimc3_match_ncc_full(ctx, xy.data(), N, offset, shift.data(), ocw, R, 0, rec.data())
-                     : mimc3_match_ncc_pyramid(ctx, xy.data(), N, offset, shift.data(), ocw, R, levels, 0, rec.data(), nullptr))) {
+        (peaks != 1 ? mimc3_match_ncc_full_multi(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks, 0, rec.data(), cand.data())
+         : levels == 1 ? mimc3_match_ncc_full(ctx, xy.data(), N, offset, shift.data(), ocw, R, 0, rec.data())
+                       : mimc3_match_ncc_pyramid(ctx, xy.data(), N, offset, shift.data(), ocw, R, levels, 0, rec.data(), nullptr))) {
         fprintf(stderr, "%s\n", mimc3_last_error());
         return leave(3);
     }
@@ -84,6 +95,7 @@ int main(int argc, char *argv[])
         nok += rec[8 * (size_t)g + 2] >= -1.0f;
     }
     bool ok = save_gma(base + ".GMA", out.data(), N, 10);
+    if (peaks != 1) ok = save_gma(std::string(argv[4]) + "/candidates_" + t0 + "_" + t1 + ".GMA", cand.data(), peaks * N, 3) && ok;
     FILE *f = fopen((base + ".txt").c_str(), "w");
     if (f) {
         fprintf(f, "# u du v dv snr h_uu h_vv h_uv   (du, dv include the control-point offset %d %d)\n", offset[0], offset[1]);

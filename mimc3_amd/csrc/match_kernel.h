@@ -64,7 +64,13 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
         int32_t full_R;             // exhaustive search: 1..15
     };
     float *out;
-    int32_t *ovf_list, *ovf_count;  // points whose NCC cache overflowed: handed to the general kernel (list mode)
+    // (exhaustive search with candidates, mimc3_match_ncc_full_multi: the best full_npeaks local maxima of every point's surface, pass-major;
+    //  the pointer and the count share the slots of the overflow list and the climb's look-ahead, which full mode never reads)
+    union {
+        int32_t *ovf_list;          // points whose NCC cache overflowed: handed to the general kernel (list mode)
+        float *full_cand;           // exhaustive search, optional: f32 [full_npeaks][N][3] (du, dv, ncc); null = the record alone
+    };
+    int32_t *ovf_count;
     const int32_t *point_list, *point_count;   // list mode: workgroup b handles point_list[b], b < *point_count (nullptr = all N points)
     // PxU8o: points whose chip or window does not fit a local 8-bit range.  Matrix-core DLC kernel behind u8_classify: the rest list --
     // a point the kernel meets but does not take (a climb that leaves the tile or outlasts the recorded scans: a few dozen per launch)
@@ -93,7 +99,10 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     const void *sat0, *sat1;
     const void *satz0, *satz1;      // u16 planes: null counts (u32), same geometry
     int32_t sat_ws;
-    int32_t lookahead;              // speculative climb: 3x3 blocks requested ahead along a straight move
+    union {
+        int32_t lookahead;          // speculative climb: 3x3 blocks requested ahead along a straight move
+        int32_t full_npeaks;        // exhaustive search with candidates: 1..8
+    };
     unsigned long long *stats;     // diagnostics only (env MIMC3_U8_STATS): per-phase s_memtime sums
     int32_t debug_stop;             // diagnostics only (env MIMC3_U8_DEBUG_STOP): leave the kernel after phase k; 0 = off
     int32_t dry_run;                // launcher only: compute the LDS carve and return hipSuccess / hipErrorInvalidValue (does not fit
@@ -160,8 +169,12 @@ hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, hipStream_t 
 // exhaustive-search NCC offsets on the same surfaces (mimc3_match_ncc_full): every point on the matrix cores -- the clean form, then
 // the window-null and general forms over the points it flags (a.mx_flags: N bytes, zero before the call); a.full_R in 1..15,
 // a.ocw one of 7, 15, 16, 30, 32, 40; a.out [N][8]; a.full_peak (optional, int32 [N]) gets every point's arg-max cell k = (su + R)(2R + 1)
-// + (sv + R), also at status -4, or -1 without one (status -3 / -2, the NaN record of a point outside the image or the zero border)
+// + (sv + R), also at status -4, or -1 without one (status -3 / -2, the NaN record of a point outside the image or the zero border);
+// a.full_cand (optional, f32 [a.full_npeaks][N][3], 1 <= full_npeaks <= kFullMaxPeaks; not together with full_peak) gets every point's
+// best local maxima as (du, dv, ncc) candidates (mimc3_match_ncc_full_multi) -- null selects the kernels without that tail
+constexpr int kFullMaxPeaks = 8;
 hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream);
+static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all
 // zero; Hd = Hs >> 1, Wd = Ws >> 1 (the destination plane pre-zeroed, border pad in both)

@@ -117,6 +117,7 @@ struct Cfg {
     static constexpr int MINW = MINW0 < MINW1 ? MINW0 : MINW1;
     static constexpr bool FULL = false;                 // the DLC matcher (true: FullCfg, the exhaustive search)
     static constexpr bool PEAK = false;                 // full mode: also write the arg-max cell to full_peak (FullPeakCfg)
+    static constexpr bool MULTI = false;                // full mode: also write the best local maxima as candidates to full_cand (FullMultiCfg)
 };
 // Exhaustive search (mimc3_match_ncc_full): the same surface builder on the cell tile whose origin is c - R (the search centre
 // c = uv0 + offset + shift, 1 <= R <= 15: all (2R + 1)^2 cells in the tile), no never-written row / column (T4), and instead of the
@@ -130,6 +131,13 @@ struct FullCfg : Cfg<OCW_, GEN_, CN_> {
 template <int OCW_, bool GEN_, bool CN_>
 struct FullPeakCfg : FullCfg<OCW_, GEN_, CN_> {
     static constexpr bool PEAK = true;
+};
+
+// ... and with candidates (mimc3_match_ncc_full_multi): the same record, plus the best full_npeaks local maxima of the surface as
+// (du, dv, ncc) candidates in full_cand, pass-major -- what mimc3_cluster_candidates reads as dp
+template <int OCW_, bool GEN_, bool CN_>
+struct FullMultiCfg : FullCfg<OCW_, GEN_, CN_> {
+    static constexpr bool MULTI = true;
 };
 
 // The constant band operands, one table per chip size (constant-initialised device data).  v_mfma_i32_16x16x64_i8: lane (n = lane & 15,
@@ -251,6 +259,19 @@ __device__ __forceinline__ void full_store(float *o, float status)
     for (int i = 3; i < 8; i++) o[i] = nanv;
 }
 
+// (FullMultiCfg) every candidate slot of a point that has no surface: (NaN, NaN, status)
+template <class C>
+__device__ __forceinline__ void full_cand_fill(const MatchU8Args &p, int gidx, float status)
+{
+    if constexpr (C::MULTI) {
+        const float nanv = __builtin_nanf("");
+        for (int j = 0; j < p.full_npeaks; j++) {
+            float *q = p.full_cand + 3 * ((size_t)j * (size_t)p.N + (size_t)gidx);
+            q[0] = nanv; q[1] = nanv; q[2] = status;
+        }
+    }
+}
+
 // The tail of the exhaustive search on wave 0, over the f32 surface val[y][x] (tile cell (x, y) = offset (x - R, y - R)):
 //   peak   first-wins arg-max over the finite cells in k = (su + R)(2R + 1) + (sv + R) (u outer): lane l scans k = l, l + 64, ...
 //          in ascending order (strict >: its first maximum), then the lanes (value, -k) lexicographically (argmax_row16, then
@@ -326,6 +347,94 @@ __device__ __forceinline__ void full_tail(const MatchU8Args &p, const float *val
     full_peak_store<C>(p, gidx, bk);
 }
 
+// The candidates of the exhaustive search (FullMultiCfg), on wave 0 behind full_tail, which has written the record -- also where it
+// has no fit (-2: there is no local maximum either; -4: the interior ones are the candidates):
+//   scan     lane l tests its cells k = l, l + 64, ... for the local-maximum rule: interior (|su|, |sv| < R), finite, and against each of
+//            the 8 neighbours t: t not finite, NCC(s) > NCC(t), or equal with k(s) < k(t) (a plateau yields its lowest k alone).  One
+//            bit per cell of the lane: at most 16;
+//   select   full_npeaks rounds of the wave arg-max (value descending, k ascending): a lane offers its best local maximum strictly
+//            behind the previous round's pick in that order -- no list, no atomics; round j's pick stays with lane j;
+//   fit      lanes 0 .. full_npeaks - 1 fit one candidate each: the reference's 3x3 quadratic, the expressions of full_tail.
+// Slots beyond the last local maximum: (NaN, NaN, -2).
+template <class C>
+__device__ __forceinline__ void full_tail_multi(const MatchU8Args &p, const float *val, int gidx, int shu, int shv, int lane)
+{
+    constexpr int VP = C::VP;
+    constexpr int kNone = 0x7fffffff;
+    const int R = p.full_R, S = 2 * R + 1, NC = S * S, npk = p.full_npeaks;
+    const float invS = 1.0f / (float)S;
+    // k / S for k < 1024, S <= 31: (k + 1/2) / S lies at least 1 / 62 from an integer, the f32 product within 2^-16 of it
+    auto col_of = [&](int k) __attribute__((always_inline)) -> int { return (int)(((float)k + 0.5f) * invS); };
+    uint32_t lm = 0u;
+    {
+        int j = 0;
+        for (int k = lane; k < NC; k += 64, j++) {
+            const int x = col_of(k), y = k - S * x;
+            const bool interior = x >= 1 && x <= S - 2 && y >= 1 && y <= S - 2;
+            const float *c = val + (interior ? y : 1) * VP + (interior ? x : 1);      // (a border cell reads a harmless block)
+            const float v = c[0];
+            bool ok = interior && __builtin_isfinite(v);
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++)
+#pragma unroll
+                for (int dy = -1; dy <= 1; dy++) {
+                    if (dx == 0 && dy == 0) continue;
+                    const float t = c[dy * VP + dx];
+                    const bool later = dx > 0 || (dx == 0 && dy > 0);                    // k(t) > k(s)
+                    ok = ok && (!__builtin_isfinite(t) || v > t || (later && v == t));
+                }
+            lm |= (ok ? 1u : 0u) << j;
+        }
+    }
+    float pv = __builtin_inff(), myv = 0.0f;
+    int pk = -1, myk = kNone;
+    for (int r = 0; r < npk; r++) {
+        float bv = -__builtin_inff();
+        int bk = kNone;
+        for (uint32_t m = lm; m != 0u; m &= m - 1u) {        // ascending k: strict > keeps the lane's first
+            const int k = lane + 64 * (__builtin_ffs((int)m) - 1);
+            const int x = col_of(k), y = k - S * x;
+            const float v = val[y * VP + x];
+            const bool behind = v < pv || (v == pv && k > pk);
+            if (behind && v > bv) { bv = v; bk = k; }
+        }
+        argmax_row16(bv, bk);
+#pragma unroll
+        for (int o = 16; o <= 32; o <<= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bk, o, 64);
+            if (ov > bv || (ov == bv && oi < bk)) { bv = ov; bk = oi; }
+        }
+        bv = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bv)));
+        bk = __builtin_amdgcn_readfirstlane(bk);
+        if (bk == kNone) break;
+        if (lane == r) { myv = bv; myk = bk; }
+        pv = bv; pk = bk;
+    }
+    if (lane >= npk) return;
+    float *q = p.full_cand + 3 * ((size_t)lane * (size_t)p.N + (size_t)gidx);
+    if (myk == kNone) { const float nanv = __builtin_nanf(""); q[0] = nanv; q[1] = nanv; q[2] = -2.0f; return; }
+    const int px = col_of(myk), py = myk - S * px, su = px - R, sv = py - R;
+    float n9[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) n9[3 * r + c] = val[(py - 1 + r) * VP + (px - 1 + c)];
+    const float e0 = 6 * n9[0] - 12 * n9[1] + 6 * n9[2] + 6 * n9[3] - 12 * n9[4] + 6 * n9[5] + 6 * n9[6] - 12 * n9[7] + 6 * n9[8];
+    const float e1 = 9 * n9[0] - 9 * n9[2] - 9 * n9[6] + 9 * n9[8];
+    const float e2 = 6 * n9[0] + 6 * n9[1] + 6 * n9[2] - 12 * n9[3] - 12 * n9[4] - 12 * n9[5] + 6 * n9[6] + 6 * n9[7] + 6 * n9[8];
+    const float e3 = -6 * n9[0] + 6 * n9[2] - 6 * n9[3] + 6 * n9[5] - 6 * n9[6] + 6 * n9[8];
+    const float e4 = -6 * n9[0] - 6 * n9[1] - 6 * n9[2] + 6 * n9[6] + 6 * n9[7] + 6 * n9[8];
+    double c0 = e0, c1 = e1, c2 = e2, c3 = e3, c4 = e4;
+    c0 /= 36; c1 /= 36; c2 /= 36; c3 /= 36; c4 /= 36;
+    const float nu = (float)(-2 * c2 * c3 + c1 * c4), nv = (float)(-2 * c0 * c4 + c1 * c3);
+    const double det = 4 * c0 * c2 - c1 * c1;
+    float du = (float)((double)nu / det), dv = (float)((double)nv / det);
+    du += (float)(su + shu);
+    dv += (float)(sv + shv);
+    q[0] = du; q[1] = dv; q[2] = myv;
+}
+
 template <class C>
 __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p)
 {
@@ -369,7 +478,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const int u0 = (int)row[0], v0 = (int)row[1];
     // (full mode, a point that breaks the bounds mimc3_match_ncc_full refuses -- only the _dev entry can pass one: no read, all NaN)
     if (C::FULL && (u0 - OCW < 0 || u0 + OCW >= p.W || v0 - OCW < 0 || v0 + OCW >= p.H)) {
-        if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); }
+        if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); full_cand_fill<C>(p, gidx, __builtin_nanf("")); }
         return;
     }
     const int64_t pbeg = C::FULL ? 0 : p.piv_off[gidx];
@@ -419,7 +528,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const int csx = Dx2 - 2 * OCW + 1, csy = Dy2 - 2 * OCW + 1;          // compact cells; a climb touches [1, cs - 2]
     const int wu0 = u0 + p.off_u - dx2 + PAD + (C::FULL ? lu : 0), wv0 = v0 + p.off_v - dy2 + PAD + (C::FULL ? lv : 0);   // plane position of window pixel (0, 0)
     if (C::FULL && (wu0 < 0 || wv0 < 0 || wu0 + Dx2 > p.W + 2 * PAD || wv0 + Dy2 > p.H + 2 * PAD)) {
-        if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); }
+        if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); full_cand_fill<C>(p, gidx, __builtin_nanf("")); }
         return;
     }
     // ---- what this kernel takes -----------------------------------------------------------------------------------
@@ -480,7 +589,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         const float rc = (float)chip_nulls / (float)NPX;
         const float rw = (float)win_nulls / (float)(Dx2 * Dy2);
         if (rc > max_ratio || rw > max_ratio) {
-            if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, -3.0f); full_peak_store<C>(p, gidx, -1); }
+            if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, -3.0f); full_peak_store<C>(p, gidx, -1); full_cand_fill<C>(p, gidx, -3.0f); }
             return;
         }
     } else {
@@ -889,6 +998,12 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     if (wave != 0) return;                                  // the sequential part needs one wave (lane k = pivot k)
     if constexpr (C::FULL) {
         full_tail<C>(p, val, gidx, lu, lv, lane);
+        if constexpr (C::MULTI) {                           // (the record's lanes have left full_tail at different places: all 64 are back here)
+            MIMC3_MX_STAMP(4)
+            full_tail_multi<C>(p, val, gidx, lu, lv, lane);
+            MIMC3_MX_STAMP(5)
+            MIMC3_MX_STATS_OUT
+        }
         return;
     }
 
@@ -1182,7 +1297,7 @@ hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
 
 // Exhaustive search: every point on the matrix cores.  The clean form runs over all points and flags the null-ridden ones for the
 // window-null form (nulls in the search box only) or the general form (chip nulls too), which run right behind in flag mode.
-// (FC: FullCfg, or FullPeakCfg when the caller wants the arg-max cells)
+// (FC: FullCfg, FullPeakCfg when the caller wants the arg-max cells, or FullMultiCfg when it wants the candidates)
 template <template <int, bool, bool> class FC, bool GEN, bool CN>
 static hipError_t launch_full_form(const MatchU8Args &a, hipStream_t stream)
 {
@@ -1213,6 +1328,10 @@ hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream)
     if (!a.mx_flags || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15) return hipErrorInvalidValue;
     a.mx_wn_on = 1; a.mx_gen_on = 1; a.mx_classified = 0;
     a.point_list = nullptr; a.point_count = nullptr; a.point_flags = nullptr;
+    if (a.full_cand) {
+        if (a.full_peak || a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks) return hipErrorInvalidValue;
+        return launch_full_forms<mx::FullMultiCfg>(a, stream);
+    }
     return a.full_peak ? launch_full_forms<mx::FullPeakCfg>(a, stream) : launch_full_forms<mx::FullCfg>(a, stream);
 }
 
