@@ -77,7 +77,8 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *       its 32 x 32 cell tile, ...) are flagged and done by kernel 1 right behind;
  *   0 = general f32 kernel (any ocw, any window size) otherwise;
  *   6 = the exhaustive search (mimc3_match_ncc_full, mimc3_match_ncc_full_multi, mimc3_match_ncc_pyramid): the matrix-core kernel's surfaces, every point
- *       on the matrix cores (it does not depend on the mode).
+ *       on the matrix cores (it does not depend on the mode);
+ *   7 = the exhaustive search of mimc3_match_ncc_full_planes on a scaled-integer pair: the u16 planes' register-tiled search kernel.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -147,7 +148,7 @@ int mimc3_pivot_extent(const int32_t *piv_uv, const int64_t *piv_off, int32_t N,
  *     Columns 3-7 are NaN when the status is negative.
  *   Refusals: ocw outside {7, 15, 16, 30, 32, 40} or R outside 1..15: MIMC3_EINVAL; a chip that leaves the image, or a search box
  *   beyond the planes' 256-px zero border: MIMC3_EBOUNDS; a pair that did not classify as 8-bit (u8 planes): MIMC3_EUNSUPPORTED.
- *   mimc3_ctx_last_path reports 6. */
+ *   mimc3_ctx_last_path reports 6.  (mimc3_match_ncc_full_planes is this search on scaled-integer pairs too.) */
 int mimc3_match_ncc_full(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                          const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t swap, float *out /*[N][8] host*/);
 /* Device-resident variant: d_xyuvav [N][6], d_shift [N][2] or NULL, d_out [N][8] device pointers; enqueues on `stream`, no sync.
@@ -181,7 +182,8 @@ int mimc3_match_ncc_full_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, 
  *     where the record has status -4 (peak on the border), the candidates are the interior local maxima that exist;
  *     status -2 (no finite cell): no local maximum, every slot (NaN, NaN, -2);
  *     at R = 1 there is one interior cell, so at most one candidate.
- *   Refusals: npeaks outside 1..8: MIMC3_EINVAL; every refusal of mimc3_match_ncc_full, unchanged.  mimc3_ctx_last_path reports 6. */
+ *   Refusals: npeaks outside 1..8: MIMC3_EINVAL; every refusal of mimc3_match_ncc_full, unchanged.  mimc3_ctx_last_path reports 6.
+ *   (mimc3_match_ncc_full_planes returns the same candidates on scaled-integer pairs too.) */
 int mimc3_match_ncc_full_multi(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                                const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap,
                                float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host*/);
@@ -189,6 +191,33 @@ int mimc3_match_ncc_full_multi(mimc3_ctx *ctx, const double *xyuvav, int32_t N, 
 int mimc3_match_ncc_full_multi_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                    const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
                                    float *d_cand, void *stream);
+
+/* ---- Exhaustive search on the planes the context matches on: 8-bit pairs and scaled-integer pairs (12-bit DN; an 8-bit pair after
+ *      mimc3_ctx_filter_images: gradients, Laplacian) -- the variants the post-matcher chain chooses among.
+ *
+ *   A superset of the two entries above.  npeaks = 0: the record alone (cand NULL), word for word mimc3_match_ncc_full; npeaks in
+ *   1..8: the record and cand [npeaks][N][3], word for word mimc3_match_ncc_full_multi -- validity, first-wins arg-max, border rule,
+ *   fit, SNR, Hessian, local-maximum rule and rank, the encodings of empty slots.  It runs on the pair the context currently matches on:
+ *     8-bit pair       the matrix-core kernels of the entries above; results bit for bit theirs.  mimc3_ctx_last_path reports 6.
+ *     scaled-integer   (every pixel q / 2^s with q < 4096, s = 0 or 3 per image: the pairs the DLC matcher runs on u16 planes) the
+ *                      search runs on the u16 planes q.  A pixel is null exactly when q == 0; box pixels outside the image are the
+ *                      256-px zero border.  mimc3_ctx_last_path reports 7.
+ *                      The integers need no new arithmetic: every f32 product of two pixels q_a / 2^sa * q_b / 2^sb is exact (< 2^24
+ *                      significant bits), every f64 sum is an exact integer times a power of two, n sxy - sx sy and both variance
+ *                      terms are exact (< 2^50), and the scale 2^-(sa + sb) commutes with the rounding of the variance product, with
+ *                      the square root (an even exponent) and with the division -- the reference's cell formula on the float pixels
+ *                      equals the same formula on the integers q bit for bit.  The record and the candidates come from the same
+ *                      code as on 8-bit pairs.
+ *     anything else    (16-bit DN, non-integral data, NaN nulls) MIMC3_EUNSUPPORTED.
+ *   Refusals: npeaks outside 0..8, or cand NULL with npeaks > 0 / not NULL with npeaks = 0: MIMC3_EINVAL; ocw, R, a chip that leaves
+ *   the image, a search box beyond the zero border: as mimc3_match_ncc_full.  The coarse-to-fine search stays 8-bit only. */
+int mimc3_match_ncc_full_planes(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                                const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                                int32_t swap, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/);
+/* Device-resident variant: enqueue only, the contract of mimc3_match_ncc_full_multi_dev (d_cand NULL iff npeaks == 0). */
+int mimc3_match_ncc_full_planes_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                    const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                                    float *d_cand, void *stream);
 
 /* ---- Coarse-to-fine exhaustive search over an image pyramid (no reference counterpart: the reach of mimc3_match_ncc_full, +-R
  *      around uv0 + offset + shift, made about R (2^L - 1) px by searching a reduced pair first -- the offset trackers' standard).

@@ -53,6 +53,9 @@ _lib.mimc3_match_ncc_full_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_in
 _lib.mimc3_match_ncc_full_multi.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p]
 _lib.mimc3_match_ncc_full_multi_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                 _vp, _vp, _vp]
+_lib.mimc3_match_ncc_full_planes.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp]
+_lib.mimc3_match_ncc_full_planes_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 _vp, _vp, _vp]
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
 _lib.mimc3_match_ncc_pyramid_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
@@ -486,6 +489,54 @@ class Context:
         _check(_lib.mimc3_match_ncc_full_multi_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                                    npeaks, 1 if swap else 0, d_out, d_cand, stream), "match_ncc_full_multi_dev")
 
+    def match_ncc_full_planes(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False):
+        """The exhaustive search on the pair the context matches on (mimc3_match_ncc_full_planes): an 8-bit pair, or a scaled-integer
+        one -- 12-bit DN, the pair after filter_images -> (float32[N][8] record as match_ncc_full, float32[npeaks][N][3] candidates
+        as match_ncc_full_multi, or None when npeaks == 0)."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_full_planes: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_full_planes(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
+                                                None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, out,
+                                                None if cand is None else cand.ctypes.data), "match_ncc_full_planes")
+        return out, cand
+
+    def match_ncc_full_planes_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False):
+        """Device-pointer variant (enqueue only): as match_ncc_full_multi_dev; d_cand 0 with npeaks == 0."""
+        _check(_lib.mimc3_match_ncc_full_planes_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                    npeaks, 1 if swap else 0, d_out, d_cand or None, stream), "match_ncc_full_planes_dev")
+
+    def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None):
+        """The candidates of the exhaustive search over image variants and chip sizes -> dp float32[ndp][N][3], ndp = len(kernels) *
+        len(vec_ocw) * npeaks <= 64: for each variant in order (None = the raw pair, else filter_images(kernel)) and each ocw one
+        forward match_ncc_full_planes call, its candidates stacked variant-major, then ocw, then peak rank -- what
+        calc_mean_var_num_dp_cluster and mimc2_postprocess read.  Every variant is filtered from fresh planes (see filter_images).
+        The pair is left unfiltered."""
+        kernels = tuple(kernels); vec_ocw = tuple(int(o) for o in vec_ocw); npeaks = int(npeaks)
+        ndp = len(kernels) * len(vec_ocw) * npeaks
+        if npeaks < 1 or ndp < 1:
+            raise ValueError("full_candidates: npeaks, kernels and vec_ocw must not be empty")
+        if ndp > 64:
+            raise ValueError(f"full_candidates: ndp = {len(kernels)} x {len(vec_ocw)} x {npeaks} = {ndp} > 64")
+        blocks = []
+        try:
+            for k in kernels:
+                self.filter_images(None)                  # (fresh planes: see filter_images)
+                if k is not None:
+                    self.filter_images(k)
+                for ocw in vec_ocw:
+                    blocks.append(self.match_ncc_full_planes(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
+        finally:
+            self.filter_images(None)
+        return np.concatenate(blocks, axis=0)
+
     def match_ncc_pyramid(self, xyuvav, offset, ocw, radius, levels, shift=None, swap=False):
         """Coarse-to-fine exhaustive search over an image pyramid (mimc3_match_ncc_pyramid) on the resident 8-bit pair ->
         (float32[N][8] record as match_ncc_full, int32[N][2] shift_out).  The search at +-radius runs on the pair reduced levels - 1
@@ -667,7 +718,12 @@ class Context:
                "GMA_float_conv2_dev")
 
     def filter_images(self, kernel):
-        """Filter the resident pair on the device and match on the filtered pair from now on; None = back to raw."""
+        """Filter the resident pair on the device and match on the filtered pair from now on; None = back to raw.
+        As in the reference program, the output planes are allocated once and a filter never writes their border but reads it (the
+        minimum, the shifted right-hand columns): what one filter leaves there is input to the next.  Two filters in a row
+        therefore differ from each on its own in the border, and the leftovers can take the pair out of the scaled-integer class
+        (negative border values: the f32 kernels then match it, and match_ncc_full_planes refuses it).  filter_images(None) in
+        between starts the next filter from fresh planes."""
         if kernel is None:
             _check(_lib.mimc3_ctx_filter_images(self._h, None, 0, 0), "filter_images")
             return
@@ -740,7 +796,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

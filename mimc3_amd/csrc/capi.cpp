@@ -789,8 +789,11 @@ extern "C" int mimc3_match_ncc_full_multi_dev(mimc3_ctx *c, const double *d_xyuv
 }
 
 // the host entry of the exhaustive search: its checks, the uploads, the device entry and the copies back (cand null: the record alone)
+// (planes: mimc3_match_ncc_full_planes -- a scaled-integer pair is taken too, on its u16 planes)
+static int full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
+                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream);
 static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
-                     int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry)
+                     int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, bool planes = false)
 {
     const std::string en(entry);
     if (!c || !xyuvav || !offset || !out || N <= 0 || (multi && !cand)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
@@ -798,7 +801,8 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
     if (multi && (npeaks < 1 || npeaks > mimc3::kFullMaxPeaks)) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 1..8");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
+    if (planes && !c->u8_ok && !c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
+    if (!planes && !c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
     // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
     RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
     const int64_t pad = mimc3::kU8Pad;
@@ -820,9 +824,12 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
         RC_TRY(h2d_copy(c, c->puv.p, shift, sizeof(int32_t) * 2 * (size_t)N));
         d_shift = static_cast<const int32_t *>(c->puv.p);
     }
-    const int rc = full_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
-                            static_cast<float *>(c->out.p), multi ? static_cast<float *>(c->full_cand.p) : nullptr, c->stream,
-                            multi ? "mimc3_match_ncc_full_multi_dev" : "mimc3_match_ncc_full_dev");
+    float *d_cand = multi ? static_cast<float *>(c->full_cand.p) : nullptr;
+    const int rc = planes ? full_planes_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
+                                            static_cast<float *>(c->out.p), d_cand, c->stream)
+                          : full_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
+                                     static_cast<float *>(c->out.p), d_cand, c->stream,
+                                     multi ? "mimc3_match_ncc_full_multi_dev" : "mimc3_match_ncc_full_dev");
     if (rc) return rc;
     RC_TRY(d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N));
     if (multi) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
@@ -839,6 +846,51 @@ extern "C" int mimc3_match_ncc_full_multi(mimc3_ctx *c, const double *xyuvav, in
                                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand)
 {
     return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, true, "mimc3_match_ncc_full_multi");
+}
+
+// ---------------------------------------------------------------------------------------------
+// the exhaustive search on the planes the context matches on (mimc3_match_ncc_full_planes): an 8-bit pair through the entries above,
+// untouched; a scaled-integer pair (12-bit DN, a filtered 8-bit pair) through match_full_u16_kernel.hip on its u16 planes
+// ---------------------------------------------------------------------------------------------
+static int full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
+                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream)
+{
+    const std::string en("mimc3_match_ncc_full_planes_dev");
+    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
+    if (c->u8_ok || !c->d_i0 || !c->d_i1 || c->child || !full_ocw_ok(ocw) || R < 1 || R > 15)      // (the 8-bit path, and every refusal it shares)
+        return full_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream, en.c_str());
+    if (!c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!c->hpl_valid || !c->sat_u16_ok) RC_TRY(build_u16(c, true));
+    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
+    u.full_shift = d_shift; u.full_R = R;
+    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
+    u.p0 = static_cast<const unsigned char *>(c->hpl0.p); u.p1 = static_cast<const unsigned char *>(c->hpl1.p);
+    u.sat0 = c->hsat0.p; u.sat1 = c->hsat1.p; u.satz0 = c->hsz0.p; u.satz1 = c->hsz1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    const hipError_t e = mimc3::launch_match_full_u16(u, s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "full-search u16 kernel launch");
+    c->last_path = 7;
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                               const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap,
+                                               float *d_out, float *d_cand, void *stream)
+{
+    return full_planes_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream);
+}
+
+extern "C" int mimc3_match_ncc_full_planes(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand)
+{
+    const char *en = "mimc3_match_ncc_full_planes";
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
+    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, true);
 }
 
 // ---------------------------------------------------------------------------------------------

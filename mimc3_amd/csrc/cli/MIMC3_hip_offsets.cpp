@@ -1,7 +1,7 @@
 // MIMC3_hip_offsets -- exhaustive-search NCC offsets with peak quality over libmimc3_hip.so (MI355X): the AMPCOR-style table that
 // MIMC_single_match.c:1-27 describes.
 //
-//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1]
+//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1] [filter=0]
 //
 // Inputs as for MIMC3_hip (the file names start with YYYYMMDDhhmmss; dt from the two timestamps); both images 8-bit.  Steps: the
 // control-point offset (mimc3_vmap_cp, as the reference program measures it), the a-priori shift of every grid point
@@ -16,6 +16,10 @@
 //   candidates_<t0>_<t1>.GMA  peaks = K > 1 (with levels = 1 only): f32 [K N][3], pass-major -- row j N + i = candidate j of grid point i,
 //                          (du, dv, ncc) of its j-th best correlation peak (mimc3_match_ncc_full_multi): the dp of the post-matcher chain.
 //                          peaks = 1 writes exactly the two files above
+// filter = k in 1..3 (with levels = 1 only): the control-point offset is measured as before, then the pair is filtered on the device with
+//   the reference program's k-th kernel (MIMC_main.c:176-194: d/dx, d/dy, Laplacian) and searched on the filtered pair
+//   (mimc3_match_ncc_full_planes); the files are offsets_<t0>_<t1>_f<k>.GMA / .txt and candidates_<t0>_<t1>_f<k>.GMA.  filter = 0 writes
+//   exactly the files of a run without the argument
 // Environment: MIMC3_HIP_DEVICE (default 0), MIMC3_CP_SEED (as for MIMC3_hip).
 #include <cstdint>
 #include <cstdio>
@@ -30,12 +34,18 @@
 int main(int argc, char *argv[])
 {
     printf("MIMC3_hip_offsets -- MI355X build (%s)\n", mimc3_version());
-    if (argc < 5 || argc > 9) {
-        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1]\n", argv[0]);
+    if (argc < 5 || argc > 10) {
+        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1] [filter=0]\n", argv[0]);
         return 2;
     }
     const int32_t ocw = argc > 5 ? atoi(argv[5]) : 15, R = argc > 6 ? atoi(argv[6]) : 15, levels = argc > 7 ? atoi(argv[7]) : 1;
     const int32_t peaks = argc > 8 ? atoi(argv[8]) : 1;
+    const int32_t filter = argc > 9 ? atoi(argv[9]) : 0;
+    if (filter < 0 || filter > 3) { fprintf(stderr, "filter must be 0 (raw), 1 (d/dx), 2 (d/dy) or 3 (Laplacian)\n"); return 2; }
+    if (filter != 0 && levels != 1) {
+        fprintf(stderr, "filter > 0 needs levels = 1: the coarse-to-fine search runs on the raw 8-bit pair only\n");
+        return 2;
+    }
     if (peaks != 1 && levels != 1) {
         fprintf(stderr, "peaks > 1 needs levels = 1: candidates on a pyramid's level 0 are not supported\n");
         return 2;
@@ -46,7 +56,8 @@ int main(int argc, char *argv[])
         return 2;
     }
     const float dt = (float)(datenum(t1) - datenum(t0));
-    const std::string base = std::string(argv[4]) + "/offsets_" + t0 + "_" + t1;
+    const std::string tag = std::string(t0) + "_" + t1 + (filter ? "_f" + std::to_string(filter) : std::string());
+    const std::string base = std::string(argv[4]) + "/offsets_" + tag;
     std::vector<double> xy;
     int32_t N = 0, ncol = 0;
     if (!load_gma_double(argv[3], xy, N, ncol) || ncol != 6) { fprintf(stderr, "cannot read %s as an [N][6] float64 .GMA\n", argv[3]); return 2; }
@@ -75,12 +86,21 @@ int main(int argc, char *argv[])
     printf("dt=%f days, MPP=%f; control-point offset [%d, %d] pixels (i1-i0); ocw=%d, R=%d, %d grid points\n", dt, r.mpp, offset[0],
            offset[1], ocw, R, N);
     if (levels != 1) printf("coarse-to-fine over %d pyramid levels\n", levels);
+    if (filter) {                              // the reference program's filter kernels (MIMC_main.c:176-194), in its order
+        static const float gx[3] = {-1, 0, 1}, lap[9] = {-0.125f, -0.125f, -0.125f, -0.125f, 1, -0.125f, -0.125f, -0.125f, -0.125f};
+        const int rcf = filter == 1 ? mimc3_ctx_filter_images(ctx, gx, 1, 3) : filter == 2 ? mimc3_ctx_filter_images(ctx, gx, 3, 1)
+                                                                                             : mimc3_ctx_filter_images(ctx, lap, 3, 3);
+        if (rcf) { fprintf(stderr, "%s\n", mimc3_last_error()); return leave(3); }
+        printf("searching on the pair filtered with kernel %d\n", filter);
+    }
     std::vector<int32_t> shift(2 * (size_t)N);
     std::vector<float> rec(8 * (size_t)N);
     std::vector<float> cand(peaks != 1 ? 3 * (size_t)(peaks > 0 ? peaks : 0) * (size_t)N : 0);
     if (peaks != 1) printf("the %d best correlation peaks of every grid point as candidates\n", peaks);
     if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
-        (peaks != 1 ? mimc3_match_ncc_full_multi(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks, 0, rec.data(), cand.data())
+        (filter ? mimc3_match_ncc_full_planes(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
+                                              peaks != 1 ? cand.data() : nullptr)
+         : peaks != 1 ? mimc3_match_ncc_full_multi(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks, 0, rec.data(), cand.data())
          : levels == 1 ? mimc3_match_ncc_full(ctx, xy.data(), N, offset, shift.data(), ocw, R, 0, rec.data())
                        : mimc3_match_ncc_pyramid(ctx, xy.data(), N, offset, shift.data(), ocw, R, levels, 0, rec.data(), nullptr))) {
         fprintf(stderr, "%s\n", mimc3_last_error());
@@ -95,7 +115,7 @@ int main(int argc, char *argv[])
         nok += rec[8 * (size_t)g + 2] >= -1.0f;
     }
     bool ok = save_gma(base + ".GMA", out.data(), N, 10);
-    if (peaks != 1) ok = save_gma(std::string(argv[4]) + "/candidates_" + t0 + "_" + t1 + ".GMA", cand.data(), peaks * N, 3) && ok;
+    if (peaks != 1) ok = save_gma(std::string(argv[4]) + "/candidates_" + tag + ".GMA", cand.data(), peaks * N, 3) && ok;
     FILE *f = fopen((base + ".txt").c_str(), "w");
     if (f) {
         fprintf(f, "# u du v dv snr h_uu h_vv h_uv   (du, dv include the control-point offset %d %d)\n", offset[0], offset[1]);

@@ -174,6 +174,10 @@ hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, hipStream_t 
 // best local maxima as (du, dv, ncc) candidates (mimc3_match_ncc_full_multi) -- null selects the kernels without that tail
 constexpr int kFullMaxPeaks = 8;
 hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream);
+// the same search on the zero-bordered u16 planes of a scaled-integer pair (match_full_u16_kernel.hip): a.p0 / a.p1 the u16 planes, a.sat0 /
+// a.sat1 their packed tables, a.satz0 / a.satz1 their null tables; a.full_shift, a.full_R, a.full_cand / a.full_npeaks and a.out as above.  Two
+// launches, the points without nulls and those with; no flags, lists or scratch
+hipError_t launch_match_full_u16(MatchU8Args a, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all
