@@ -78,7 +78,9 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *   0 = general f32 kernel (any ocw, any window size) otherwise;
  *   6 = the exhaustive search (mimc3_match_ncc_full, mimc3_match_ncc_full_multi, mimc3_match_ncc_pyramid): the matrix-core kernel's surfaces, every point
  *       on the matrix cores (it does not depend on the mode);
- *   7 = the exhaustive search of mimc3_match_ncc_full_planes on a scaled-integer pair: the u16 planes' register-tiled search kernel.
+ *   7 = the exhaustive search of mimc3_match_ncc_full_planes on a scaled-integer pair: the u16 planes' register-tiled search kernel;
+ *   8 = the exhaustive search of mimc3_match_ncc_full_dn on an integral-f32 pair (16-bit DN and its filtered forms): the f32 planes'
+ *       search kernel.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -208,7 +210,7 @@ int mimc3_match_ncc_full_multi_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32
  *                      the square root (an even exponent) and with the division -- the reference's cell formula on the float pixels
  *                      equals the same formula on the integers q bit for bit.  The record and the candidates come from the same
  *                      code as on 8-bit pairs.
- *     anything else    (16-bit DN, non-integral data, NaN nulls) MIMC3_EUNSUPPORTED.
+ *     anything else    (16-bit DN, non-integral data, NaN nulls) MIMC3_EUNSUPPORTED.  (mimc3_match_ncc_full_dn takes 16-bit DN.)
  *   Refusals: npeaks outside 0..8, or cand NULL with npeaks > 0 / not NULL with npeaks = 0: MIMC3_EINVAL; ocw, R, a chip that leaves
  *   the image, a search box beyond the zero border: as mimc3_match_ncc_full.  The coarse-to-fine search stays 8-bit only. */
 int mimc3_match_ncc_full_planes(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
@@ -218,6 +220,41 @@ int mimc3_match_ncc_full_planes(mimc3_ctx *ctx, const double *xyuvav, int32_t N,
 int mimc3_match_ncc_full_planes_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                     const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
                                     float *d_cand, void *stream);
+
+/* ---- Exhaustive search on every pair the planes' matchers take: the two classes above and integral-f32 pairs -- 16-bit DN (Landsat 8/9
+ *      OLI, Sentinel-2) and what mimc3_ctx_filter_images makes of it.
+ *
+ *   A superset of mimc3_match_ncc_full_planes: its arguments, checks, record, candidates, statuses and empty-slot encodings word for
+ *   word, with one more class.  It runs on the pair the context currently matches on:
+ *     8-bit pair       as mimc3_match_ncc_full_planes; results bit for bit.  mimc3_ctx_last_path reports 6.
+ *     scaled-integer   as mimc3_match_ncc_full_planes; results bit for bit.  mimc3_ctx_last_path reports 7.
+ *     integral f32     (every pixel w / 2^s with w an integer in [0, 2^20), s = 0 or 3 per image, and the pair in neither class above)
+ *                      the search runs on the zero-bordered f32 planes and their 16-byte summed-area tables (sum w | nulls << 40,
+ *                      sum fl(w w)), built on the first call that needs them and kept until the pair changes.  A pixel is null
+ *                      exactly when it is 0 (MIN_DN = 1e-10 lies below 1/8); box pixels outside the image are the 256-px zero border.
+ *                      mimc3_ctx_last_path reports 8.
+ *                      The cell is the one defined above, the reference's (MIMC_module.c:719-734): f32 pixel products, f64 sums, the
+ *                      f64 expression without contraction, cast to f32.  On this class the f32 product ROUNDS (w_a w_b reaches 2^40,
+ *                      an f32 holds 24 bits), and that rounding is part of the result: sxx, syy and sxy are sums of
+ *                      (double)(float)(a * b), not of exact products.  What stays exact: fl(w_a w_b) is an integer below 2^40 and
+ *                      a chip has at most 6,561 pixels, so every f64 sum is an exact integer below 2^53 in any order; and the
+ *                      scales 2^-s commute with the product's rounding and with every later operation (the square root sees the
+ *                      even exponent 2 (sa + sb), the division cancels it), so the kernel works on the integers w alone.  What does
+ *                      not: n sxy, sx sy and the variance terms pass 2^53 (up to about 2^57) and round, so the finish performs
+ *                      the reference's operations one by one -- each product, each difference, the variance product, sqrt, the
+ *                      division, all correctly rounded f64 -- and not the reciprocal-square-root shortcut of the other classes,
+ *                      whose guard was argued for exact inputs.  The record and the candidates come from the same code as on
+ *                      every other class.
+ *     anything else    (non-integral data, NaN nulls, values of 2^20 and above) MIMC3_EUNSUPPORTED.
+ *   Refusals: those of mimc3_match_ncc_full_planes; a chip-atlas context: MIMC3_ESTATE.  The coarse-to-fine search stays 8-bit only. */
+int mimc3_match_ncc_full_dn(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                            const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                            int32_t swap, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_planes_dev.  (The first call on an integral-f32 pair builds its planes
+ * and tables on the context's own stream and waits for them before it enqueues on `stream`.) */
+int mimc3_match_ncc_full_dn_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                                float *d_cand, void *stream);
 
 /* ---- Coarse-to-fine exhaustive search over an image pyramid (no reference counterpart: the reach of mimc3_match_ncc_full, +-R
  *      around uv0 + offset + shift, made about R (2^L - 1) px by searching a reduced pair first -- the offset trackers' standard).

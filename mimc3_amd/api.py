@@ -56,6 +56,9 @@ _lib.mimc3_match_ncc_full_multi_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, 
 _lib.mimc3_match_ncc_full_planes.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp]
 _lib.mimc3_match_ncc_full_planes_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  _vp, _vp, _vp]
+_lib.mimc3_match_ncc_full_dn.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp]
+_lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             _vp, _vp, _vp]
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
 _lib.mimc3_match_ncc_pyramid_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
@@ -513,10 +516,34 @@ class Context:
         _check(_lib.mimc3_match_ncc_full_planes_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                                     npeaks, 1 if swap else 0, d_out, d_cand or None, stream), "match_ncc_full_planes_dev")
 
+    def match_ncc_full_dn(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False):
+        """The exhaustive search on every pair the planes' matchers take (mimc3_match_ncc_full_dn): what match_ncc_full_planes takes,
+        bit for bit, and an integral-f32 pair -- 16-bit DN, and what filter_images makes of it -> (float32[N][8] record,
+        float32[npeaks][N][3] candidates, or None when npeaks == 0)."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_full_dn: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_full_dn(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
+                                            None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, out,
+                                            None if cand is None else cand.ctypes.data), "match_ncc_full_dn")
+        return out, cand
+
+    def match_ncc_full_dn_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False):
+        """Device-pointer variant (enqueue only): as match_ncc_full_planes_dev."""
+        _check(_lib.mimc3_match_ncc_full_dn_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                npeaks, 1 if swap else 0, d_out, d_cand or None, stream), "match_ncc_full_dn_dev")
+
     def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None):
         """The candidates of the exhaustive search over image variants and chip sizes -> dp float32[ndp][N][3], ndp = len(kernels) *
         len(vec_ocw) * npeaks <= 64: for each variant in order (None = the raw pair, else filter_images(kernel)) and each ocw one
-        forward match_ncc_full_planes call, its candidates stacked variant-major, then ocw, then peak rank -- what
+        forward match_ncc_full_dn call, its candidates stacked variant-major, then ocw, then peak rank -- what
         calc_mean_var_num_dp_cluster and mimc2_postprocess read.  Every variant is filtered from fresh planes (see filter_images).
         The pair is left unfiltered."""
         kernels = tuple(kernels); vec_ocw = tuple(int(o) for o in vec_ocw); npeaks = int(npeaks)
@@ -532,7 +559,7 @@ class Context:
                 if k is not None:
                     self.filter_images(k)
                 for ocw in vec_ocw:
-                    blocks.append(self.match_ncc_full_planes(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
+                    blocks.append(self.match_ncc_full_dn(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
         finally:
             self.filter_images(None)
         return np.concatenate(blocks, axis=0)
@@ -796,7 +823,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

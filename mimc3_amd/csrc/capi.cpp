@@ -789,12 +789,18 @@ extern "C" int mimc3_match_ncc_full_multi_dev(mimc3_ctx *c, const double *d_xyuv
 }
 
 // the host entry of the exhaustive search: its checks, the uploads, the device entry and the copies back (cand null: the record alone)
-// (planes: mimc3_match_ncc_full_planes -- a scaled-integer pair is taken too, on its u16 planes)
+// (kind 1: mimc3_match_ncc_full_planes -- a scaled-integer pair is taken too, on its u16 planes; kind 2: mimc3_match_ncc_full_dn -- and an
+//  integral-f32 pair on its f32 planes)
 static int full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream);
+                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream,
+                           const char *entry = "mimc3_match_ncc_full_planes_dev");
+static int full_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
+                       int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream);
+static int full_dn_class(mimc3_ctx *c, const std::string &en);
 static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
-                     int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, bool planes = false)
+                     int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, int kind = 0)
 {
+    const bool planes = kind == 1;
     const std::string en(entry);
     if (!c || !xyuvav || !offset || !out || N <= 0 || (multi && !cand)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
@@ -802,7 +808,8 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     if (multi && (npeaks < 1 || npeaks > mimc3::kFullMaxPeaks)) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 1..8");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
     if (planes && !c->u8_ok && !c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
-    if (!planes && !c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
+    if (kind == 0 && !c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
+    if (kind == 2) RC_TRY(full_dn_class(c, en));
     // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
     RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
     const int64_t pad = mimc3::kU8Pad;
@@ -825,8 +832,10 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
         d_shift = static_cast<const int32_t *>(c->puv.p);
     }
     float *d_cand = multi ? static_cast<float *>(c->full_cand.p) : nullptr;
-    const int rc = planes ? full_planes_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
-                                            static_cast<float *>(c->out.p), d_cand, c->stream)
+    const int rc = kind == 2 ? full_dn_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
+                                           static_cast<float *>(c->out.p), d_cand, c->stream)
+                   : planes ? full_planes_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
+                                              static_cast<float *>(c->out.p), d_cand, c->stream)
                           : full_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
                                      static_cast<float *>(c->out.p), d_cand, c->stream,
                                      multi ? "mimc3_match_ncc_full_multi_dev" : "mimc3_match_ncc_full_dev");
@@ -853,9 +862,9 @@ extern "C" int mimc3_match_ncc_full_multi(mimc3_ctx *c, const double *xyuvav, in
 // untouched; a scaled-integer pair (12-bit DN, a filtered 8-bit pair) through match_full_u16_kernel.hip on its u16 planes
 // ---------------------------------------------------------------------------------------------
 static int full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream)
+                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream, const char *entry)
 {
-    const std::string en("mimc3_match_ncc_full_planes_dev");
+    const std::string en(entry);
     if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
     if (c->u8_ok || !c->d_i0 || !c->d_i1 || c->child || !full_ocw_ok(ocw) || R < 1 || R > 15)      // (the 8-bit path, and every refusal it shares)
@@ -890,7 +899,66 @@ extern "C" int mimc3_match_ncc_full_planes(mimc3_ctx *c, const double *xyuvav, i
     const char *en = "mimc3_match_ncc_full_planes";
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
     if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, true);
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 1);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the exhaustive search on every class the planes' matchers take (mimc3_match_ncc_full_dn): 8-bit and scaled-integer pairs through the
+// entries above, untouched; an integral-f32 pair (16-bit DN and its filtered forms: every pixel x 1 or x 8 an integer in [0, 2^20))
+// through match_full_f32_kernel.hip on its f32 planes and 16-byte tables (build_f32)
+// ---------------------------------------------------------------------------------------------
+// the class of a pair that is neither 8-bit nor scaled-integer: its f32 planes and tables are built on first use (drains the stream)
+static int full_dn_class(mimc3_ctx *c, const std::string &en)
+{
+    if (c->u8_ok || c->u16_ok) return 0;
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->fplanes_ok) RC_TRY(build_f32(c));
+    if (!c->f32i_ok)
+        return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit, scaled-integer nor integral f32 (pixels x 1 or x 8 integers below 2^20)");
+    return 0;
+}
+
+static int full_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
+                       int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream)
+{
+    const char *entry = "mimc3_match_ncc_full_dn_dev";
+    const std::string en(entry);
+    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
+    if (c->u8_ok || c->u16_ok || !c->d_i0 || !c->d_i1 || c->child || !full_ocw_ok(ocw) || R < 1 || R > 15)      // (the other classes, and every refusal they share)
+        return full_planes_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream, entry);
+    RC_TRY(full_dn_class(c, en));
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
+    u.full_shift = d_shift; u.full_R = R;
+    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
+    u.p0 = static_cast<const unsigned char *>(c->fpl0.p); u.p1 = static_cast<const unsigned char *>(c->fpl1.p);
+    u.sat0 = c->fsat0.p; u.sat1 = c->fsat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
+    u.scale0 = 1.0 / (double)(1 << c->fshift0); u.scale1 = 1.0 / (double)(1 << c->fshift1);
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    const hipError_t e = mimc3::launch_match_full_f32(u, s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "full-search f32 kernel launch");
+    c->last_path = 8;
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_full_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                           const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap,
+                                           float *d_out, float *d_cand, void *stream)
+{
+    return full_dn_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream);
+}
+
+extern "C" int mimc3_match_ncc_full_dn(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                       int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand)
+{
+    const char *en = "mimc3_match_ncc_full_dn";
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
+    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 2);
 }
 
 // ---------------------------------------------------------------------------------------------

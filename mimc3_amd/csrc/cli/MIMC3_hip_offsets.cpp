@@ -3,7 +3,8 @@
 //
 //     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1] [filter=0]
 //
-// Inputs as for MIMC3_hip (the file names start with YYYYMMDDhhmmss; dt from the two timestamps); both images 8-bit.  Steps: the
+// Inputs as for MIMC3_hip (the file names start with YYYYMMDDhhmmss; dt from the two timestamps); both images 8-bit, or both 16-bit
+// (see below).  Steps: the
 // control-point offset (mimc3_vmap_cp, as the reference program measures it), the a-priori shift of every grid point
 // (mimc3_prior_shift), then every offset in [-R, R]^2 around uv0 + offset + shift (mimc3_match_ncc_full), or -- levels > 1 -- the
 // coarse-to-fine search that starts there on a pair reduced levels - 1 times (mimc3_match_ncc_pyramid: a reach of about
@@ -20,6 +21,9 @@
 //   the reference program's k-th kernel (MIMC_main.c:176-194: d/dx, d/dy, Laplacian) and searched on the filtered pair
 //   (mimc3_match_ncc_full_planes); the files are offsets_<t0>_<t1>_f<k>.GMA / .txt and candidates_<t0>_<t1>_f<k>.GMA.  filter = 0 writes
 //   exactly the files of a run without the argument
+// Two 16-bit TIFFs (levels = 1 only: the pyramid stays 8-bit): the same steps and the same files, the search through
+//   mimc3_match_ncc_full_dn, which takes whatever the files hold -- 16-bit DN, or 8- and 12-bit DN in a 16-bit container -- raw or
+//   filtered.  One 8-bit and one 16-bit file are refused
 // Environment: MIMC3_HIP_DEVICE (default 0), MIMC3_CP_SEED (as for MIMC3_hip).
 #include <cstdint>
 #include <cstdio>
@@ -64,14 +68,24 @@ int main(int argc, char *argv[])
     RawImage i0, i1;
     if (!load_tiff(argv[1], i0) || !load_tiff(argv[2], i1)) { fprintf(stderr, "cannot read the TIFF images\n"); return 2; }
     if (i0.H != i1.H || i0.W != i1.W) { fprintf(stderr, "the two images differ in size\n"); return 2; }
-    if (i0.bpp != 1 || i1.bpp != 1) { fprintf(stderr, "the exhaustive search takes 8-bit images only\n"); return 2; }
+    if (i0.bpp != i1.bpp || (i0.bpp != 1 && i0.bpp != 2)) {
+        fprintf(stderr, "the exhaustive search takes two 8-bit or two 16-bit images\n");
+        return 2;
+    }
+    const bool dn16 = i0.bpp == 2;
+    if (dn16 && levels != 1) {
+        fprintf(stderr, "16-bit images need levels = 1: the coarse-to-fine search runs on 8-bit pairs only\n");
+        return 2;
+    }
     const char *dev = getenv("MIMC3_HIP_DEVICE");
     mimc3_ctx *ctx = nullptr;
     auto leave = [&](int code) -> int {        // (as MIMC3_hip: no runtime teardown on the way out)
         fflush(nullptr);
         _exit(code);
     };
-    if (mimc3_ctx_create(dev ? atoi(dev) : 0, &ctx) || mimc3_ctx_set_images_u8(ctx, i0.px.data(), i1.px.data(), i0.H, i0.W)) {
+    if (mimc3_ctx_create(dev ? atoi(dev) : 0, &ctx) ||
+        (dn16 ? mimc3_ctx_set_images_u16(ctx, reinterpret_cast<const uint16_t *>(i0.px.data()), reinterpret_cast<const uint16_t *>(i1.px.data()), i0.H, i0.W)
+              : mimc3_ctx_set_images_u8(ctx, i0.px.data(), i1.px.data(), i0.H, i0.W))) {
         fprintf(stderr, "%s\n", mimc3_last_error());
         return leave(3);
     }
@@ -98,8 +112,10 @@ int main(int argc, char *argv[])
     std::vector<float> cand(peaks != 1 ? 3 * (size_t)(peaks > 0 ? peaks : 0) * (size_t)N : 0);
     if (peaks != 1) printf("the %d best correlation peaks of every grid point as candidates\n", peaks);
     if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
-        (filter ? mimc3_match_ncc_full_planes(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
-                                              peaks != 1 ? cand.data() : nullptr)
+        (dn16 ? mimc3_match_ncc_full_dn(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
+                                        peaks != 1 ? cand.data() : nullptr)
+         : filter ? mimc3_match_ncc_full_planes(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
+                                                peaks != 1 ? cand.data() : nullptr)
          : peaks != 1 ? mimc3_match_ncc_full_multi(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks, 0, rec.data(), cand.data())
          : levels == 1 ? mimc3_match_ncc_full(ctx, xy.data(), N, offset, shift.data(), ocw, R, 0, rec.data())
                        : mimc3_match_ncc_pyramid(ctx, xy.data(), N, offset, shift.data(), ocw, R, levels, 0, rec.data(), nullptr))) {

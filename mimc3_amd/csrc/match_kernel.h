@@ -178,6 +178,10 @@ hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream);
 // a.sat1 their packed tables, a.satz0 / a.satz1 their null tables; a.full_shift, a.full_R, a.full_cand / a.full_npeaks and a.out as above.  Two
 // launches, the points without nulls and those with; no flags, lists or scratch
 hipError_t launch_match_full_u16(MatchU8Args a, hipStream_t stream);
+// the same search on the zero-bordered f32 planes of an integral-f32 pair (match_full_f32_kernel.hip; 16-bit DN and its filtered forms):
+// a.p0 / a.p1 the f32 planes, a.sat0 / a.sat1 their 16-byte tables (Sat2), a.scale0 / a.scale1 = 2^-s of each image (pixel * 2^s is the
+// integer the tables sum); the rest as above.  Two launches, dynamic LDS sized by a.full_R
+hipError_t launch_match_full_f32(MatchU8Args a, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all
