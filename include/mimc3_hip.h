@@ -212,7 +212,7 @@ int mimc3_match_ncc_full_multi_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32
  *                      code as on 8-bit pairs.
  *     anything else    (16-bit DN, non-integral data, NaN nulls) MIMC3_EUNSUPPORTED.  (mimc3_match_ncc_full_dn takes 16-bit DN.)
  *   Refusals: npeaks outside 0..8, or cand NULL with npeaks > 0 / not NULL with npeaks = 0: MIMC3_EINVAL; ocw, R, a chip that leaves
- *   the image, a search box beyond the zero border: as mimc3_match_ncc_full.  The coarse-to-fine search stays 8-bit only. */
+ *   the image, a search box beyond the zero border: as mimc3_match_ncc_full.  (mimc3_match_ncc_pyramid_dn is the coarse-to-fine search on these pairs.) */
 int mimc3_match_ncc_full_planes(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                                 const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
                                 int32_t swap, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/);
@@ -246,7 +246,7 @@ int mimc3_match_ncc_full_planes_dev(mimc3_ctx *ctx, const double *d_xyuvav, int3
  *                      whose guard was argued for exact inputs.  The record and the candidates come from the same code as on
  *                      every other class.
  *     anything else    (non-integral data, NaN nulls, values of 2^20 and above) MIMC3_EUNSUPPORTED.
- *   Refusals: those of mimc3_match_ncc_full_planes; a chip-atlas context: MIMC3_ESTATE.  The coarse-to-fine search stays 8-bit only. */
+ *   Refusals: those of mimc3_match_ncc_full_planes; a chip-atlas context: MIMC3_ESTATE.  (mimc3_match_ncc_pyramid_dn is the coarse-to-fine search on these pairs.) */
 int mimc3_match_ncc_full_dn(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                             const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
                             int32_t swap, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/);
@@ -289,6 +289,46 @@ int mimc3_match_ncc_pyramid(mimc3_ctx *ctx, const double *xyuvav, int32_t N, con
 int mimc3_match_ncc_pyramid_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                 const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t swap,
                                 float *d_out, int32_t *d_shift_out /*or NULL*/, void *stream);
+/* ---- Coarse-to-fine exhaustive search on every pair mimc3_match_ncc_full_dn takes: 8-bit, scaled-integer (12-bit DN, a filtered 8-bit
+ *      pair) and integral-f32 pairs (16-bit DN -- Landsat 8/9 OLI, Sentinel-2 -- and its filtered forms), with candidates at level 0.
+ *
+ *   mimc3_match_ncc_pyramid's definition word for word -- levels 1..5, p_l = (u0 >> l, v0 >> l), d_{L-1} = floor((D + 2^{L-2}) / 2^{L-1}),
+ *   d_{l-1} = 2 (d_l + s) with the level's arg-max cell s or 2 d_l without one, shift_out = d_0 - offset, the +-2^24 bound on the starting
+ *   displacement, the refusal of a coarsest level smaller than a chip, the all-NaN record for a level-0 box beyond the zero border, one
+ *   stream and no host round trip -- with three things new:
+ *   Classes.  The pair the context currently matches on is classified once, as by mimc3_match_ncc_full_dn; the class of level 0 decides
+ *     the kernels of every level, and a level is never classified again:
+ *       8-bit pair       the u8 levels and matrix-core kernels of mimc3_match_ncc_pyramid.  mimc3_ctx_last_path reports 6.  With npeaks = 0,
+ *                        record and shift_out are mimc3_match_ncc_pyramid's bit for bit.
+ *       scaled-integer   u16 levels, the kernels of mimc3_match_ncc_full_planes.  mimc3_ctx_last_path reports 7.
+ *       integral f32     f32 levels with 16-byte tables, the kernels of mimc3_match_ncc_full_dn.  mimc3_ctx_last_path reports 8.
+ *       anything else    (non-integral data, NaN nulls, values of 2^20 and above) MIMC3_EUNSUPPORTED.
+ *   Reduction, on integers.  With w = pixel * 2^s, s the image's shift (0 or 3: the one its class was established with), a level pixel is
+ *     ((sum w + n/2) / n) / 2^s in integer arithmetic over the n non-zero pixels of its 2 x 2 block, or 0 when n = 0; H >> 1 x W >> 1 (an odd
+ *     last row or column is dropped); the level inherits the shift.  Both classes are closed under the rule (a mean of values below 4096
+ *     stays below 4096, one of values below 2^20 below 2^20; the sum stays below 2^22), and a pixel is null exactly when its whole block
+ *     is.  On an 8-bit pair s = 0 and this is mimc3_match_ncc_pyramid's reduction.
+ *     The levels are reductions of the planes the context CURRENTLY matches on: after mimc3_ctx_filter_images that is the filtered pair.
+ *     The rule is filter, then reduce -- not the filter of the reduced pair.
+ *   Candidates.  npeaks in 0..8, cand [npeaks][N][3] with npeaks > 0 (NULL with 0), as mimc3_match_ncc_full_dn.  Level 0 IS
+ *     mimc3_match_ncc_full_dn with shift = shift_out, its candidates included (on an 8-bit pair: mimc3_match_ncc_full_multi's kernels);
+ *     the coarser levels never compute candidates.  A point that gets the all-NaN record gets all-NaN candidate slots.
+ *   Refusals: those of mimc3_match_ncc_pyramid, with the class rule above in place of "not 8-bit"; npeaks outside 0..8, or cand NULL with
+ *   npeaks > 0 / not NULL with npeaks = 0: MIMC3_EINVAL.
+ *   Not covered: several devices, a candidates-over-variants driver (api.Context.full_candidates stays single-level), non-integral
+ *   floats and NaN nulls. */
+int mimc3_match_ncc_pyramid_dn(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                               const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t levels,
+                               int32_t npeaks /*0 = record only*/, int32_t swap, float *out /*[N][8] host*/,
+                               float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/, int32_t *shift_out /*[N][2] host or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_pyramid_dev, plus d_cand [npeaks][N][3] (NULL iff npeaks == 0). */
+int mimc3_match_ncc_pyramid_dn_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                   const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
+                                   float *d_out, float *d_cand, int32_t *d_shift_out /*or NULL*/, void *stream);
+/* Level `level` (1..4) of the pair the context currently matches on, as pixel values (w / 2^s): out0, out1 [H >> level][W >> level] host.
+ * Builds the levels that are missing, for any of the three classes.  A pair of no class: MIMC3_EUNSUPPORTED; a level whose image would
+ * be empty: MIMC3_EINVAL.  (For tests of the reduction.) */
+int mimc3_ctx_get_pyramid_level(mimc3_ctx *ctx, int32_t level, float *out0, float *out1);
 /* Host helper: the a-priori displacement as whole pixels, get_uv_pivot's sign convention (:559-598):
  *   shift[i] = (floor(vx dt / 365 / mpp + 0.5), floor(-vy dt / 365 / mpp + 0.5))   (f64, vx = xyuvav[i][4], vy = xyuvav[i][5]) */
 int mimc3_prior_shift(const double *xyuvav, int32_t N, float dt, float mpp, int32_t *shift /*[N][2]*/);

@@ -62,6 +62,11 @@ _lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
 _lib.mimc3_match_ncc_pyramid_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
+_lib.mimc3_match_ncc_pyramid_dn.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp,
+                                            _i32p]
+_lib.mimc3_match_ncc_pyramid_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_int32, _vp, _vp, _vp, _vp]
+_lib.mimc3_ctx_get_pyramid_level.argtypes = [_vp, C.c_int32, _f32p, _f32p]
 _lib.mimc3_prior_shift.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, _i32p]
 _lib.mimc3_pivot_corridors.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _vp]
 _lib.mimc3_get_uv_pivot_dev.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _vp]
@@ -586,6 +591,41 @@ class Context:
         d_shift_out [n][2] int32 or 0."""
         _check(_lib.mimc3_match_ncc_pyramid_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius, levels,
                                                 1 if swap else 0, d_out, d_shift_out or None, stream), "match_ncc_pyramid_dev")
+
+    def match_ncc_pyramid_dn(self, xyuvav, offset, ocw, radius, levels, npeaks=0, shift=None, swap=False):
+        """Coarse-to-fine exhaustive search (mimc3_match_ncc_pyramid_dn) on every pair match_ncc_full_dn takes: 8-bit, scaled-integer and
+        integral-f32 (16-bit DN and its filtered forms) -> (float32[N][8] record, float32[npeaks][N][3] candidates or None when
+        npeaks == 0, int32[N][2] shift_out).  The levels are reductions of the pair currently matched on (filter, then reduce); record
+        and candidates are match_ncc_full_dn's with shift = shift_out."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        sh_out = np.empty((n, 2), np.int32)
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_pyramid_dn: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_pyramid_dn(self._h, xy, n, np.ascontiguousarray(offset, np.int32), None if sh is None else sh.ctypes.data,
+                                               ocw, radius, levels, npeaks, 1 if swap else 0, out,
+                                               None if cand is None else cand.ctypes.data, sh_out), "match_ncc_pyramid_dn")
+        return out, cand, sh_out
+
+    def match_ncc_pyramid_dn_dev(self, d_xyuvav, n, offset, ocw, radius, levels, npeaks, d_out, d_cand=0, d_shift=0, d_shift_out=0, stream=0,
+                                 swap=False):
+        """Device-pointer variant (enqueue only): as match_ncc_pyramid_dev, plus d_cand [npeaks][n][3] f32 (0 with npeaks == 0)."""
+        _check(_lib.mimc3_match_ncc_pyramid_dn_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius, levels,
+                                                   npeaks, 1 if swap else 0, d_out, d_cand or None, d_shift_out or None, stream),
+               "match_ncc_pyramid_dn_dev")
+
+    def get_pyramid_level(self, level):
+        """Level `level` (1..4) of the pair currently matched on, as pixel values -> (float32[H >> level][W >> level],) * 2."""
+        H, W = self.H, self.W
+        l0 = np.empty((H >> level, W >> level), np.float32); l1 = np.empty_like(l0)
+        _check(_lib.mimc3_ctx_get_pyramid_level(self._h, level, l0, l1), "get_pyramid_level")
+        return l0, l1
 
     # -- QM -----------------------------------------------------------------------------------
     def get_dpf_pseudosmoothing(self, dpf, dpf_dx, dpf_dy, ruv, mvn, nclus, xyuvav, max_sweeps=101):

@@ -125,6 +125,10 @@ struct mimc3_ctx {
     // prepare_pair's pitch rule) with its tables; levels 1..pyr_levels hold the CURRENT pair (built on first use by build_levels)
     struct PyrLevel { DevBuf pl0, pl1, sat0, sat1; int32_t H = 0, W = 0, Wp = 0; } pyr[4];
     int pyr_levels = 0;
+    // mimc3_match_ncc_pyramid_dn: the same for the other two classes -- u16 planes with packed and null tables (a scaled-integer pair),
+    // f32 planes with 16-byte tables (an integral-f32 pair).  A pair has one class, so pyr_levels counts the levels of whichever set is its
+    struct PyrLevel16 { DevBuf pl0, pl1, sat0, sat1, sz0, sz1; int32_t H = 0, W = 0, Wp = 0; } pyr16[4];
+    struct PyrLevelF { DevBuf pl0, pl1, sat0, sat1; int32_t H = 0, W = 0, Wp = 0; } pyrf[4];
     DevBuf pyr_pos, pyr_peak, pyr_sh;   // per point: position on the level (f64 [N][2]), arg-max cell, search shift (the host entry's)
     DevBuf full_cand;                   // mimc3_match_ncc_full_multi's host entry: the candidates, f32 [npeaks][N][3]
 };
@@ -962,8 +966,9 @@ extern "C" int mimc3_match_ncc_full_dn(mimc3_ctx *c, const double *xyuvav, int32
 }
 
 // ---------------------------------------------------------------------------------------------
-// coarse-to-fine exhaustive search over an image pyramid (pyramid_kernel.hip; every level's search is the full mode of
-// match_mx_kernel.hip): the levels of the u8 pair, the per-level searches and the chaining between them on one stream
+// coarse-to-fine exhaustive search over an image pyramid (pyramid_kernel.hip; every level's search is the exhaustive search of the
+// pair's class: match_mx_kernel.hip, match_full_u16_kernel.hip or match_full_f32_kernel.hip): the levels of the pair, the per-level
+// searches and the chaining between them on one stream
 // ---------------------------------------------------------------------------------------------
 // Pyramid levels pyr_levels + 1 .. L - 1 of the u8 pair, each from the level above by the 2 x 2 null-aware reduction, with their
 // tables.  Like every plane-set builder: enqueued on the context's stream and drained before the levels count as built.
@@ -996,8 +1001,88 @@ static int build_levels(mimc3_ctx *c, int L)
     return 0;
 }
 
-// the refusals both pyramid entries make before anything runs (those of the exhaustive search, levels, the coarsest level's size)
-static int pyramid_check(const mimc3_ctx *c, int32_t ocw, int32_t R, int32_t levels, const char *entry)
+// The same for a scaled-integer pair (mimc3_match_ncc_pyramid_dn): the levels of the u16 planes q = pixel * 2^shift, which keep the
+// image's shift, with their packed and null tables.
+static int build_levels16(mimc3_ctx *c, int L)
+{
+    const int pad = mimc3::kU8Pad;
+    for (int l = c->pyr_levels + 1; l < L; ++l) {
+        mimc3_ctx::PyrLevel16 &d = c->pyr16[l - 1];
+        const bool top = l == 1;
+        const void *s0 = top ? c->hpl0.p : c->pyr16[l - 2].pl0.p, *s1 = top ? c->hpl1.p : c->pyr16[l - 2].pl1.p;
+        const int Hs = top ? c->H : c->pyr16[l - 2].H, Ws = top ? c->W : c->pyr16[l - 2].W, Wps = top ? c->Wp : c->pyr16[l - 2].Wp;
+        d.H = Hs >> 1; d.W = Ws >> 1; d.Wp = (d.W + 2 * pad + 3) & ~3;
+        const int Hp = d.H + 2 * pad;
+        const size_t bytes = sizeof(unsigned short) * (size_t)Hp * d.Wp;
+        HIP_TRY(d.pl0.reserve(bytes));
+        HIP_TRY(d.pl1.reserve(bytes));
+        HIP_TRY(d.sat0.reserve(mimc3::sat_bytes(Hp, d.Wp)));
+        HIP_TRY(d.sat1.reserve(mimc3::sat_bytes(Hp, d.Wp)));
+        HIP_TRY(d.sz0.reserve(mimc3::sat_null_bytes(Hp, d.Wp)));
+        HIP_TRY(d.sz1.reserve(mimc3::sat_null_bytes(Hp, d.Wp)));
+        HIP_TRY(c->sat_tmp.reserve(mimc3::sat_scratch_bytes(Hp, d.Wp)));
+        HIP_TRY(hipMemsetAsync(d.pl0.p, 0, bytes, c->stream));
+        HIP_TRY(hipMemsetAsync(d.pl1.p, 0, bytes, c->stream));
+        HIP_TRY(mimc3::launch_pyr_reduce_u16(static_cast<const unsigned short *>(s0), Hs, Ws, Wps, static_cast<unsigned short *>(d.pl0.p), d.H, d.W, d.Wp, pad, c->stream));
+        HIP_TRY(mimc3::launch_pyr_reduce_u16(static_cast<const unsigned short *>(s1), Hs, Ws, Wps, static_cast<unsigned short *>(d.pl1.p), d.H, d.W, d.Wp, pad, c->stream));
+        const mimc3::SatRegion rg{0, 0, d.Wp, Hp};
+        HIP_TRY(mimc3::launch_sat_u16(static_cast<const unsigned short *>(d.pl0.p), d.Wp, rg, static_cast<unsigned long long *>(d.sat0.p),
+                                      static_cast<unsigned int *>(d.sz0.p), c->sat_tmp.p, c->stream));
+        HIP_TRY(mimc3::launch_sat_u16(static_cast<const unsigned short *>(d.pl1.p), d.Wp, rg, static_cast<unsigned long long *>(d.sat1.p),
+                                      static_cast<unsigned int *>(d.sz1.p), c->sat_tmp.p, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (L - 1 > c->pyr_levels) c->pyr_levels = L - 1;
+    return 0;
+}
+
+// ... and for an integral-f32 pair: the levels of the f32 planes (reduced on the integers w = pixel * 2^fshift) with their 16-byte tables.
+static int build_levelsf(mimc3_ctx *c, int L)
+{
+    const int pad = mimc3::kU8Pad;
+    for (int l = c->pyr_levels + 1; l < L; ++l) {
+        mimc3_ctx::PyrLevelF &d = c->pyrf[l - 1];
+        const bool top = l == 1;
+        const void *s0 = top ? c->fpl0.p : c->pyrf[l - 2].pl0.p, *s1 = top ? c->fpl1.p : c->pyrf[l - 2].pl1.p;
+        const int Hs = top ? c->H : c->pyrf[l - 2].H, Ws = top ? c->W : c->pyrf[l - 2].W, Wps = top ? c->Wp : c->pyrf[l - 2].Wp;
+        d.H = Hs >> 1; d.W = Ws >> 1; d.Wp = (d.W + 2 * pad + 3) & ~3;
+        const int Hp = d.H + 2 * pad;
+        const size_t bytes = sizeof(float) * (size_t)Hp * d.Wp;
+        HIP_TRY(d.pl0.reserve(bytes));
+        HIP_TRY(d.pl1.reserve(bytes));
+        HIP_TRY(d.sat0.reserve(mimc3::sat2_bytes(Hp, d.Wp)));
+        HIP_TRY(d.sat1.reserve(mimc3::sat2_bytes(Hp, d.Wp)));
+        HIP_TRY(c->sat_tmp.reserve(mimc3::sat2_scratch_bytes(Hp, d.Wp)));
+        HIP_TRY(hipMemsetAsync(d.pl0.p, 0, bytes, c->stream));
+        HIP_TRY(hipMemsetAsync(d.pl1.p, 0, bytes, c->stream));
+        HIP_TRY(mimc3::launch_pyr_reduce_f32(static_cast<const float *>(s0), Hs, Ws, Wps, static_cast<float *>(d.pl0.p), d.H, d.W, d.Wp, pad, c->fshift0, c->stream));
+        HIP_TRY(mimc3::launch_pyr_reduce_f32(static_cast<const float *>(s1), Hs, Ws, Wps, static_cast<float *>(d.pl1.p), d.H, d.W, d.Wp, pad, c->fshift1, c->stream));
+        const mimc3::SatRegion rg{0, 0, d.Wp, Hp};
+        HIP_TRY(mimc3::launch_sat_f32i(static_cast<const float *>(d.pl0.p), d.Wp, rg, c->fshift0, static_cast<mimc3::Sat2 *>(d.sat0.p), c->sat_tmp.p, c->stream));
+        HIP_TRY(mimc3::launch_sat_f32i(static_cast<const float *>(d.pl1.p), d.Wp, rg, c->fshift1, static_cast<mimc3::Sat2 *>(d.sat1.p), c->sat_tmp.p, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (L - 1 > c->pyr_levels) c->pyr_levels = L - 1;
+    return 0;
+}
+
+// levels 1 .. L - 1 of the current pair, whatever its class (which full_dn_class has settled), and the level-0 set they start from
+static int build_levels_of_class(mimc3_ctx *c, int L)
+{
+    if (c->u8_ok) {
+        if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
+        return c->pyr_levels < L - 1 ? build_levels(c, L) : 0;
+    }
+    if (c->u16_ok) {
+        if (!c->hpl_valid || !c->sat_u16_ok) RC_TRY(build_u16(c, true));
+        return c->pyr_levels < L - 1 ? build_levels16(c, L) : 0;
+    }
+    return c->pyr_levels < L - 1 ? build_levelsf(c, L) : 0;
+}
+
+// the refusals the pyramid entries make before anything runs (those of the exhaustive search, levels, the coarsest level's size); dn: the
+// classes of mimc3_match_ncc_full_dn (an integral-f32 pair's planes are built here), else 8-bit alone
+static int pyramid_check(mimc3_ctx *c, int32_t ocw, int32_t R, int32_t levels, const char *entry, bool dn)
 {
     const std::string e(entry);
     if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, e + ": ocw must be one of 7, 15, 16, 30, 32, 40");
@@ -1005,9 +1090,67 @@ static int pyramid_check(const mimc3_ctx *c, int32_t ocw, int32_t R, int32_t lev
     if (levels < 1 || levels > 5) return mimc3::fail(MIMC3_EINVAL, e + ": levels must be in 1..5");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, e + ": images not set");
     if (c->child) return mimc3::fail(MIMC3_ESTATE, e + ": not on a chip-atlas context");
-    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, e + ": the pair is not 8-bit (u8 planes only)");
+    if (dn) RC_TRY(full_dn_class(c, e));
+    else if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, e + ": the pair is not 8-bit (u8 planes only)");
     if (std::min(c->H >> (levels - 1), c->W >> (levels - 1)) < 2 * ocw + 1)
         return mimc3::fail(MIMC3_EINVAL, e + ": level " + std::to_string(levels - 1) + " is smaller than a chip");
+    return 0;
+}
+
+// The device entry of both pyramid searches, behind their checks: the levels of the pair's class, then per level the step and the class's
+// exhaustive search with the arg-max cells; level 0 is mimc3_match_ncc_full_dn_dev's launch at shift = sh (record and candidates)
+static int pyramid_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
+                       int32_t R, int32_t levels, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, int32_t *d_shift_out, void *stream)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RC_TRY(build_levels_of_class(c, levels));
+    DevBuf &ml = c->mxl[0];
+    if (c->u8_ok) HIP_TRY(ml.reserve((size_t)N));
+    HIP_TRY(c->pyr_pos.reserve(sizeof(double) * 2 * (size_t)N));
+    HIP_TRY(c->pyr_peak.reserve(sizeof(int32_t) * (size_t)N));
+    if (!d_shift_out) HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
+    int32_t *sh = d_shift_out ? d_shift_out : static_cast<int32_t *>(c->pyr_sh.p);
+    double *pos = static_cast<double *>(c->pyr_pos.p);
+    int32_t *peak = static_cast<int32_t *>(c->pyr_peak.p);
+    const bool timing = c->timing;
+    if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    // the coarsest level's displacement d_{L-1} and positions p_{L-1} (for L = 1: shift_out = shift)
+    HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, d_shift, nullptr, R, levels - 1, true, sh, pos, s));
+    for (int l = levels - 1; l >= 1; --l) {     // level l: its planes, tables and geometry, and the arg-max cells for the step to level l - 1
+        mimc3::MatchU8Args u = u8_args(c, pos, 2, 0, N, 0, 0, ocw, swap, d_out);
+        u.full_shift = sh; u.full_R = R; u.full_peak = peak;
+        hipError_t e;
+        if (c->u8_ok) {
+            const mimc3_ctx::PyrLevel &d = c->pyr[l - 1];
+            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
+            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
+            u.sat0 = d.sat0.p; u.sat1 = d.sat1.p; u.sat_ws = mimc3::sat_pitch(d.Wp);
+            HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
+            u.mx_flags = static_cast<uint8_t *>(ml.p);
+            e = mimc3::launch_match_full_mx(u, s);
+        } else if (c->u16_ok) {
+            const mimc3_ctx::PyrLevel16 &d = c->pyr16[l - 1];
+            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
+            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
+            u.sat0 = d.sat0.p; u.sat1 = d.sat1.p; u.satz0 = d.sz0.p; u.satz1 = d.sz1.p; u.sat_ws = mimc3::sat_pitch(d.Wp);
+            e = mimc3::launch_match_full_u16(u, s);
+        } else {
+            const mimc3_ctx::PyrLevelF &d = c->pyrf[l - 1];
+            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
+            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
+            u.sat0 = d.sat0.p; u.sat1 = d.sat1.p; u.sat_ws = mimc3::sat_pitch(d.Wp);
+            u.scale0 = 1.0 / (double)(1 << c->fshift0); u.scale1 = 1.0 / (double)(1 << c->fshift1);
+            e = mimc3::launch_match_full_f32(u, s);
+        }
+        if (e != hipSuccess) return mimc3::hip_fail(e, "pyramid-level search launch");
+        HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, nullptr, peak, R, l - 1, false, sh, pos, s));
+    }
+    c->timing = false;                  // (the events bracket the whole pass, not the level-0 launch)
+    const int rc = full_dn_dev(c, d_xyuvav, N, off_u, off_v, sh, ocw, R, npeaks, swap, d_out, d_cand, stream);      // sets last_path
+    c->timing = timing;
+    if (rc) return rc;
+    if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
     return 0;
 }
 
@@ -1016,64 +1159,44 @@ extern "C" int mimc3_match_ncc_pyramid_dev(mimc3_ctx *c, const double *d_xyuvav,
                                            int32_t *d_shift_out, void *stream)
 {
     if (!c || !d_xyuvav || !d_out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_pyramid_dev: bad argument");
-    RC_TRY(pyramid_check(c, ocw, R, levels, "mimc3_match_ncc_pyramid_dev"));
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
-    if (c->pyr_levels < levels - 1) RC_TRY(build_levels(c, levels));
-    DevBuf &ml = c->mxl[0];
-    HIP_TRY(ml.reserve((size_t)N));
-    HIP_TRY(c->pyr_pos.reserve(sizeof(double) * 2 * (size_t)N));
-    HIP_TRY(c->pyr_peak.reserve(sizeof(int32_t) * (size_t)N));
-    if (!d_shift_out) HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
-    int32_t *sh = d_shift_out ? d_shift_out : static_cast<int32_t *>(c->pyr_sh.p);
-    double *pos = static_cast<double *>(c->pyr_pos.p);
-    int32_t *peak = static_cast<int32_t *>(c->pyr_peak.p);
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    // the coarsest level's displacement d_{L-1} and positions p_{L-1} (for L = 1: shift_out = shift)
-    HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, d_shift, nullptr, R, levels - 1, true, sh, pos, s));
-    for (int l = levels - 1; l >= 0; --l) {
-        mimc3::MatchU8Args u = u8_args(c, l ? pos : d_xyuvav, l ? 2 : 6, l ? 0 : 2, N, l ? 0 : off_u, l ? 0 : off_v, ocw, swap, d_out);
-        u.full_shift = sh; u.full_R = R;
-        if (l == 0) {
-            u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
-            u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
-        } else {                        // level l: its planes, tables and geometry, and the arg-max cells for the step to level l - 1
-            const mimc3_ctx::PyrLevel &d = c->pyr[l - 1];
-            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
-            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
-            u.sat0 = d.sat0.p; u.sat1 = d.sat1.p; u.sat_ws = mimc3::sat_pitch(d.Wp);
-            u.full_peak = peak;
-        }
-        HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
-        u.mx_flags = static_cast<uint8_t *>(ml.p);
-        const hipError_t e = mimc3::launch_match_full_mx(u, s);
-        if (e != hipSuccess) return mimc3::hip_fail(e, "pyramid-level search launch");
-        if (l) HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, nullptr, peak, R, l - 1, false, sh, pos, s));
-    }
-    c->last_path = 6;
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
+    RC_TRY(pyramid_check(c, ocw, R, levels, "mimc3_match_ncc_pyramid_dev", false));
+    return pyramid_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, levels, 0, swap, d_out, nullptr, d_shift_out, stream);
 }
 
-extern "C" int mimc3_match_ncc_pyramid(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                       int32_t ocw, int32_t R, int32_t levels, int32_t swap, float *out, int32_t *shift_out)
+extern "C" int mimc3_match_ncc_pyramid_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                              const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
+                                              float *d_out, float *d_cand, int32_t *d_shift_out, void *stream)
 {
-    if (!c || !xyuvav || !offset || !out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_pyramid: bad argument");
-    RC_TRY(pyramid_check(c, ocw, R, levels, "mimc3_match_ncc_pyramid"));
+    const char *en = "mimc3_match_ncc_pyramid_dn_dev";
+    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
+    RC_TRY(pyramid_check(c, ocw, R, levels, en, true));
+    return pyramid_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, levels, npeaks, swap, d_out, d_cand, d_shift_out, stream);
+}
+
+// the host entry of both pyramid searches: the checks, the uploads, the device entry and the copies back (dn: mimc3_match_ncc_pyramid_dn)
+static int pyramid_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
+                        int32_t levels, int32_t npeaks, int32_t swap, float *out, float *cand, int32_t *shift_out, bool dn, const char *entry)
+{
+    const std::string en(entry);
+    if (!c || !xyuvav || !offset || !out || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
+    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": cand goes with npeaks > 0");
+    RC_TRY(pyramid_check(c, ocw, R, levels, entry, dn));
     // the chip inside the level-0 image (a point whose derived search box leaves the zero border gets the all-NaN record); the starting
     // displacement within +-2^24 per axis, so that every level's shifts stay exact int32
-    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, "mimc3_match_ncc_pyramid"));
+    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
     const int64_t lim = (int64_t)1 << 24;
     for (int32_t g = 0; g < N; ++g) {
         const int64_t du = (int64_t)offset[0] + (shift ? shift[2 * (size_t)g] : 0), dv = (int64_t)offset[1] + (shift ? shift[2 * (size_t)g + 1] : 0);
         if (offset[0] < -lim || offset[0] > lim || offset[1] < -lim || offset[1] > lim || du < -lim || du > lim || dv < -lim || dv > lim)
-            return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_pyramid: grid point " + std::to_string(g) + " starting displacement beyond +-2^24");
+            return mimc3::fail(MIMC3_EINVAL, en + ": grid point " + std::to_string(g) + " starting displacement beyond +-2^24");
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
     HIP_TRY(c->out.reserve(sizeof(float) * 8 * (size_t)N));
     HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
+    if (npeaks) HIP_TRY(c->full_cand.reserve(sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
     RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
     const int32_t *d_shift = nullptr;
     if (shift) {
@@ -1081,11 +1204,58 @@ extern "C" int mimc3_match_ncc_pyramid(mimc3_ctx *c, const double *xyuvav, int32
         RC_TRY(h2d_copy(c, c->puv.p, shift, sizeof(int32_t) * 2 * (size_t)N));
         d_shift = static_cast<const int32_t *>(c->puv.p);
     }
-    const int rc = mimc3_match_ncc_pyramid_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, levels, swap,
-                                               static_cast<float *>(c->out.p), static_cast<int32_t *>(c->pyr_sh.p), c->stream);
-    if (rc) return rc;
+    RC_TRY(pyramid_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, levels, npeaks, swap,
+                       static_cast<float *>(c->out.p), npeaks ? static_cast<float *>(c->full_cand.p) : nullptr,
+                       static_cast<int32_t *>(c->pyr_sh.p), c->stream));
     if (shift_out) RC_TRY(d2h_copy(c, shift_out, c->pyr_sh.p, sizeof(int32_t) * 2 * (size_t)N));
+    if (npeaks) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
     return d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N);
+}
+
+extern "C" int mimc3_match_ncc_pyramid(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                       int32_t ocw, int32_t R, int32_t levels, int32_t swap, float *out, int32_t *shift_out)
+{
+    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, 0, swap, out, nullptr, shift_out, false, "mimc3_match_ncc_pyramid");
+}
+
+extern "C" int mimc3_match_ncc_pyramid_dn(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                          int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap, float *out, float *cand,
+                                          int32_t *shift_out)
+{
+    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, npeaks, swap, out, cand, shift_out, true, "mimc3_match_ncc_pyramid_dn");
+}
+
+// one level of the current pair as pixel values (the planes' interior; u16 planes divided by 2^shift), for tests of the reduction
+extern "C" int mimc3_ctx_get_pyramid_level(mimc3_ctx *c, int32_t level, float *out0, float *out1)
+{
+    const char *en = "mimc3_ctx_get_pyramid_level";
+    if (!c || !out0 || !out1 || level < 1 || level > 4) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, std::string(en) + ": images not set");
+    RC_TRY(full_dn_class(c, en));
+    if ((c->H >> level) < 1 || (c->W >> level) < 1) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": level " + std::to_string(level) + " is empty");
+    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(build_levels_of_class(c, level + 1));
+    const int pad = mimc3::kU8Pad;
+    const int cls = c->u8_ok ? 0 : c->u16_ok ? 1 : 2;
+    const size_t es = cls == 0 ? 1 : cls == 1 ? 2 : 4;
+    const int H = c->H >> level, W = c->W >> level;
+    std::vector<unsigned char> tmp(es * (size_t)H * W);
+    for (int k = 0; k < 2; k++) {
+        const void *pl;
+        int Wp;
+        if (cls == 0) { const mimc3_ctx::PyrLevel &d = c->pyr[level - 1]; pl = k ? d.pl1.p : d.pl0.p; Wp = d.Wp; }
+        else if (cls == 1) { const mimc3_ctx::PyrLevel16 &d = c->pyr16[level - 1]; pl = k ? d.pl1.p : d.pl0.p; Wp = d.Wp; }
+        else { const mimc3_ctx::PyrLevelF &d = c->pyrf[level - 1]; pl = k ? d.pl1.p : d.pl0.p; Wp = d.Wp; }
+        float *out = k ? out1 : out0;
+        void *dst = cls == 2 ? static_cast<void *>(out) : static_cast<void *>(tmp.data());
+        HIP_TRY(hipMemcpy2DAsync(dst, es * W, static_cast<const unsigned char *>(pl) + es * ((size_t)pad * Wp + pad), es * Wp, es * W, H,
+                                 hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const float sc = 1.0f / (float)(1 << (k ? c->shift1 : c->shift0));
+        if (cls == 0) for (size_t i = 0; i < (size_t)H * W; i++) out[i] = (float)tmp[i];
+        if (cls == 1) for (size_t i = 0; i < (size_t)H * W; i++) out[i] = (float)reinterpret_cast<const unsigned short *>(tmp.data())[i] * sc;
+    }
+    return 0;
 }
 
 // the a-priori displacement in pixels (get_uv_pivot's sign convention, :559-598), rounded to the nearest integer

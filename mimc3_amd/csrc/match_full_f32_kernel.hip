@@ -59,6 +59,14 @@ struct Cfg {
     static_assert(PB >= BW && PB % 4 == 0, "LDS layout");
 };
 
+// ... and for a level of the coarse-to-fine search (mimc3_match_ncc_pyramid_dn): the same record, plus every point's arg-max cell k
+// (or -1) in full_peak, where the next level's search centre comes from.  (A configuration of its own, as FullPeakCfg of
+// match_mx_kernel.hip, and not a fourth parameter of Cfg: the kernels without it keep their names and their code.)
+template <int OCW_, bool DIRTY_>
+struct PeakCfg : Cfg<OCW_, DIRTY_, false> {
+    static constexpr bool PEAK = true;
+};
+
 template <class C>
 __global__ __launch_bounds__(C::NT) void match_ncc_full_f32(MatchU8Args p)
 {
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(C::NT) void match_ncc_full_f32(MatchU8Args p)
 
     // ---- point header: the refusals, the class and the validity rule of the other fronts ---------------------------------------------
     auto no_record = [&](float status) __attribute__((always_inline)) {
-        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_cand_fill<C>(p, gidx, status); }
+        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_peak_store<C>(p, gidx, -1); mx::full_cand_fill<C>(p, gidx, status); }
     };
     const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;
     const int u0 = (int)row[0], v0 = (int)row[1];
@@ -220,27 +228,22 @@ static hipError_t launch_one(const MatchU8Args &a, unsigned nb, hipStream_t stre
     return hipGetLastError();
 }
 
-template <int OCW, bool MULTI>
-static hipError_t launch_ocw(const MatchU8Args &a, hipStream_t stream)
+template <class Clean, class Dirty>
+static hipError_t launch_pair(const MatchU8Args &a, hipStream_t stream)
 {
     const unsigned nb = (unsigned)((a.N + 7) & ~7);
-    const hipError_t e = launch_one<Cfg<OCW, false, MULTI>>(a, nb, stream);
+    const hipError_t e = launch_one<Clean>(a, nb, stream);
     if (e != hipSuccess) return e;
-    return launch_one<Cfg<OCW, true, MULTI>>(a, nb, stream);
+    return launch_one<Dirty>(a, nb, stream);
 }
 
-template <bool MULTI>
-static hipError_t launch_multi(const MatchU8Args &a, hipStream_t stream)
+// the record alone, with the arg-max cells (PEAK) or with the candidates (MULTI)
+template <int OCW>
+static hipError_t launch_ocw(const MatchU8Args &a, hipStream_t stream)
 {
-    switch (a.ocw) {
-    case 7: return launch_ocw<7, MULTI>(a, stream);
-    case 15: return launch_ocw<15, MULTI>(a, stream);
-    case 16: return launch_ocw<16, MULTI>(a, stream);
-    case 30: return launch_ocw<30, MULTI>(a, stream);
-    case 32: return launch_ocw<32, MULTI>(a, stream);
-    case 40: return launch_ocw<40, MULTI>(a, stream);
-    default: return hipErrorInvalidValue;
-    }
+    if (a.full_peak) return launch_pair<PeakCfg<OCW, false>, PeakCfg<OCW, true>>(a, stream);
+    if (a.full_cand) return launch_pair<Cfg<OCW, false, true>, Cfg<OCW, true, true>>(a, stream);
+    return launch_pair<Cfg<OCW, false, false>, Cfg<OCW, true, false>>(a, stream);
 }
 
 }  // namespace ff32
@@ -249,11 +252,16 @@ hipError_t launch_match_full_f32(MatchU8Args a, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
     if (!a.p0 || !a.p1 || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15 || !(a.scale0 > 0.0) || !(a.scale1 > 0.0)) return hipErrorInvalidValue;
-    if (a.full_cand) {
-        if (a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks) return hipErrorInvalidValue;
-        return ff32::launch_multi<true>(a, stream);
+    if (a.full_cand && (a.full_peak || a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks)) return hipErrorInvalidValue;
+    switch (a.ocw) {
+    case 7: return ff32::launch_ocw<7>(a, stream);
+    case 15: return ff32::launch_ocw<15>(a, stream);
+    case 16: return ff32::launch_ocw<16>(a, stream);
+    case 30: return ff32::launch_ocw<30>(a, stream);
+    case 32: return ff32::launch_ocw<32>(a, stream);
+    case 40: return ff32::launch_ocw<40>(a, stream);
+    default: return hipErrorInvalidValue;
     }
-    return ff32::launch_multi<false>(a, stream);
 }
 
 }  // namespace mimc3

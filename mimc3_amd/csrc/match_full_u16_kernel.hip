@@ -65,6 +65,14 @@ struct Cfg {
     static_assert(PB >= 2 * BW && PB % 8 == 0 && LDS <= 65536, "LDS layout");
 };
 
+// ... and for a level of the coarse-to-fine search (mimc3_match_ncc_pyramid_dn): the same record, plus every point's arg-max cell k
+// (or -1) in full_peak, where the next level's search centre comes from.  (A configuration of its own, as FullPeakCfg of
+// match_mx_kernel.hip, and not a fourth parameter of Cfg: the kernels without it keep their names and their code.)
+template <int OCW_, bool DIRTY_>
+struct PeakCfg : Cfg<OCW_, DIRTY_, false> {
+    static constexpr bool PEAK = true;
+};
+
 template <class C>
 __global__ __launch_bounds__(C::NT) void match_ncc_full_u16(MatchU8Args p)
 {
@@ -92,7 +100,7 @@ __global__ __launch_bounds__(C::NT) void match_ncc_full_u16(MatchU8Args p)
 
     // ---- point header: the refusals, the class and the validity rule of the 8-bit kernels' full mode ---------------------------------
     auto no_record = [&](float status) __attribute__((always_inline)) {
-        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_cand_fill<C>(p, gidx, status); }
+        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_peak_store<C>(p, gidx, -1); mx::full_cand_fill<C>(p, gidx, status); }
     };
     const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;
     const int u0 = (int)row[0], v0 = (int)row[1];
@@ -257,29 +265,22 @@ __global__ __launch_bounds__(C::NT) void match_ncc_full_u16(MatchU8Args p)
     if constexpr (C::MULTI) mx::full_tail_multi<C>(p, val, gidx, lu, lv, lane);
 }
 
-template <int OCW, bool MULTI>
-static hipError_t launch_ocw(const MatchU8Args &a, hipStream_t stream)
+template <class Clean, class Dirty>
+static hipError_t launch_pair(const MatchU8Args &a, hipStream_t stream)
 {
     const unsigned nb = (unsigned)((a.N + 7) & ~7);
-    typedef Cfg<OCW, false, MULTI> Clean;
-    typedef Cfg<OCW, true, MULTI> Dirty;
     hipLaunchKernelGGL(match_ncc_full_u16<Clean>, dim3(nb), dim3(Clean::NT), 0, stream, a);
     hipLaunchKernelGGL(match_ncc_full_u16<Dirty>, dim3(nb), dim3(Dirty::NT), 0, stream, a);
     return hipGetLastError();
 }
 
-template <bool MULTI>
-static hipError_t launch_multi(const MatchU8Args &a, hipStream_t stream)
+// the record alone, with the arg-max cells (PEAK) or with the candidates (MULTI)
+template <int OCW>
+static hipError_t launch_ocw(const MatchU8Args &a, hipStream_t stream)
 {
-    switch (a.ocw) {
-    case 7: return launch_ocw<7, MULTI>(a, stream);
-    case 15: return launch_ocw<15, MULTI>(a, stream);
-    case 16: return launch_ocw<16, MULTI>(a, stream);
-    case 30: return launch_ocw<30, MULTI>(a, stream);
-    case 32: return launch_ocw<32, MULTI>(a, stream);
-    case 40: return launch_ocw<40, MULTI>(a, stream);
-    default: return hipErrorInvalidValue;
-    }
+    if (a.full_peak) return launch_pair<PeakCfg<OCW, false>, PeakCfg<OCW, true>>(a, stream);
+    if (a.full_cand) return launch_pair<Cfg<OCW, false, true>, Cfg<OCW, true, true>>(a, stream);
+    return launch_pair<Cfg<OCW, false, false>, Cfg<OCW, true, false>>(a, stream);
 }
 
 }  // namespace fu16
@@ -288,11 +289,16 @@ hipError_t launch_match_full_u16(MatchU8Args a, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
     if (!a.p0 || !a.p1 || !a.sat0 || !a.sat1 || !a.satz0 || !a.satz1 || a.full_R < 1 || a.full_R > 15 || (a.Wp & 3)) return hipErrorInvalidValue;
-    if (a.full_cand) {
-        if (a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks) return hipErrorInvalidValue;
-        return fu16::launch_multi<true>(a, stream);
+    if (a.full_cand && (a.full_peak || a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks)) return hipErrorInvalidValue;
+    switch (a.ocw) {
+    case 7: return fu16::launch_ocw<7>(a, stream);
+    case 15: return fu16::launch_ocw<15>(a, stream);
+    case 16: return fu16::launch_ocw<16>(a, stream);
+    case 30: return fu16::launch_ocw<30>(a, stream);
+    case 32: return fu16::launch_ocw<32>(a, stream);
+    case 40: return fu16::launch_ocw<40>(a, stream);
+    default: return hipErrorInvalidValue;
     }
-    return fu16::launch_multi<false>(a, stream);
 }
 
 }  // namespace mimc3

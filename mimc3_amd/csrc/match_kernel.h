@@ -175,8 +175,8 @@ hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, hipStream_t 
 constexpr int kFullMaxPeaks = 8;
 hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream);
 // the same search on the zero-bordered u16 planes of a scaled-integer pair (match_full_u16_kernel.hip): a.p0 / a.p1 the u16 planes, a.sat0 /
-// a.sat1 their packed tables, a.satz0 / a.satz1 their null tables; a.full_shift, a.full_R, a.full_cand / a.full_npeaks and a.out as above.  Two
-// launches, the points without nulls and those with; no flags, lists or scratch
+// a.sat1 their packed tables, a.satz0 / a.satz1 their null tables; a.full_shift, a.full_R, a.full_peak, a.full_cand / a.full_npeaks and a.out as
+// above.  Two launches, the points without nulls and those with; no flags, lists or scratch
 hipError_t launch_match_full_u16(MatchU8Args a, hipStream_t stream);
 // the same search on the zero-bordered f32 planes of an integral-f32 pair (match_full_f32_kernel.hip; 16-bit DN and its filtered forms):
 // a.p0 / a.p1 the f32 planes, a.sat0 / a.sat1 their 16-byte tables (Sat2), a.scale0 / a.scale1 = 2^-s of each image (pixel * 2^s is the
@@ -188,6 +188,13 @@ static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slot
 // zero; Hd = Hs >> 1, Wd = Ws >> 1 (the destination plane pre-zeroed, border pad in both)
 hipError_t launch_pyr_reduce(const unsigned char *src, int Hs, int Ws, int Wps, unsigned char *dst, int Hd, int Wd, int Wpd, int pad,
                              hipStream_t s);
+// The same rule on the integers the other two plane types stand for (mimc3_match_ncc_pyramid_dn): a u16 plane's values q = pixel * 2^s,
+// and an f32 plane's w = pixel * 2^shift (an integer below 2^20; the level pixel is the reduced integer times 2^-shift).  The level
+// inherits the image's shift
+hipError_t launch_pyr_reduce_u16(const unsigned short *src, int Hs, int Ws, int Wps, unsigned short *dst, int Hd, int Wd, int Wpd, int pad,
+                                 hipStream_t s);
+hipError_t launch_pyr_reduce_f32(const float *src, int Hs, int Ws, int Wps, float *dst, int Hd, int Wd, int Wpd, int pad, int shift,
+                                 hipStream_t s);
 // Per point before the search of level `lnext`: its starting displacement D = (off_u, off_v) + shift[g] (shift null = 0) scaled to the
 // coarsest level (first: d = floor((D + 2^(L-2)) / 2^(L-1)), L = lnext + 1), or the step d = 2 (d_l + s) / 2 d_l from the level just
 // searched (d_l = sh[g], s its arg-max peak[g]); writes sh[g] = d, or d - (off_u, off_v) when lnext == 0, and the level's
