@@ -80,7 +80,9 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *       on the matrix cores (it does not depend on the mode);
  *   7 = the exhaustive search of mimc3_match_ncc_full_planes on a scaled-integer pair: the u16 planes' register-tiled search kernel;
  *   8 = the exhaustive search of mimc3_match_ncc_full_dn on an integral-f32 pair (16-bit DN and its filtered forms): the f32 planes'
- *       search kernel.
+ *       search kernel;
+ *   9 = the exhaustive search of mimc3_match_ncc_full_any on any other f32 pair (non-integral pixels, NaN or negative nulls), or on any
+ *       pair with its mode 1: the float search kernel on the f32 planes, without tables.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -245,7 +247,7 @@ int mimc3_match_ncc_full_planes_dev(mimc3_ctx *ctx, const double *d_xyuvav, int3
  *                      division, all correctly rounded f64 -- and not the reciprocal-square-root shortcut of the other classes,
  *                      whose guard was argued for exact inputs.  The record and the candidates come from the same code as on
  *                      every other class.
- *     anything else    (non-integral data, NaN nulls, values of 2^20 and above) MIMC3_EUNSUPPORTED.
+ *     anything else    (non-integral data, NaN nulls, values of 2^20 and above) MIMC3_EUNSUPPORTED.  (mimc3_match_ncc_full_any takes it.)
  *   Refusals: those of mimc3_match_ncc_full_planes; a chip-atlas context: MIMC3_ESTATE.  (mimc3_match_ncc_pyramid_dn is the coarse-to-fine search on these pairs.) */
 int mimc3_match_ncc_full_dn(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                             const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
@@ -255,6 +257,54 @@ int mimc3_match_ncc_full_dn(mimc3_ctx *ctx, const double *xyuvav, int32_t N, con
 int mimc3_match_ncc_full_dn_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                 const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
                                 float *d_cand, void *stream);
+
+/* ---- Exhaustive search on ANY f32 pair: non-integral pixels (SAR amplitude or sigma-0, high-pass or Wallis filtered optical pairs,
+ *      reflectance), NaN or negative nulls (GeoTIFF no-data NaN or -9999).  The arguments of mimc3_match_ncc_full_dn plus `mode` and `surf`.
+ *
+ *   mode 0   dispatch by the class of the pair the context currently matches on: 8-bit, scaled-integer and integral-f32 pairs go where
+ *            mimc3_match_ncc_full_dn sends them (mimc3_ctx_last_path 6, 7, 8), bit for bit; every other f32 pair runs the float kernel
+ *            (match_full_f32g_kernel.hip) on the zero-bordered f32 planes, without tables.  mimc3_ctx_last_path reports 9.
+ *   mode 1   the float kernel on any pair, whatever its class (tests; and the only way to the surfaces of an integer-class pair).
+ *   Any other mode: MIMC3_EINVAL.
+ *   surf     optional (NULL: none), f32 [N][(2R+1)^2]: every point's NCC surface in k order, k = (su + R)(2R + 1) + (sv + R); all NaN at
+ *            status -3 (and for a point of the _dev entry that breaks the bounds).  Only the float kernel serves it: surf != NULL on a
+ *            call the float kernel does not run is MIMC3_EINVAL.
+ *   out, cand   exactly the record and the candidates of mimc3_match_ncc_full_dn: statuses -2 / -3 / -4, the local-maximum rule, the
+ *            rank, the fit.  Refusals as there (ocw one of 7, 15, 16, 30, 32, 40; 1 <= R <= 15; npeaks 0..8 and cand NULL iff npeaks == 0;
+ *            MIMC3_EBOUNDS; a chip-atlas context: MIMC3_ESTATE).  The older entries keep refusing this class (MIMC3_EUNSUPPORTED).
+ *
+ *   The cell on float pixels is the reference's, literally (MIMC_module.c:605-644, :719-734), with its TWO null rules, which differ on NaN:
+ *     validity   counts the pixels with p < MIN_DN (MIN_DN = 1e-10, compared in double) in the chip and in the whole (2R + 2 ocw + 1)^2
+ *                box, pixels outside the image being 0; the point gets status -3 when either f32 ratio exceeds 0.8.  A NaN pixel is
+ *                NOT counted (NaN < x is false): a chip of NaN alone is valid, and has no cell (-2).
+ *     inclusion  a pixel pair enters a cell's sums when a >= MIN_DN && b >= MIN_DN.  A NaN pixel IS excluded (NaN >= x is false), as
+ *                are 0, -0.0, negatives and positives below 1e-10.  An included +Inf, or a product that overflows, goes through the
+ *                arithmetic as in the reference (the cells that contain it are not finite; no other cell sees it).
+ *     terms      n counts the included pairs; sx, sy add (double)a, (double)b; sxx, syy, sxy add (double)(float)(a a), (double)(float)(b b),
+ *                (double)(float)(a b): f32 products, widened.
+ *     finish     the reference's f64 operations one by one, correctly rounded (no reciprocal-square-root shortcut), cast to f32.
+ *   Order, and its bound.  On the integer classes every partial sum is an exact integer and any order gives the reference's bits.  Float
+ *   terms do not have that, so: each of the five sums is the f64 sum of exactly those terms in an order the kernel chooses; the order is
+ *   a function of (ocw, R, npeaks == 0) alone, so a call is deterministic run to run; and the sums are formed by ADDITIONS ONLY -- no
+ *   running sum that subtracts, no summed-area difference.  Every included term is positive (pixels >= 1e-10), so an additions-only f64
+ *   sum of m <= 6,561 terms has a relative error of at most (m - 1) 2^-53 < 7.3e-13 in ANY order: the kernel's sums and the
+ *   reference's (pixel order) differ by at most twice that, some 2^-39 -- against the 2^-24 of an f32 ulp.  Where the cell's expression
+ *   is well conditioned (a textured chip: the variances are not differences of nearly equal numbers) the f32 cell differs from the
+ *   reference's by at most 1 ulp, and on well under 1 % of the cells.  Everything after the surface -- arg-max, border test, fit, SNR,
+ *   Hessian, local maxima, rank -- is a deterministic function of the surface's f32 values.
+ *   On an integer-class pair every sum is exact in any order and the finish is the reference's: mode 1 returns the bytes of
+ *   mimc3_match_ncc_full_dn.
+ *   Out of scope here: the coarse-to-fine search (mimc3_match_ncc_pyramid_dn) on float pairs, several GPUs, MIMC3_hip_offsets on float
+ *   TIFFs, and any tuning of the float kernel beyond its first form. */
+int mimc3_match_ncc_full_any(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                             const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                             int32_t swap, int32_t mode, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
+                             float *surf /*[N][(2R+1)^2] host, or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_dn_dev; d_surf device memory or NULL.  (The first call on a pair builds
+ * its f32 planes on the context's own stream and waits for them before it enqueues on `stream`.) */
+int mimc3_match_ncc_full_any_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                 const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
+                                 float *d_cand, float *d_surf, void *stream);
 
 /* ---- Coarse-to-fine exhaustive search over an image pyramid (no reference counterpart: the reach of mimc3_match_ncc_full, +-R
  *      around uv0 + offset + shift, made about R (2^L - 1) px by searching a reduced pair first -- the offset trackers' standard).

@@ -57,6 +57,10 @@ _lib.mimc3_match_ncc_full_planes.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, 
 _lib.mimc3_match_ncc_full_planes_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  _vp, _vp, _vp]
 _lib.mimc3_match_ncc_full_dn.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp]
+_lib.mimc3_match_ncc_full_any.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p,
+                                          _vp, _vp]
+_lib.mimc3_match_ncc_full_any_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, _vp, _vp, _vp, _vp]
 _lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
@@ -545,12 +549,42 @@ class Context:
         _check(_lib.mimc3_match_ncc_full_dn_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                                 npeaks, 1 if swap else 0, d_out, d_cand or None, stream), "match_ncc_full_dn_dev")
 
-    def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None):
+    def match_ncc_full_any(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False, mode=0, surface=False):
+        """The exhaustive search on any f32 pair (mimc3_match_ncc_full_any): mode 0 sends what match_ncc_full_dn takes where that sends it,
+        bit for bit, and every other pair -- non-integral pixels, NaN or negative nulls -- through the float kernel ("f32g_full"); mode 1
+        sends any pair through the float kernel -> (float32[N][8] record, float32[npeaks][N][3] candidates or None when npeaks == 0),
+        and with surface=True (float kernel only) every point's NCC surface float32[N][(2 radius + 1)^2] in k order as a third item."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        surf = np.empty((n, (2 * int(radius) + 1) ** 2), np.float32) if surface else None
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_full_any: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_full_any(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
+                                             None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, int(mode), out,
+                                             None if cand is None else cand.ctypes.data, None if surf is None else surf.ctypes.data),
+               "match_ncc_full_any")
+        return (out, cand, surf) if surface else (out, cand)
+
+    def match_ncc_full_any_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, mode=0,
+                               d_surf=0):
+        """Device-pointer variant (enqueue only): as match_ncc_full_dn_dev; d_surf 0 = no surfaces."""
+        _check(_lib.mimc3_match_ncc_full_any_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                 npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
+               "match_ncc_full_any_dev")
+
+    def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None, any_pair=False):
         """The candidates of the exhaustive search over image variants and chip sizes -> dp float32[ndp][N][3], ndp = len(kernels) *
         len(vec_ocw) * npeaks <= 64: for each variant in order (None = the raw pair, else filter_images(kernel)) and each ocw one
         forward match_ncc_full_dn call, its candidates stacked variant-major, then ocw, then peak rank -- what
         calc_mean_var_num_dp_cluster and mimc2_postprocess read.  Every variant is filtered from fresh planes (see filter_images).
-        The pair is left unfiltered."""
+        The pair is left unfiltered.  any_pair: the calls are match_ncc_full_any's (mode 0), so a float pair goes through every variant."""
+        match = self.match_ncc_full_any if any_pair else self.match_ncc_full_dn
         kernels = tuple(kernels); vec_ocw = tuple(int(o) for o in vec_ocw); npeaks = int(npeaks)
         ndp = len(kernels) * len(vec_ocw) * npeaks
         if npeaks < 1 or ndp < 1:
@@ -564,7 +598,7 @@ class Context:
                 if k is not None:
                     self.filter_images(k)
                 for ocw in vec_ocw:
-                    blocks.append(self.match_ncc_full_dn(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
+                    blocks.append(match(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
         finally:
             self.filter_images(None)
         return np.concatenate(blocks, axis=0)
@@ -863,7 +897,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

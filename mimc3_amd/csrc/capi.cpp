@@ -91,7 +91,7 @@ struct mimc3_ctx {
     int32_t Wp = 0;
     bool u8_ok = false;                 // both images proven to be integers in [0,255]: the u8 planes are built with the classification
     int path_mode = 0;                  // 0 auto, 1 force the general f32 kernel, 2 no integer kernels, 3 no u8 kernel, 4 auto without the matrix-core kernel
-    int last_path = -1;                 // 0 general f32/f64 kernel, 1 exact u8 kernel, ... (mimc3_hip.h), 5 matrix-core u8 kernel
+    int last_path = -1;                 // 0 general f32/f64 kernel, 1 exact u8 kernel, ... (mimc3_hip.h), 5 matrix-core u8 kernel, 9 float search kernel
     DevBuf xy, puv, poff, out;          // matcher staging for the host-buffer entry point
     DevBuf pcor, pcnt, pext;            // device pivots: corridors [N] x 24 B, counts [N], extents + total (24 B)
     hipEvent_t ev_chunk[2][8] = {};     // mimc3_match_ncc_dlc_cor: "chunk uploaded + counted" / "chunk matched"
@@ -131,6 +131,7 @@ struct mimc3_ctx {
     struct PyrLevelF { DevBuf pl0, pl1, sat0, sat1; int32_t H = 0, W = 0, Wp = 0; } pyrf[4];
     DevBuf pyr_pos, pyr_peak, pyr_sh;   // per point: position on the level (f64 [N][2]), arg-max cell, search shift (the host entry's)
     DevBuf full_cand;                   // mimc3_match_ncc_full_multi's host entry: the candidates, f32 [npeaks][N][3]
+    DevBuf full_surf;                   // mimc3_match_ncc_full_any's host entry: the surfaces, f32 [N][(2R+1)^2]
 };
 
 static constexpr size_t kPinChunk = 4u << 20;
@@ -801,8 +802,13 @@ static int full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int3
 static int full_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
                        int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream);
 static int full_dn_class(mimc3_ctx *c, const std::string &en);
+static int full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
+                        int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out, float *d_cand, float *d_surf,
+                        void *stream);
+// (kind 3: mimc3_match_ncc_full_any -- any f32 pair, with `mode` and the optional surfaces `surf`)
 static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
-                     int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, int kind = 0)
+                     int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, int kind = 0,
+                     int32_t mode = 0, float *surf = nullptr)
 {
     const bool planes = kind == 1;
     const std::string en(entry);
@@ -814,6 +820,8 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     if (planes && !c->u8_ok && !c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
     if (kind == 0 && !c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
     if (kind == 2) RC_TRY(full_dn_class(c, en));
+    if (kind == 3 && mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
+    if (kind == 3 && c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
     // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
     RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
     const int64_t pad = mimc3::kU8Pad;
@@ -836,7 +844,12 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
         d_shift = static_cast<const int32_t *>(c->puv.p);
     }
     float *d_cand = multi ? static_cast<float *>(c->full_cand.p) : nullptr;
-    const int rc = kind == 2 ? full_dn_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
+    const size_t surf_bytes = sizeof(float) * (size_t)N * (size_t)((2 * R + 1) * (2 * R + 1));
+    if (kind == 3 && surf) HIP_TRY(c->full_surf.reserve(surf_bytes));
+    const int rc = kind == 3 ? full_any_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap, mode,
+                                            static_cast<float *>(c->out.p), d_cand, surf ? static_cast<float *>(c->full_surf.p) : nullptr,
+                                            c->stream)
+                   : kind == 2 ? full_dn_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
                                            static_cast<float *>(c->out.p), d_cand, c->stream)
                    : planes ? full_planes_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
                                               static_cast<float *>(c->out.p), d_cand, c->stream)
@@ -846,6 +859,7 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     if (rc) return rc;
     RC_TRY(d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N));
     if (multi) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
+    if (kind == 3 && surf) RC_TRY(d2h_copy(c, surf, c->full_surf.p, surf_bytes));
     return 0;
 }
 
@@ -963,6 +977,67 @@ extern "C" int mimc3_match_ncc_full_dn(mimc3_ctx *c, const double *xyuvav, int32
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
     if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
     return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 2);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the exhaustive search on any f32 pair (mimc3_match_ncc_full_any): mode 0 sends the classes above where mimc3_match_ncc_full_dn sends
+// them, untouched, and every other pair (non-integral pixels, NaN or negative nulls, values of 2^20 and above) through
+// match_full_f32g_kernel.hip on its f32 planes (build_f32; no tables); mode 1 sends any pair through that kernel.  Only that kernel
+// serves the surfaces
+// ---------------------------------------------------------------------------------------------
+static int full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
+                        int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out, float *d_cand, float *d_surf,
+                        void *stream)
+{
+    const std::string en("mimc3_match_ncc_full_any_dev");
+    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
+    if (mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    HIP_TRY(hipSetDevice(c->device));
+    bool general = mode == 1;
+    if (!general && !c->u8_ok && !c->u16_ok) {          // the class of an f32 pair: its planes are built on first use (drains the stream)
+        if (!c->fplanes_ok) RC_TRY(build_f32(c));
+        general = !c->f32i_ok;
+    }
+    if (!general) {
+        if (d_surf) return mimc3::fail(MIMC3_EINVAL, en + ": only the float kernel serves the surfaces (mode 1, or a pair of no integer class)");
+        return full_dn_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream);
+    }
+    // (mode 1 on an 8-bit or scaled-integer pair: build_f32 also classifies the pair as integral f32 and builds the 16-byte tables, which
+    //  this kernel never reads -- once per pair, on the path of tests and surfaces; the planes are the same ones either way)
+    if (!c->fplanes_ok) RC_TRY(build_f32(c));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
+    u.full_shift = d_shift; u.full_R = R;
+    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
+    u.p0 = static_cast<const unsigned char *>(c->fpl0.p); u.p1 = static_cast<const unsigned char *>(c->fpl1.p);
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    const hipError_t e = mimc3::launch_match_full_f32g(u, d_surf, s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "full-search general f32 kernel launch");
+    c->last_path = 9;
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                            const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                            float *d_out, float *d_cand, float *d_surf, void *stream)
+{
+    return full_any_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, d_surf, stream);
+}
+
+extern "C" int mimc3_match_ncc_full_any(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                        int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *out, float *cand,
+                                        float *surf)
+{
+    const char *en = "mimc3_match_ncc_full_any";
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
+    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 3, mode, surf);
 }
 
 // ---------------------------------------------------------------------------------------------

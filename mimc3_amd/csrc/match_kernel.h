@@ -182,6 +182,9 @@ hipError_t launch_match_full_u16(MatchU8Args a, hipStream_t stream);
 // a.p0 / a.p1 the f32 planes, a.sat0 / a.sat1 their 16-byte tables (Sat2), a.scale0 / a.scale1 = 2^-s of each image (pixel * 2^s is the
 // integer the tables sum); the rest as above.  Two launches, dynamic LDS sized by a.full_R
 hipError_t launch_match_full_f32(MatchU8Args a, hipStream_t stream);
+// the same search on the zero-bordered f32 planes of ANY f32 pair (match_full_f32g_kernel.hip; non-integral pixels, NaN and negative
+// nulls): a.p0 / a.p1 the f32 planes, no tables; surf (optional, f32 [N][(2R+1)^2]) gets every point's surface in k order.  One launch
+hipError_t launch_match_full_f32g(MatchU8Args a, float *surf, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all
