@@ -294,8 +294,8 @@ int mimc3_match_ncc_full_dn_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *   Hessian, local maxima, rank -- is a deterministic function of the surface's f32 values.
  *   On an integer-class pair every sum is exact in any order and the finish is the reference's: mode 1 returns the bytes of
  *   mimc3_match_ncc_full_dn.
- *   Out of scope here: the coarse-to-fine search (mimc3_match_ncc_pyramid_dn) on float pairs, several GPUs, MIMC3_hip_offsets on float
- *   TIFFs, and any tuning of the float kernel beyond its first form. */
+ *   (mimc3_match_ncc_pyramid_any is the coarse-to-fine search on these pairs.)
+ *   Out of scope here: several GPUs, MIMC3_hip_offsets on float TIFFs, and any tuning of the float kernel beyond its first form. */
 int mimc3_match_ncc_full_any(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                              const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
                              int32_t swap, int32_t mode, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
@@ -352,7 +352,7 @@ int mimc3_match_ncc_pyramid_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *                        record and shift_out are mimc3_match_ncc_pyramid's bit for bit.
  *       scaled-integer   u16 levels, the kernels of mimc3_match_ncc_full_planes.  mimc3_ctx_last_path reports 7.
  *       integral f32     f32 levels with 16-byte tables, the kernels of mimc3_match_ncc_full_dn.  mimc3_ctx_last_path reports 8.
- *       anything else    (non-integral data, NaN nulls, values of 2^20 and above) MIMC3_EUNSUPPORTED.
+ *       anything else    (non-integral data, NaN nulls, values of 2^20 and above) MIMC3_EUNSUPPORTED.  (mimc3_match_ncc_pyramid_any takes it.)
  *   Reduction, on integers.  With w = pixel * 2^s, s the image's shift (0 or 3: the one its class was established with), a level pixel is
  *     ((sum w + n/2) / n) / 2^s in integer arithmetic over the n non-zero pixels of its 2 x 2 block, or 0 when n = 0; H >> 1 x W >> 1 (an odd
  *     last row or column is dropped); the level inherits the shift.  Both classes are closed under the rule (a mean of values below 4096
@@ -365,8 +365,7 @@ int mimc3_match_ncc_pyramid_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *     the coarser levels never compute candidates.  A point that gets the all-NaN record gets all-NaN candidate slots.
  *   Refusals: those of mimc3_match_ncc_pyramid, with the class rule above in place of "not 8-bit"; npeaks outside 0..8, or cand NULL with
  *   npeaks > 0 / not NULL with npeaks = 0: MIMC3_EINVAL.
- *   Not covered: several devices, a candidates-over-variants driver (api.Context.full_candidates stays single-level), non-integral
- *   floats and NaN nulls. */
+ *   Not covered: several devices, a candidates-over-variants driver (api.Context.full_candidates stays single-level). */
 int mimc3_match_ncc_pyramid_dn(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                                const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t levels,
                                int32_t npeaks /*0 = record only*/, int32_t swap, float *out /*[N][8] host*/,
@@ -375,6 +374,53 @@ int mimc3_match_ncc_pyramid_dn(mimc3_ctx *ctx, const double *xyuvav, int32_t N, 
 int mimc3_match_ncc_pyramid_dn_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                    const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
                                    float *d_out, float *d_cand, int32_t *d_shift_out /*or NULL*/, void *stream);
+/* ---- Coarse-to-fine exhaustive search on ANY f32 pair: the pairs of mimc3_match_ncc_full_any (non-integral pixels, NaN or negative
+ *      nulls), which need the reach most.  The arguments of mimc3_match_ncc_pyramid_dn plus `mode` (after swap, as in
+ *      mimc3_match_ncc_full_any); there is no surf argument.
+ *
+ *   mimc3_match_ncc_pyramid's definition word for word -- levels 1..5, p_l = (u0 >> l, v0 >> l), d_{L-1} = floor((D + 2^{L-2}) / 2^{L-1}),
+ *   d_{l-1} = 2 (d_l + s) with the level's arg-max cell s (a status -4 peak counts) or 2 d_l without one, shift_out = d_0 - offset, the
+ *   +-2^24 bound on the starting displacement, the refusal of a coarsest level smaller than a chip, the all-NaN record (and all-NaN
+ *   candidate slots) for a level-0 box beyond the 256-px zero border, one stream and no host round trip, the same refusals -- with:
+ *   mode 0   on an 8-bit, scaled-integer or integral-f32 pair: exactly mimc3_match_ncc_pyramid_dn -- its levels, its kernels, its bytes;
+ *            mimc3_ctx_last_path reports 6 / 7 / 8.  On every other f32 pair: the float levels and the float kernel below;
+ *            mimc3_ctx_last_path reports 9.
+ *   mode 1   the float levels and the float kernel on any pair, whatever its class (built beside that class's own levels; both sets
+ *            stay valid until the pair changes).
+ *   Any other mode: MIMC3_EINVAL.  Class is no reason to refuse.
+ *   Float reduction.  Level l has H_{l-1} >> 1 x W_{l-1} >> 1 pixels (an odd last row or column is dropped).  A pixel p of the 2 x 2 block
+ *     is INCLUDED when (double)p >= 1e-10 -- the reference's inclusion rule: NaN, 0, -0.0, negatives and positives below MIN_DN are not.
+ *     With n the number of included pixels and S their f64 sum, added in the fixed order (2y, 2x), (2y, 2x+1), (2y+1, 2x), (2y+1, 2x+1),
+ *     the level pixel is (float)(S / (double)n), or 0.0f when n = 0.  (The order is fixed so that the reduction can be restated bit for
+ *     bit.)  An included +Inf goes through the arithmetic: the pixel is +Inf.
+ *     A block with no included pixel becomes the canonical null 0 -- an all-NaN block too.  So on a coarser level an area that is all
+ *     no-data, in whatever encoding, counts under the validity rule and is refused with status -3, where on level 0 an all-NaN chip is
+ *     "valid, no cell" (-2).  This is deliberate: a coarser level only steers the search, and a chip that is mostly no-data must not
+ *     steer it.
+ *     Level 0 is the zero-bordered f32 plane pair as it stands; the levels are reductions of the pair the context CURRENTLY matches on
+ *     (after mimc3_ctx_filter_images: filter, then reduce).  No tables are built for these levels.
+ *   Searches.  Levels L-1 .. 1 are the exhaustive search of mimc3_match_ncc_full_any in mode 1 on the level pair -- its two null rules,
+ *     its terms, its finish -- in the summation order that entry uses for npeaks == 0.  Level 0 IS mimc3_match_ncc_full_any with the
+ *     caller's mode at shift = shift_out, candidates included.  Consequence: on the float class, record and shift_out equal bit for bit
+ *     what a caller gets by chaining mimc3_match_ncc_full_any(mode 1, surf) over the same levels by hand (arg-max of surf: the lowest k
+ *     among the largest finite cells).  On an integer-class pair whose float and integer levels coincide, mode 1 returns the bytes of
+ *     mimc3_match_ncc_pyramid_dn.
+ *   Refusals: those of mimc3_match_ncc_pyramid_dn without its class rule; mode outside 0..1: MIMC3_EINVAL.
+ *   Not covered: several GPUs; a candidates-over-variants driver (api.Context.full_candidates stays single-level); MIMC3_hip_offsets
+ *   on float TIFFs. */
+int mimc3_match_ncc_pyramid_any(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                                const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t levels,
+                                int32_t npeaks /*0 = record only*/, int32_t swap, int32_t mode, float *out /*[N][8] host*/,
+                                float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/, int32_t *shift_out /*[N][2] host or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_pyramid_dn_dev.  (The first call on a pair builds its f32 planes and float
+ * levels on the context's own stream and waits for them before it enqueues on `stream`.) */
+int mimc3_match_ncc_pyramid_any_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                    const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
+                                    int32_t mode, float *d_out, float *d_cand, int32_t *d_shift_out /*or NULL*/, void *stream);
+/* FLOAT level `level` (1..4) of the pair the context currently matches on, whatever its class (mimc3_match_ncc_pyramid_any's levels), as
+ * pixel values: out0, out1 [H >> level][W >> level] host.  Builds the float levels that are missing.  A level whose image would be
+ * empty: MIMC3_EINVAL.  mimc3_ctx_get_pyramid_level keeps serving the integer levels, and keeps refusing a pair of no class. */
+int mimc3_ctx_get_pyramid_level_any(mimc3_ctx *ctx, int32_t level, float *out0, float *out1);
 /* Level `level` (1..4) of the pair the context currently matches on, as pixel values (w / 2^s): out0, out1 [H >> level][W >> level] host.
  * Builds the levels that are missing, for any of the three classes.  A pair of no class: MIMC3_EUNSUPPORTED; a level whose image would
  * be empty: MIMC3_EINVAL.  (For tests of the reduction.) */

@@ -70,7 +70,12 @@ _lib.mimc3_match_ncc_pyramid_dn.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C
                                             _i32p]
 _lib.mimc3_match_ncc_pyramid_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                 C.c_int32, _vp, _vp, _vp, _vp]
+_lib.mimc3_match_ncc_pyramid_any.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             _f32p, _vp, _i32p]
+_lib.mimc3_match_ncc_pyramid_any_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]
 _lib.mimc3_ctx_get_pyramid_level.argtypes = [_vp, C.c_int32, _f32p, _f32p]
+_lib.mimc3_ctx_get_pyramid_level_any.argtypes = [_vp, C.c_int32, _f32p, _f32p]
 _lib.mimc3_prior_shift.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, _i32p]
 _lib.mimc3_pivot_corridors.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _vp]
 _lib.mimc3_get_uv_pivot_dev.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _vp]
@@ -659,6 +664,42 @@ class Context:
         H, W = self.H, self.W
         l0 = np.empty((H >> level, W >> level), np.float32); l1 = np.empty_like(l0)
         _check(_lib.mimc3_ctx_get_pyramid_level(self._h, level, l0, l1), "get_pyramid_level")
+        return l0, l1
+
+    def match_ncc_pyramid_any(self, xyuvav, offset, ocw, radius, levels, npeaks=0, shift=None, swap=False, mode=0):
+        """Coarse-to-fine exhaustive search (mimc3_match_ncc_pyramid_any) on any f32 pair -> (float32[N][8] record, float32[npeaks][N][3]
+        candidates or None when npeaks == 0, int32[N][2] shift_out).  mode 0: match_ncc_pyramid_dn on the pairs that takes, bit for bit,
+        and float levels with the float kernel ("f32g_full") on every other pair -- non-integral pixels, NaN or negative nulls; mode 1:
+        the float levels and the float kernel on any pair.  Record and candidates are match_ncc_full_any's with shift = shift_out."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        sh_out = np.empty((n, 2), np.int32)
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_pyramid_any: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_pyramid_any(self._h, xy, n, np.ascontiguousarray(offset, np.int32), None if sh is None else sh.ctypes.data,
+                                                ocw, radius, levels, npeaks, 1 if swap else 0, int(mode), out,
+                                                None if cand is None else cand.ctypes.data, sh_out), "match_ncc_pyramid_any")
+        return out, cand, sh_out
+
+    def match_ncc_pyramid_any_dev(self, d_xyuvav, n, offset, ocw, radius, levels, npeaks, d_out, d_cand=0, d_shift=0, d_shift_out=0, stream=0,
+                                  swap=False, mode=0):
+        """Device-pointer variant (enqueue only): as match_ncc_pyramid_dn_dev, plus mode."""
+        _check(_lib.mimc3_match_ncc_pyramid_any_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius, levels,
+                                                    npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_shift_out or None, stream),
+               "match_ncc_pyramid_any_dev")
+
+    def get_pyramid_level_any(self, level):
+        """FLOAT level `level` (1..4) of the pair currently matched on, whatever its class (match_ncc_pyramid_any's levels: the mean of
+        each 2 x 2 block's pixels >= 1e-10) -> (float32[H >> level][W >> level],) * 2."""
+        H, W = self.H, self.W
+        l0 = np.empty((H >> level, W >> level), np.float32); l1 = np.empty_like(l0)
+        _check(_lib.mimc3_ctx_get_pyramid_level_any(self._h, level, l0, l1), "get_pyramid_level_any")
         return l0, l1
 
     # -- QM -----------------------------------------------------------------------------------

@@ -129,6 +129,11 @@ struct mimc3_ctx {
     // f32 planes with 16-byte tables (an integral-f32 pair).  A pair has one class, so pyr_levels counts the levels of whichever set is its
     struct PyrLevel16 { DevBuf pl0, pl1, sat0, sat1, sz0, sz1; int32_t H = 0, W = 0, Wp = 0; } pyr16[4];
     struct PyrLevelF { DevBuf pl0, pl1, sat0, sat1; int32_t H = 0, W = 0, Wp = 0; } pyrf[4];
+    // mimc3_match_ncc_pyramid_any: float levels 1..pyrg_levels of the f32 planes (build_f32), planes alone -- the float kernel reads no
+    // tables.  A set and a counter of their own: mode 1 on an integer-class pair builds them beside that class's levels, and both stay
+    // valid until the pair changes
+    struct PyrLevelG { DevBuf pl0, pl1; int32_t H = 0, W = 0, Wp = 0; } pyrg[4];
+    int pyrg_levels = 0;
     DevBuf pyr_pos, pyr_peak, pyr_sh;   // per point: position on the level (f64 [N][2]), arg-max cell, search shift (the host entry's)
     DevBuf full_cand;                   // mimc3_match_ncc_full_multi's host entry: the candidates, f32 [npeaks][N][3]
     DevBuf full_surf;                   // mimc3_match_ncc_full_any's host entry: the surfaces, f32 [N][(2R+1)^2]
@@ -412,7 +417,7 @@ static int prepare_pair(mimc3_ctx *c, bool planes_built = false)
 {
     c->u8_ok = c->u16_ok = c->u8o_ok = false;
     c->hpl_valid = c->sat_u8_ok = c->sat_u16_ok = c->fplanes_ok = false;
-    c->pyr_levels = 0;
+    c->pyr_levels = c->pyrg_levels = 0;
     c->shift0 = c->shift1 = 0;
     const int pad = mimc3::kU8Pad;
     c->Wp = (c->W + 2 * pad + 3) & ~3;
@@ -483,7 +488,7 @@ extern "C" int mimc3_ctx_set_images_u8(mimc3_ctx *c, const uint8_t *i0, const ui
     RC_TRY(h2d_copy(c, r1, i1, npx));
     const int pad = mimc3::kU8Pad;
     c->H = H; c->W = W; c->filt_live = false;
-    c->pyr_levels = 0;                   // (level 0 is overwritten below, before prepare_pair)
+    c->pyr_levels = c->pyrg_levels = 0;  // (level 0 is overwritten below, before prepare_pair)
     c->Wp = (W + 2 * pad + 3) & ~3;
     const size_t pbytes = (size_t)(H + 2 * pad) * c->Wp;
     HIP_TRY(c->pl0.reserve(pbytes));
@@ -1141,6 +1146,31 @@ static int build_levelsf(mimc3_ctx *c, int L)
     return 0;
 }
 
+// ... and for any pair (mimc3_match_ncc_pyramid_any): float levels pyrg_levels + 1 .. L - 1 of the f32 planes, each the f64 mean of the
+// block's included pixels (pyr_reduce_f32g_kernel); no tables.
+static int build_levelsg(mimc3_ctx *c, int L)
+{
+    const int pad = mimc3::kU8Pad;
+    if (!c->fplanes_ok) RC_TRY(build_f32(c));
+    for (int l = c->pyrg_levels + 1; l < L; ++l) {
+        mimc3_ctx::PyrLevelG &d = c->pyrg[l - 1];
+        const bool top = l == 1;
+        const void *s0 = top ? c->fpl0.p : c->pyrg[l - 2].pl0.p, *s1 = top ? c->fpl1.p : c->pyrg[l - 2].pl1.p;
+        const int Hs = top ? c->H : c->pyrg[l - 2].H, Ws = top ? c->W : c->pyrg[l - 2].W, Wps = top ? c->Wp : c->pyrg[l - 2].Wp;
+        d.H = Hs >> 1; d.W = Ws >> 1; d.Wp = (d.W + 2 * pad + 3) & ~3;
+        const size_t bytes = sizeof(float) * (size_t)(d.H + 2 * pad) * d.Wp;
+        HIP_TRY(d.pl0.reserve(bytes));
+        HIP_TRY(d.pl1.reserve(bytes));
+        HIP_TRY(hipMemsetAsync(d.pl0.p, 0, bytes, c->stream));
+        HIP_TRY(hipMemsetAsync(d.pl1.p, 0, bytes, c->stream));
+        HIP_TRY(mimc3::launch_pyr_reduce_f32g(static_cast<const float *>(s0), Hs, Ws, Wps, static_cast<float *>(d.pl0.p), d.H, d.W, d.Wp, pad, c->stream));
+        HIP_TRY(mimc3::launch_pyr_reduce_f32g(static_cast<const float *>(s1), Hs, Ws, Wps, static_cast<float *>(d.pl1.p), d.H, d.W, d.Wp, pad, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (L - 1 > c->pyrg_levels) c->pyrg_levels = L - 1;
+    return 0;
+}
+
 // levels 1 .. L - 1 of the current pair, whatever its class (which full_dn_class has settled), and the level-0 set they start from
 static int build_levels_of_class(mimc3_ctx *c, int L)
 {
@@ -1155,9 +1185,10 @@ static int build_levels_of_class(mimc3_ctx *c, int L)
     return c->pyr_levels < L - 1 ? build_levelsf(c, L) : 0;
 }
 
-// the refusals the pyramid entries make before anything runs (those of the exhaustive search, levels, the coarsest level's size); dn: the
-// classes of mimc3_match_ncc_full_dn (an integral-f32 pair's planes are built here), else 8-bit alone
-static int pyramid_check(mimc3_ctx *c, int32_t ocw, int32_t R, int32_t levels, const char *entry, bool dn)
+// the refusals the pyramid entries make before anything runs (those of the exhaustive search, levels, the coarsest level's size); kind 0:
+// 8-bit alone; 1: the classes of mimc3_match_ncc_full_dn (an integral-f32 pair's planes are built here); 2: any pair
+// (mimc3_match_ncc_pyramid_any: class is no reason to refuse)
+static int pyramid_check(mimc3_ctx *c, int32_t ocw, int32_t R, int32_t levels, const char *entry, int kind)
 {
     const std::string e(entry);
     if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, e + ": ocw must be one of 7, 15, 16, 30, 32, 40");
@@ -1165,23 +1196,28 @@ static int pyramid_check(mimc3_ctx *c, int32_t ocw, int32_t R, int32_t levels, c
     if (levels < 1 || levels > 5) return mimc3::fail(MIMC3_EINVAL, e + ": levels must be in 1..5");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, e + ": images not set");
     if (c->child) return mimc3::fail(MIMC3_ESTATE, e + ": not on a chip-atlas context");
-    if (dn) RC_TRY(full_dn_class(c, e));
-    else if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, e + ": the pair is not 8-bit (u8 planes only)");
+    if (kind == 1) RC_TRY(full_dn_class(c, e));
+    else if (kind == 0 && !c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, e + ": the pair is not 8-bit (u8 planes only)");
     if (std::min(c->H >> (levels - 1), c->W >> (levels - 1)) < 2 * ocw + 1)
         return mimc3::fail(MIMC3_EINVAL, e + ": level " + std::to_string(levels - 1) + " is smaller than a chip");
     return 0;
 }
 
 // The device entry of both pyramid searches, behind their checks: the levels of the pair's class, then per level the step and the class's
-// exhaustive search with the arg-max cells; level 0 is mimc3_match_ncc_full_dn_dev's launch at shift = sh (record and candidates)
+// exhaustive search with the arg-max cells; level 0 is mimc3_match_ncc_full_dn_dev's launch at shift = sh (record and candidates).
+// fmode >= 0 (mimc3_match_ncc_pyramid_any on the float levels): the float levels and the float kernel on every level, and level 0 is
+// mimc3_match_ncc_full_any_dev's launch with mode = fmode
 static int pyramid_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                       int32_t R, int32_t levels, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, int32_t *d_shift_out, void *stream)
+                       int32_t R, int32_t levels, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, int32_t *d_shift_out, void *stream,
+                       int32_t fmode = -1)
 {
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RC_TRY(build_levels_of_class(c, levels));
+    const bool general = fmode >= 0;
+    if (!general) RC_TRY(build_levels_of_class(c, levels));
+    else if (!c->fplanes_ok || c->pyrg_levels < levels - 1) RC_TRY(build_levelsg(c, levels));
     DevBuf &ml = c->mxl[0];
-    if (c->u8_ok) HIP_TRY(ml.reserve((size_t)N));
+    if (c->u8_ok && !general) HIP_TRY(ml.reserve((size_t)N));
     HIP_TRY(c->pyr_pos.reserve(sizeof(double) * 2 * (size_t)N));
     HIP_TRY(c->pyr_peak.reserve(sizeof(int32_t) * (size_t)N));
     if (!d_shift_out) HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
@@ -1196,7 +1232,12 @@ static int pyramid_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t 
         mimc3::MatchU8Args u = u8_args(c, pos, 2, 0, N, 0, 0, ocw, swap, d_out);
         u.full_shift = sh; u.full_R = R; u.full_peak = peak;
         hipError_t e;
-        if (c->u8_ok) {
+        if (general) {
+            const mimc3_ctx::PyrLevelG &d = c->pyrg[l - 1];
+            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
+            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
+            e = mimc3::launch_match_full_f32g(u, nullptr, s);
+        } else if (c->u8_ok) {
             const mimc3_ctx::PyrLevel &d = c->pyr[l - 1];
             u.Wp = d.Wp; u.H = d.H; u.W = d.W;
             u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
@@ -1222,7 +1263,8 @@ static int pyramid_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t 
         HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, nullptr, peak, R, l - 1, false, sh, pos, s));
     }
     c->timing = false;                  // (the events bracket the whole pass, not the level-0 launch)
-    const int rc = full_dn_dev(c, d_xyuvav, N, off_u, off_v, sh, ocw, R, npeaks, swap, d_out, d_cand, stream);      // sets last_path
+    const int rc = general ? full_any_dev(c, d_xyuvav, N, off_u, off_v, sh, ocw, R, npeaks, swap, fmode, d_out, d_cand, nullptr, stream)
+                           : full_dn_dev(c, d_xyuvav, N, off_u, off_v, sh, ocw, R, npeaks, swap, d_out, d_cand, stream);      // sets last_path
     c->timing = timing;
     if (rc) return rc;
     if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
@@ -1234,7 +1276,7 @@ extern "C" int mimc3_match_ncc_pyramid_dev(mimc3_ctx *c, const double *d_xyuvav,
                                            int32_t *d_shift_out, void *stream)
 {
     if (!c || !d_xyuvav || !d_out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_pyramid_dev: bad argument");
-    RC_TRY(pyramid_check(c, ocw, R, levels, "mimc3_match_ncc_pyramid_dev", false));
+    RC_TRY(pyramid_check(c, ocw, R, levels, "mimc3_match_ncc_pyramid_dev", 0));
     return pyramid_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, levels, 0, swap, d_out, nullptr, d_shift_out, stream);
 }
 
@@ -1245,19 +1287,53 @@ extern "C" int mimc3_match_ncc_pyramid_dn_dev(mimc3_ctx *c, const double *d_xyuv
     const char *en = "mimc3_match_ncc_pyramid_dn_dev";
     if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    RC_TRY(pyramid_check(c, ocw, R, levels, en, true));
+    RC_TRY(pyramid_check(c, ocw, R, levels, en, 1));
     return pyramid_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, levels, npeaks, swap, d_out, d_cand, d_shift_out, stream);
 }
 
-// the host entry of both pyramid searches: the checks, the uploads, the device entry and the copies back (dn: mimc3_match_ncc_pyramid_dn)
+// mimc3_match_ncc_pyramid_any behind pyramid_check: which levels and kernels the call runs.  fmode -1: those of the pair's integer class
+// (mode 0 on an 8-bit, scaled-integer or integral-f32 pair: mimc3_match_ncc_pyramid_dn unchanged); else the float ones, level 0 in `mode`.
+// (The class of an f32 pair needs its planes: built here on first use, which drains the stream.)
+static int pyramid_any_fmode(mimc3_ctx *c, int32_t mode, const char *entry, int32_t &fmode)
+{
+    if (mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, std::string(entry) + ": mode must be 0 or 1");
+    fmode = mode;
+    if (mode == 1) return 0;
+    if (!c->u8_ok && !c->u16_ok) {
+        HIP_TRY(hipSetDevice(c->device));
+        if (!c->fplanes_ok) RC_TRY(build_f32(c));
+        if (!c->f32i_ok) return 0;
+    }
+    fmode = -1;
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_pyramid_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                               const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
+                                               int32_t mode, float *d_out, float *d_cand, int32_t *d_shift_out, void *stream)
+{
+    const char *en = "mimc3_match_ncc_pyramid_any_dev";
+    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
+    RC_TRY(pyramid_check(c, ocw, R, levels, en, 2));
+    int32_t fmode;
+    RC_TRY(pyramid_any_fmode(c, mode, en, fmode));
+    return pyramid_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, levels, npeaks, swap, d_out, d_cand, d_shift_out, stream, fmode);
+}
+
+// the host entry of the pyramid searches: the checks, the uploads, the device entry and the copies back (kind: pyramid_check's -- 0
+// mimc3_match_ncc_pyramid, 1 mimc3_match_ncc_pyramid_dn, 2 mimc3_match_ncc_pyramid_any with its `mode`)
 static int pyramid_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
-                        int32_t levels, int32_t npeaks, int32_t swap, float *out, float *cand, int32_t *shift_out, bool dn, const char *entry)
+                        int32_t levels, int32_t npeaks, int32_t swap, float *out, float *cand, int32_t *shift_out, int kind, const char *entry,
+                        int32_t mode = 0)
 {
     const std::string en(entry);
     if (!c || !xyuvav || !offset || !out || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
     if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": cand goes with npeaks > 0");
-    RC_TRY(pyramid_check(c, ocw, R, levels, entry, dn));
+    RC_TRY(pyramid_check(c, ocw, R, levels, entry, kind));
+    int32_t fmode = -1;
+    if (kind == 2) RC_TRY(pyramid_any_fmode(c, mode, entry, fmode));
     // the chip inside the level-0 image (a point whose derived search box leaves the zero border gets the all-NaN record); the starting
     // displacement within +-2^24 per axis, so that every level's shifts stay exact int32
     RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
@@ -1281,7 +1357,7 @@ static int pyramid_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int
     }
     RC_TRY(pyramid_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, levels, npeaks, swap,
                        static_cast<float *>(c->out.p), npeaks ? static_cast<float *>(c->full_cand.p) : nullptr,
-                       static_cast<int32_t *>(c->pyr_sh.p), c->stream));
+                       static_cast<int32_t *>(c->pyr_sh.p), c->stream, fmode));
     if (shift_out) RC_TRY(d2h_copy(c, shift_out, c->pyr_sh.p, sizeof(int32_t) * 2 * (size_t)N));
     if (npeaks) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
     return d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N);
@@ -1290,14 +1366,21 @@ static int pyramid_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int
 extern "C" int mimc3_match_ncc_pyramid(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
                                        int32_t ocw, int32_t R, int32_t levels, int32_t swap, float *out, int32_t *shift_out)
 {
-    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, 0, swap, out, nullptr, shift_out, false, "mimc3_match_ncc_pyramid");
+    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, 0, swap, out, nullptr, shift_out, 0, "mimc3_match_ncc_pyramid");
 }
 
 extern "C" int mimc3_match_ncc_pyramid_dn(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
                                           int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap, float *out, float *cand,
                                           int32_t *shift_out)
 {
-    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, npeaks, swap, out, cand, shift_out, true, "mimc3_match_ncc_pyramid_dn");
+    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, npeaks, swap, out, cand, shift_out, 1, "mimc3_match_ncc_pyramid_dn");
+}
+
+extern "C" int mimc3_match_ncc_pyramid_any(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                           int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap, int32_t mode, float *out,
+                                           float *cand, int32_t *shift_out)
+{
+    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, npeaks, swap, out, cand, shift_out, 2, "mimc3_match_ncc_pyramid_any", mode);
 }
 
 // one level of the current pair as pixel values (the planes' interior; u16 planes divided by 2^shift), for tests of the reduction
@@ -1330,6 +1413,27 @@ extern "C" int mimc3_ctx_get_pyramid_level(mimc3_ctx *c, int32_t level, float *o
         if (cls == 0) for (size_t i = 0; i < (size_t)H * W; i++) out[i] = (float)tmp[i];
         if (cls == 1) for (size_t i = 0; i < (size_t)H * W; i++) out[i] = (float)reinterpret_cast<const unsigned short *>(tmp.data())[i] * sc;
     }
+    return 0;
+}
+
+// one FLOAT level of the current pair, whatever its class (mimc3_match_ncc_pyramid_any's levels), for tests of the reduction
+extern "C" int mimc3_ctx_get_pyramid_level_any(mimc3_ctx *c, int32_t level, float *out0, float *out1)
+{
+    const char *en = "mimc3_ctx_get_pyramid_level_any";
+    if (!c || !out0 || !out1 || level < 1 || level > 4) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, std::string(en) + ": images not set");
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, std::string(en) + ": not on a chip-atlas context");
+    if ((c->H >> level) < 1 || (c->W >> level) < 1) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": level " + std::to_string(level) + " is empty");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->fplanes_ok || c->pyrg_levels < level) RC_TRY(build_levelsg(c, level + 1));
+    const int pad = mimc3::kU8Pad;
+    const mimc3_ctx::PyrLevelG &d = c->pyrg[level - 1];
+    for (int k = 0; k < 2; k++) {
+        const float *pl = static_cast<const float *>(k ? d.pl1.p : d.pl0.p);
+        HIP_TRY(hipMemcpy2DAsync(k ? out1 : out0, sizeof(float) * d.W, pl + (size_t)pad * d.Wp + pad, sizeof(float) * d.Wp, sizeof(float) * d.W, d.H,
+                                 hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -59,6 +59,15 @@ struct Cfg {
     static_assert(CWP - CW == 1 || CWP - CW == 3, "the edge pixels CW .. CW + 2 sit in the last chunk and the one read ahead");
 };
 
+// The record-only form that also leaves the arg-max cell (or -1) in full_peak, where the next level's search centre comes from
+// (mimc3_match_ncc_pyramid_any).  A configuration of its own, as PeakCfg of match_full_f32_kernel.hip, not a third parameter of Cfg: the
+// existing instantiations keep their names.  It shares every statement of the accumulation with Cfg<OCW, false>: the same sums in the
+// same order, so the same surface bits.
+template <int OCW_>
+struct PeakCfg : Cfg<OCW_, false> {
+    static constexpr bool PEAK = true;
+};
+
 constexpr double kMinDn = 1e-10;        // MIN_DN (MIMC_module.c:21), compared in double as there
 
 template <class C>
@@ -84,7 +93,7 @@ __global__ __launch_bounds__(C::NT) void match_ncc_full_f32g(MatchU8Args p, floa
     float *sf = surf ? surf + (size_t)gidx * (size_t)NC : nullptr;
 
     auto no_record = [&](float status) __attribute__((always_inline)) {
-        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_cand_fill<C>(p, gidx, status); }
+        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_peak_store<C>(p, gidx, -1); mx::full_cand_fill<C>(p, gidx, status); }
         if (sf) for (int k = tid; k < NC; k += NT) sf[k] = __builtin_nanf("");
     };
     const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;
@@ -287,6 +296,7 @@ static hipError_t launch_one(const MatchU8Args &a, float *surf, hipStream_t stre
 template <int OCW>
 static hipError_t launch_ocw(const MatchU8Args &a, float *surf, hipStream_t stream)
 {
+    if (a.full_peak) return launch_one<PeakCfg<OCW>>(a, surf, stream);
     if (a.full_cand) return launch_one<Cfg<OCW, true>>(a, surf, stream);
     return launch_one<Cfg<OCW, false>>(a, surf, stream);
 }
@@ -296,7 +306,8 @@ static hipError_t launch_ocw(const MatchU8Args &a, float *surf, hipStream_t stre
 hipError_t launch_match_full_f32g(MatchU8Args a, float *surf, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
-    if (!a.p0 || !a.p1 || a.full_R < 1 || a.full_R > 15 || a.full_peak) return hipErrorInvalidValue;
+    if (!a.p0 || !a.p1 || a.full_R < 1 || a.full_R > 15) return hipErrorInvalidValue;
+    if (a.full_peak && (a.full_cand || surf)) return hipErrorInvalidValue;
     if (a.full_cand && (a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks)) return hipErrorInvalidValue;
     switch (a.ocw) {
     case 7: return fg32::launch_ocw<7>(a, surf, stream);

@@ -183,7 +183,8 @@ hipError_t launch_match_full_u16(MatchU8Args a, hipStream_t stream);
 // integer the tables sum); the rest as above.  Two launches, dynamic LDS sized by a.full_R
 hipError_t launch_match_full_f32(MatchU8Args a, hipStream_t stream);
 // the same search on the zero-bordered f32 planes of ANY f32 pair (match_full_f32g_kernel.hip; non-integral pixels, NaN and negative
-// nulls): a.p0 / a.p1 the f32 planes, no tables; surf (optional, f32 [N][(2R+1)^2]) gets every point's surface in k order.  One launch
+// nulls): a.p0 / a.p1 the f32 planes, no tables; surf (optional, f32 [N][(2R+1)^2]) gets every point's surface in k order; a.full_peak
+// (optional; not together with full_cand or surf) the arg-max cells, summed in the order of the record-only form.  One launch
 hipError_t launch_match_full_f32g(MatchU8Args a, float *surf, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
@@ -198,6 +199,9 @@ hipError_t launch_pyr_reduce_u16(const unsigned short *src, int Hs, int Ws, int 
                                  hipStream_t s);
 hipError_t launch_pyr_reduce_f32(const float *src, int Hs, int Ws, int Wps, float *dst, int Hd, int Wd, int Wpd, int pad, int shift,
                                  hipStream_t s);
+// ... and on the f32 plane of any float pair (mimc3_match_ncc_pyramid_any): the f64 mean, rounded to f32, of the block's pixels with
+// (double)p >= 1e-10 added in row-major order, 0 when there is none; no shift, and no tables are built for these levels
+hipError_t launch_pyr_reduce_f32g(const float *src, int Hs, int Ws, int Wps, float *dst, int Hd, int Wd, int Wpd, int pad, hipStream_t s);
 // Per point before the search of level `lnext`: its starting displacement D = (off_u, off_v) + shift[g] (shift null = 0) scaled to the
 // coarsest level (first: d = floor((D + 2^(L-2)) / 2^(L-1)), L = lnext + 1), or the step d = 2 (d_l + s) / 2 d_l from the level just
 // searched (d_l = sh[g], s its arg-max peak[g]); writes sh[g] = d, or d - (off_u, off_v) when lnext == 0, and the level's

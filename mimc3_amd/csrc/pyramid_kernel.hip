@@ -1,7 +1,8 @@
 // pyramid_kernel.hip -- the small kernels of the coarse-to-fine exhaustive search (mimc3_match_ncc_pyramid / _pyramid_dn, capi.cpp): the
-// 2 x 2 null-aware reduction that makes one pyramid level of a plane (one kernel per plane type: u8, u16, f32), and the per-point step
-// that carries the search centre from one level to the next.  The searches themselves are the full mode of the matrix-core kernel
-// (match_mx_kernel.hip) and the two register-tiled full kernels (match_full_u16_kernel.hip, match_full_f32_kernel.hip).
+// 2 x 2 null-aware reduction that makes one pyramid level of a plane (one kernel per plane type: u8, u16, f32, and f32 of any float
+// pair for mimc3_match_ncc_pyramid_any), and the per-point step that carries the search centre from one level to the next.  The searches
+// themselves are the full mode of the matrix-core kernel (match_mx_kernel.hip) and the register-tiled full kernels
+// (match_full_u16_kernel.hip, match_full_f32_kernel.hip, match_full_f32g_kernel.hip).
 #include "match_kernel.h"
 
 namespace mimc3 {
@@ -68,6 +69,37 @@ __global__ __launch_bounds__(256) void pyr_reduce_f32_kernel(const float *__rest
     const uint32_t v1 = reduce4((uint32_t)(t.z * mul), (uint32_t)(t.w * mul), (uint32_t)(b.z * mul), (uint32_t)(b.w * mul));
     *reinterpret_cast<float2 *>(dst + (size_t)(y + pad) * Wpd + pad + 2 * j) =
         make_float2((float)v0 * inv, 2 * j + 1 < Wd ? (float)v1 * inv : 0.0f);
+}
+
+// ... and on the f32 plane of ANY float pair (mimc3_match_ncc_pyramid_any): the f64 mean of the block's INCLUDED pixels, those with
+// (double)p >= MIN_DN -- the reference's inclusion rule: NaN, 0, negatives and positives below 1e-10 stay out -- added in the order
+// (2y, 2x), (2y, 2x + 1), (2y + 1, 2x), (2y + 1, 2x + 1) and rounded to f32 once; the canonical null 0 when none is included (an all-NaN
+// block too).  Every term is selected, not multiplied by its mask: 0 * Inf and NaN must not reach the sum through an excluded pixel.
+__device__ __forceinline__ float reduce4g(float a, float b, float c, float d)
+{
+    const double v[4] = {(double)a, (double)b, (double)c, (double)d};
+    double s = 0.0;
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const bool in = v[i] >= 1e-10;
+        s += in ? v[i] : 0.0;                   // (s >= 0: adding 0 leaves its bits alone)
+        n += in ? 1 : 0;
+    }
+    return n ? (float)(s / (double)n) : 0.0f;
+}
+
+// lane (j, y): destination pixels x = 2 j, 2 j + 1 from 16 bytes of each of the two source rows, as pyr_reduce_f32_kernel
+__global__ __launch_bounds__(256) void pyr_reduce_f32g_kernel(const float *__restrict__ src, int Wps, float *__restrict__ dst, int Hd, int Wd,
+                                                              int Wpd, int pad)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (2 * j >= Wd || y >= Hd) return;
+    const float4 *r0 = reinterpret_cast<const float4 *>(src + (size_t)(2 * y + pad) * Wps + pad) + j;
+    const float4 *r1 = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(r0) + Wps);
+    const float4 t = r0[0], b = r1[0];
+    *reinterpret_cast<float2 *>(dst + (size_t)(y + pad) * Wpd + pad + 2 * j) =
+        make_float2(reduce4g(t.x, t.y, b.x, b.y), 2 * j + 1 < Wd ? reduce4g(t.z, t.w, b.z, b.w) : 0.0f);
 }
 
 __global__ __launch_bounds__(256) void pyr_step_kernel(const double *__restrict__ xyuvav, int N, int off_u, int off_v, const int32_t *shift,
@@ -138,6 +170,16 @@ hipError_t launch_pyr_reduce_f32(const float *src, int Hs, int Ws, int Wps, floa
     const float mul = (float)(1 << shift);
     hipLaunchKernelGGL(pyr_reduce_f32_kernel, dim3((unsigned)((nj + 255) / 256), (unsigned)Hd), dim3(256), 0, s, src, Wps, dst, Hd, Wd, Wpd, pad,
                        mul, 1.0f / mul);
+    return hipGetLastError();
+}
+
+hipError_t launch_pyr_reduce_f32g(const float *src, int Hs, int Ws, int Wps, float *dst, int Hd, int Wd, int Wpd, int pad, hipStream_t s)
+{
+    // (the last 8 bytes of a row reach 1 pixel and their source 2 pixels past the image: inside the border)
+    if (Hd < 1 || Wd < 1 || Hd > Hs / 2 || Wd > Ws / 2 || pad < 8 || (pad & 3) || (Wps & 3) || (Wpd & 3) || Wps < Ws + 2 * pad || Wpd < Wd + 2 * pad)
+        return hipErrorInvalidValue;
+    const int nj = (Wd + 1) / 2;
+    hipLaunchKernelGGL(pyr_reduce_f32g_kernel, dim3((unsigned)((nj + 255) / 256), (unsigned)Hd), dim3(256), 0, s, src, Wps, dst, Hd, Wd, Wpd, pad);
     return hipGetLastError();
 }
 
