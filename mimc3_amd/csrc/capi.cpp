@@ -662,12 +662,15 @@ static int match_dlc(mimc3_ctx *c, const double *d_xy, int32_t xy_stride, int32_
                 // corridors wider than the tile, and what the matrix-core launch appended) right behind: no memset, no host round trip
                 DevBuf &ml = c->mxl[lane], &ul = c->u8l[lane];
                 HIP_TRY(ml.reserve((size_t)N));
-                HIP_TRY(ul.reserve(sizeof(int32_t) * (mimc3::kU8ListHead + 2 * (size_t)N + mimc3::u8_classify_scratch_ints(N))));
+                HIP_TRY(ul.reserve(mimc3::u8_lists_bytes(N)));      // (the lists, the classifier's scratch, the point records)
                 int32_t *lists = static_cast<int32_t *>(ul.p);
                 u.mx_flags = static_cast<uint8_t *>(ml.p);
                 e = mimc3::launch_match_mx(u, lists, s);
                 if (e == hipSuccess) {
                     u.point_count = lists + 1; u.point_list = lists + mimc3::kU8ListHead + (size_t)N;
+                    // the rest list's records.  point_recs shares rt0's slot (match_kernel.h): every PxU8 launch over the rest list,
+                    // the many-pivot and big-chip forms included, sees a non-null rt0 that is this pointer -- only PxU8o reads rt0
+                    if (mimc3::u8_point_records_on()) u.point_recs = mimc3::u8_list_recs(lists, N) + (size_t)N;
                 } else {                // the register-tiled kernel alone, over all points
                     path = 1;
                     e = hipMemsetAsync(ovf.p, 0, sizeof(int32_t), s);
@@ -687,7 +690,7 @@ static int match_dlc(mimc3_ctx *c, const double *d_xy, int32_t xy_stride, int32_
                 u.fail_list = u.fail_count + 1;
                 if (!getenv("MIMC3_NO_RANGE_TILES")) { u.rt0 = static_cast<const uint32_t *>(c->rt0.p); u.rt1 = static_cast<const uint32_t *>(c->rt1.p); u.rt_tw = (c->Wp + 15) / 16; }
                 e = mimc3::launch_match_u8o(u, max_abs_piv_u, max_abs_piv_v, max_npiv, s);
-                u.rt0 = u.rt1 = nullptr;
+                u.rt0 = u.rt1 = nullptr;        // (the slots alias point_recs / rest_recs: cleared so that no later launch takes tiles for records)
                 u.point_count = u.fail_count; u.point_list = u.fail_list;
                 u.fail_count = nullptr; u.fail_list = nullptr;
             }

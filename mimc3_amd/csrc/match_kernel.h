@@ -92,8 +92,14 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     int32_t lds_off_chip, lds_off_lw, lds_off_lc;   // big-chip integer configs: LDS chip copy, window-null and chip-null lists
     int32_t lds_off_traj;                           // many-pivot configs: recorded climbs of the pivots beyond the first 64
     int32_t lds_off_vals, lds_nslot;                // compact configs: value slots of the two-level NCC cache
-    // PxU8o: min | max << 16 of the non-null pixels of every 16x16-pixel tile of the two u16 planes (plane coordinates), or null
-    const uint32_t *rt0, *rt1;
+    // PxU8o: min | max << 16 of the non-null pixels of every 16x16-pixel tile of the two u16 planes (plane coordinates), or null.
+    // The 8-bit pair behind u8_classify (whose kernels read no range tiles): the point records (U8PointRec below), or null = none --
+    // point_recs[i] is the header of point_list[i]; rest_recs is the array parallel to rest_list, where the matrix-core kernel puts the
+    // record of a point it appends (both writable: u8_classify fills them).  ALIASED SLOTS: a caller sets either the range tiles (PxU8o,
+    // the only policy that reads rt0 / rt1) or the records (the PxU8 launches behind u8_classify), never both, and clears them before
+    // the argument block goes to a kernel of the other kind -- a non-null rt0 in a PxU8 launch is a record pointer
+    union { const uint32_t *rt0; struct U8PointRec *point_recs; };
+    union { const uint32_t *rt1; struct U8PointRec *rest_recs; };
     int32_t rt_tw;                                  // tiles per plane row
     // packed summed-area tables of the two planes (sat_kernel.hip; policies with P::SAT), (Hp + 1) rows of sat_ws entries
     const void *sat0, *sat1;
@@ -108,6 +114,22 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     int32_t dry_run;                // launcher only: compute the LDS carve and return hipSuccess / hipErrorInvalidValue (does not fit
                                     // 160 KB) without launching -- the C ABI asks this before it commits to a kernel policy
 };
+
+// What u8_classify has read and derived of a point to class it, kept for the two matcher kernels: one record per list position, so that
+// a workgroup's header is ONE load behind the list length (16 lanes, a dword each, fields by readlane) instead of the chain list entry ->
+// point row and pivot range -> last pivot -> table queries.  Everything in it is independent of the kernels' template parameters.
+struct alignas(64) U8PointRec {
+    int32_t g;                      // the point
+    int32_t u0, v0;                 // its chip centre (image pixels)
+    int32_t lu, lv;                 // its last pivot
+    int32_t npiv;
+    int64_t pbeg;                   // piv_off[g]
+    uint32_t tile;                  // tx0 | ty0 << 10 | fits << 20 (mx_tile_fit of the DLC tile, origin 1) | the chip's corner pixel << 24 (clean points)
+    int32_t win_nulls;              // nulls of the window's written area
+    unsigned long long chipQ;       // the chip's packed table query (sum, sum of squares, nulls)
+    unsigned long long colQ, rowQ;  // clean points only: the queries of the chip's last column and last row (the matrix-core kernel's closed-form T4 terms)
+};
+static_assert(sizeof(U8PointRec) == 64, "U8PointRec: one 64-byte line, sixteen dwords");
 
 // ---- what the matrix-core DLC kernel takes: shared by its header and by u8_classify, so that the two cannot drift apart ----------
 // The 32 x 32 cell tile of a point whose last pivot is (lu, lv) and whose compact cell grid is csx x csy (a climb touches [1, cs - 2]):
@@ -163,6 +185,12 @@ hipError_t launch_match_u8(MatchU8Args a, int max_abs_u, int max_abs_v, int max_
 bool match_mx_supported(int ocw, int max_npiv, int win_half, int max_abs_u, int max_abs_v);
 constexpr int kU8ListHead = 4;
 size_t u8_classify_scratch_ints(int N);
+// ... and with point records (U8PointRec): the bytes of `lists` with the records behind the scratch, and where they start -- [N] parallel
+// to the clean list, [N] parallel to the rest list, [N] of the classifier's staging.  launch_match_mx sets them up in its own launches when
+// u8_point_records_on(); the caller hands the rest records (u8_list_recs(lists, N) + N) to launch_match_u8 with the rest list
+size_t u8_lists_bytes(int N);
+U8PointRec *u8_list_recs(int32_t *lists, int N);
+bool u8_point_records_on();        // (tuning / A-B: MIMC3_U8_RECS=0 keeps the memory headers)
 hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream);
 // (u8_classify_kernel.hip; wn_on / gen_on: which forms for null-ridden points run behind the clean form)
 hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, hipStream_t stream);

@@ -32,6 +32,8 @@
 // in ascending point order, and this kernel's DLC launch runs over the clean list only -- a point it does not take never issues a
 // tile or chip load.  A climb that leaves the tile or outlasts the 16 recorded scans (a few dozen points per launch) is only known
 // here: such a point is appended to the rest list with one atomicAdd, and the register-tiled kernel runs over that list right behind.
+// With point records (U8PointRec, match_kernel.h; RecCfg below) the classifier also leaves, at every list position, the header it has read
+// and derived of that point: the clean form starts from that one record, and a point it appends takes its record along.
 // (The exhaustive search classifies in the clean form's header and hands on through the class byte alone: every one of its points
 // stays on this kernel's forms, which run behind in flag mode.)
 #include <hip/hip_runtime.h>
@@ -106,6 +108,14 @@ struct Cfg {
     static constexpr bool FULL = false;                 // the DLC matcher (true: FullCfg, the exhaustive search)
     static constexpr bool PEAK = false;                 // full mode: also write the arg-max cell to full_peak (FullPeakCfg)
     static constexpr bool MULTI = false;                // full mode: also write the best local maxima as candidates to full_cand (FullMultiCfg)
+    static constexpr bool REC = false;                  // the header comes from u8_classify's point record (RecCfg)
+};
+// The clean form behind u8_classify with point records (U8PointRec, match_kernel.h): workgroup b starts from the record at list position b
+// -- one load behind the list length -- instead of the list entry, the point row and pivot range, the last pivot and the table queries,
+// each of which waited for the one before.  Everything behind the header is Cfg<OCW_, false>'s
+template <int OCW_>
+struct RecCfg : Cfg<OCW_, false, false> {
+    static constexpr bool REC = true;
 };
 // Exhaustive search (mimc3_match_ncc_full): the same surface builder on the cell tile whose origin is c - R (the search centre
 // c = uv0 + offset + shift, 1 <= R <= 15: all (2R + 1)^2 cells in the tile), no never-written row / column (T4), and instead of the
@@ -253,20 +263,42 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     int gidx = blockIdx.x;
-    if (p.point_list) {                                      // list mode: the clean list of u8_classify (the launch is sized for all N points)
+    [[maybe_unused]] int rpos = 0;                           // REC: the list position, i.e. where the point's record is
+    [[maybe_unused]] uint32_t recw = 0u;                     // REC: lane k < 16 holds dword k of the record
+    auto rec = [&](int k) __attribute__((always_inline)) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)recw, k); };
+    auto rec64 = [&](int k) __attribute__((always_inline)) -> unsigned long long { return ((unsigned long long)rec(k + 1) << 32) | rec(k); };
+    if (C::REC || p.point_list) {                            // list mode: the clean list of u8_classify (the launch is sized for all N points)
         const int cnt = *p.point_count;
         if (gidx >= cnt) return;
         const int per = cnt >> 3;
         if (gidx < per * 8) gidx = (gidx & 7) * per + (gidx >> 3);              // XCD-contiguous order of the list positions
-        gidx = p.point_list[gidx];
+        if constexpr (C::REC) {
+            static_assert(sizeof(U8PointRec) == 64 && offsetof(U8PointRec, rowQ) == 56, "the dword numbers below");
+            rpos = gidx;
+            recw = reinterpret_cast<const uint32_t *>(p.point_recs + rpos)[lane & 15];
+            gidx = (int)rec(0);
+        } else gidx = p.point_list[gidx];
     } else {
         const int nb = gridDim.x, per = nb >> 3;
         if (per > 0 && gidx < per * 8) gidx = (gidx & 7) * per + (gidx >> 3);   // XCD-contiguous point order
     }
-    if (gidx >= p.N) return;
-    if (p.point_flags && p.point_flags[gidx] != (uint8_t)p.flag_value) return;      // flag mode: the points another kernel handed over
+    if (!C::REC && gidx >= p.N) return;
+    if (!C::REC && p.point_flags && p.point_flags[gidx] != (uint8_t)p.flag_value) return;      // flag mode: the points another kernel handed over
     auto hand_on = [&](uint8_t to) __attribute__((always_inline)) {
-        if (tid == 0) {
+        if constexpr (C::REC) {
+            // the point goes to the rest list with its record, which holds all the register-tiled kernel's header reads: fetched again
+            // (a few dozen points per launch) rather than carried through the kernel in a register.  Wave 0 calls this, whole
+            if (wave == 0) {
+                int slot = 0;
+                if (lane == 0) {
+                    p.mx_flags[gidx] = to;
+                    if (to == kMxRest) { slot = atomicAdd(p.rest_count, 1); p.rest_list[slot] = gidx; }
+                }
+                slot = __builtin_amdgcn_readfirstlane(slot);
+                if (to == kMxRest && lane < 16)
+                    reinterpret_cast<uint32_t *>(p.rest_recs + slot)[lane] = reinterpret_cast<const uint32_t *>(p.point_recs + rpos)[lane];
+            }
+        } else if (tid == 0) {
             p.mx_flags[gidx] = to;
             if (!C::FULL && p.mx_classified && to == kMxRest) p.rest_list[atomicAdd(p.rest_count, 1)] = gidx;
         }
@@ -277,15 +309,25 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const int Wp = p.Wp, PAD = p.pad;
 
     // ---- point header (as match_px_kernel.hip) ---------------------------------------------------------------------
-    const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;
-    const int u0 = (int)row[0], v0 = (int)row[1];
+    // (REC: u8_classify has read and derived all of it; the record's dwords by number, see U8PointRec)
+    int u0, v0;
+    if constexpr (C::REC) { u0 = (int)rec(1); v0 = (int)rec(2); }
+    else {
+        const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;
+        u0 = (int)row[0]; v0 = (int)row[1];
+    }
     // (full mode, a point that breaks the bounds mimc3_match_ncc_full refuses -- only the _dev entry can pass one: no read, all NaN)
     if (C::FULL && (u0 - OCW < 0 || u0 + OCW >= p.W || v0 - OCW < 0 || v0 + OCW >= p.H)) {
         if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); full_cand_fill<C>(p, gidx, __builtin_nanf("")); }
         return;
     }
-    const int64_t pbeg = C::FULL ? 0 : p.piv_off[gidx];
-    const int npiv = C::FULL ? 1 : (int)(p.piv_off[gidx + 1] - pbeg);
+    int64_t pbeg;
+    int npiv;
+    if constexpr (C::REC) { pbeg = (int64_t)rec64(6); npiv = (int)rec(5); }
+    else {
+        pbeg = C::FULL ? 0 : p.piv_off[gidx];
+        npiv = C::FULL ? 1 : (int)(p.piv_off[gidx + 1] - pbeg);
+    }
     const int32_t *pv_g = p.piv_uv + 2 * pbeg;
     // Everything the header needs from memory beyond (u, v) and the pivot range is issued together -- the last pivot, the twelve table
     // corners of the three chip-side queries (one per lane), the chip's corner pixel, this lane's pivot -- and only then waited for:
@@ -296,15 +338,18 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const SatT *sat_chip = reinterpret_cast<const SatT *>(p.swap ? p.sat1 : p.sat0);
     const SatT *sat_win = reinterpret_cast<const SatT *>(p.swap ? p.sat0 : p.sat1);
     // (full mode: the point's shift in place of the last pivot)
-    const int2 lastpv = C::FULL ? (p.full_shift ? *reinterpret_cast<const int2 *>(p.full_shift + 2 * (size_t)gidx) : make_int2(0, 0))
-                                : *reinterpret_cast<const int2 *>(pv_g + 2 * (npiv - 1));
+    int2 lastpv = make_int2(0, 0);
+    if constexpr (!C::REC)
+        lastpv = C::FULL ? (p.full_shift ? *reinterpret_cast<const int2 *>(p.full_shift + 2 * (size_t)gidx) : make_int2(0, 0))
+                         : *reinterpret_cast<const int2 *>(pv_g + 2 * (npiv - 1));
     SatT satv = 0;
-    {   // lane 4 q + c: corner c of query q (0: the chip, 1: its last column, 2: its last row)
+    if constexpr (!C::REC) {   // lane 4 q + c: corner c of query q (0: the chip, 1: its last column, 2: its last row)
         const int q = (lane >> 2) & 3, c = lane & 3;
         const int bx = cu0 + (q == 1 ? CW - 1 : 0), by = cv0 + (q == 2 ? CW - 1 : 0), bw = q == 1 ? 1 : CW, bh = q == 2 ? 1 : CW;
         if (lane < 12) satv = sat_chip[(size_t)(by + ((c & 2) ? bh : 0)) * p.sat_ws + bx + ((c & 1) ? bw : 0)];
     }
-    const uint32_t cornerv = chip_pl[(size_t)(cv0 + CW - 1) * Wp + cu0 + CW - 1];
+    uint32_t cornerv = 0u;
+    if constexpr (!C::REC) cornerv = chip_pl[(size_t)(cv0 + CW - 1) * Wp + cu0 + CW - 1];
     // the pivots (lane k of wave 0 = pivot k in the climbs): parked in LDS until the surface is there
     int2 pv_mine = make_int2(0, 0);
     if (!C::FULL && wave == 0 && lane < npiv && npiv <= 64) pv_mine = *reinterpret_cast<const int2 *>(pv_g + 2 * lane);
@@ -324,7 +369,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         }
     };
     chip_loads(0);
-    const int lu = __builtin_amdgcn_readfirstlane(lastpv.x), lv = __builtin_amdgcn_readfirstlane(lastpv.y);
+    const int lu = C::REC ? (int)rec(3) : __builtin_amdgcn_readfirstlane(lastpv.x), lv = C::REC ? (int)rec(4) : __builtin_amdgcn_readfirstlane(lastpv.y);
     // (full mode: the search box is the Dx2 x Dy2 window centred on c, i.e. dx2 = dy2 = R + OCW; the tile's cell s_t = s + R)
     const int dx2 = C::FULL ? p.full_R + OCW : (lu < 0 ? -lu : lu) + OCW + 2, dy2 = C::FULL ? p.full_R + OCW : (lv < 0 ? -lv : lv) + OCW + 2;
     const int Dx2 = 2 * dx2 + 1, Dy2 = 2 * dy2 + 1;
@@ -337,9 +382,12 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     // ---- what this kernel takes -----------------------------------------------------------------------------------
     // the tile: all reachable cells if they fit, else centred on the pivots' starts (a scan that leaves it hands the point on)
     int tx0, ty0;
-    const bool fits = mx_tile_fit(lu, lv, OCW, dx2, dy2, csx, csy, C::FULL ? 0 : 1, tx0, ty0);
+    bool fits;
+    if constexpr (C::REC) { const uint32_t t = rec(8); tx0 = (int)(t & 1023u); ty0 = (int)((t >> 10) & 1023u); fits = ((t >> 20) & 1u) != 0u; }
+    else fits = mx_tile_fit(lu, lv, OCW, dx2, dy2, csx, csy, C::FULL ? 0 : 1, tx0, ty0);
     // the null count of the window's written area (:869-886) and the first batch of the tile's pixels: issued now, read below
-    const int win_nulls_v = sat_nulls_u8(sat_win, p.sat_ws, wu0, wv0, C::FULL ? Dx2 : 2 * dx2, C::FULL ? Dy2 : 2 * dy2, lane);      // (exact for any window size; full mode: the whole search box)
+    int win_nulls_v = 0;
+    if constexpr (!C::REC) win_nulls_v = sat_nulls_u8(sat_win, p.sat_ws, wu0, wv0, C::FULL ? Dx2 : 2 * dx2, C::FULL ? Dy2 : 2 * dy2, lane);      // (exact for any window size; full mode: the whole search box)
     constexpr int NSEG = C::SW / 16, TTASK = C::KW * NSEG;           // (tile rows >= KW and columns >= SW are only ever weighted 0: left as they are)
     constexpr int TNIT = (TTASK + NT - 1) / NT, TKB = TNIT < 4 ? TNIT : 4;
     const int tsh = (wu0 + tx0) & 3;
@@ -366,13 +414,13 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)satv, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(satv >> 32), l);
         return ((SatT)hi << 32) | lo;
     };
-    const SatT chipQ = lane64(3) - lane64(1) - lane64(2) + lane64(0);
-    const SatT colQ = lane64(7) - lane64(5) - lane64(6) + lane64(4);
-    const SatT rowQ = lane64(11) - lane64(9) - lane64(10) + lane64(8);
-    const uint32_t corner = (uint32_t)__builtin_amdgcn_readfirstlane((int)cornerv);
+    const SatT chipQ = C::REC ? rec64(10) : lane64(3) - lane64(1) - lane64(2) + lane64(0);
+    const SatT colQ = C::REC ? rec64(12) : lane64(7) - lane64(5) - lane64(6) + lane64(4);
+    const SatT rowQ = C::REC ? rec64(14) : lane64(11) - lane64(9) - lane64(10) + lane64(8);
+    const uint32_t corner = C::REC ? rec(8) >> 24 : (uint32_t)__builtin_amdgcn_readfirstlane((int)cornerv);
 
     const int chip_nulls = (int)(chipQ >> kSatNullShift8);
-    const int win_nulls = __builtin_amdgcn_readfirstlane(win_nulls_v);
+    const int win_nulls = C::REC ? (int)rec(9) : __builtin_amdgcn_readfirstlane(win_nulls_v);
     // (behind u8_classify these two tests never fire on a listed point -- they are its own, from the same helpers; they stay as the
     //  guard of a launch whose list did not come from it.  The guard decides who computes the point, it does not protect the loads
     //  above: the last pivot was read at pv_g + 2 (npiv - 1) before it, so a point without pivots has already read 8 bytes in front
@@ -1061,6 +1109,25 @@ static hipError_t launch_form(const MatchU8Args &a, hipStream_t stream)
     }
 }
 
+static hipError_t launch_rec_form(const MatchU8Args &a, hipStream_t stream)
+{
+    switch (a.ocw) {
+    case 7: return mx::launch_one<mx::RecCfg<7>>(a, stream);
+    case 15: return mx::launch_one<mx::RecCfg<15>>(a, stream);
+    case 16: return mx::launch_one<mx::RecCfg<16>>(a, stream);
+    case 30: return mx::launch_one<mx::RecCfg<30>>(a, stream);
+    case 32: return mx::launch_one<mx::RecCfg<32>>(a, stream);
+    case 40: return mx::launch_one<mx::RecCfg<40>>(a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+bool u8_point_records_on()
+{
+    static const int on = getenv("MIMC3_U8_RECS") ? atoi(getenv("MIMC3_U8_RECS")) : 1;      // tuning / A-B: 0 = the headers read memory, as without records
+    return on != 0;
+}
+
 // u8_classify, then up to three launches: the clean form over the clean list, then the forms for the other classes in flag mode.  Points
 // none takes are on the rest list afterwards (and carry kMxRest in mx_flags).
 hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
@@ -1081,10 +1148,14 @@ hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
     a.point_flags = nullptr;
     a.point_count = lists; a.point_list = lists + kU8ListHead;
     a.rest_count = lists + 1; a.rest_list = lists + kU8ListHead + (size_t)a.N;
+    // with point records (U8PointRec): the classifier leaves every listed point's header at its list position, the clean form reads it
+    // there, and a point it hands on takes its record along to the rest list
+    a.point_recs = nullptr; a.rest_recs = nullptr;
+    if (u8_point_records_on()) { a.point_recs = u8_list_recs(lists, a.N); a.rest_recs = u8_list_recs(lists, a.N) + (size_t)a.N; }
     hipError_t e = launch_u8_classify(a, lists, stream);
     if (e == hipSuccess) e = mx::classify_stats(a, lists, stream);
-    if (e == hipSuccess) e = launch_form<false, false>(a, stream);
-    a.point_list = nullptr; a.point_count = nullptr;
+    if (e == hipSuccess) e = a.point_recs ? launch_rec_form(a, stream) : launch_form<false, false>(a, stream);
+    a.point_list = nullptr; a.point_count = nullptr; a.point_recs = nullptr;
     a.point_flags = a.mx_flags;
     if (e == hipSuccess && a.mx_wn_on) { a.flag_value = kMxWn; e = launch_form<true, false>(a, stream); }
     if (e == hipSuccess && a.mx_gen_on) { a.flag_value = kMxNulls; e = launch_form<true, true>(a, stream); }
@@ -1123,7 +1194,7 @@ hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream)
     if (a.N <= 0) return hipSuccess;
     if (!a.mx_flags || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15) return hipErrorInvalidValue;
     a.mx_wn_on = 1; a.mx_gen_on = 1; a.mx_classified = 0;
-    a.point_list = nullptr; a.point_count = nullptr; a.point_flags = nullptr;
+    a.point_list = nullptr; a.point_count = nullptr; a.point_flags = nullptr; a.point_recs = nullptr; a.rest_recs = nullptr;
     if (a.full_cand) {
         if (a.full_peak || a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks) return hipErrorInvalidValue;
         return launch_full_forms<mx::FullMultiCfg>(a, stream);

@@ -583,6 +583,7 @@ struct PxCfg {
     // their own; their speculative climbs are recorded in LDS so that the exact replay stays on the fast form.  A separate
     // instantiation: the plain configurations keep their register allocation.
     static constexpr bool MANYP = MANY_;
+    static constexpr bool REC = false;                  // the header comes from u8_classify's point record (PxRec)
     // Tail tasks without masks (sparse-correction configs): a tail dword is all chip pixels except the LAST dword of a
     // chip row, whose pad bytes carry no pixel.  If no lane owns more than one such dword, the evaluation runs every tail
     // task with a full mask and takes the pad pixels of that one dword out again (one extra dword per lane and cell)
@@ -600,6 +601,13 @@ struct PxCfg {
         return true;
     }
     static constexpr bool FULLTAIL = SPARSE && !CHIP_LDS && TT >= 4 && LASTN < P::G && one_pad_task_per_lane();   // (measured: no gain for the chip-from-LDS u16 ocw 40 form, a loss with one tail task: ocw 32)
+};
+// A configuration in list mode behind u8_classify with point records (U8PointRec, match_kernel.h): the same kernel with the header read
+// from the record at the workgroup's list position.  An instantiation of its own (launch_cfg takes it when the launch has records), so
+// that the kernels with the memory header -- u8px, flag mode, every other policy -- are the code they were
+template <class C0>
+struct PxRec : C0 {
+    static constexpr bool REC = true;
 };
 static constexpr int kLwCap = 1024;    // window-null list entries (x | y << 16); more -> the point falls back to GENERAL
 static constexpr int kLcCap = 512;     // chip-null list entries
@@ -738,15 +746,27 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
     constexpr int OCW = C::OCW, CW = C::CW, GPR = C::GPR, NT = C::NT, NW = C::NW;
 
     int gidx = blockIdx.x;
+    // point records (U8PointRec, match_kernel.h): behind u8_classify the rest list comes with every point's header at its list position
+    // -- what the classifier read and derived, and the matrix-core kernel copied for the points it appended -- and the header below is
+    // ONE load behind the list length (lane k < 16 of every wave: dword k) instead of the chain list entry -> point row and pivot range
+    // -> last pivot -> the two table queries.  The 8-bit policy in list mode only (PxRec<C>, chosen by launch_cfg)
+    constexpr bool kRec = C::REC;
+    static_assert(!kRec || (std::is_same<P, PxU8>::value && !C::MANYP), "point records: the 8-bit policy's plain forms");
+    [[maybe_unused]] uint32_t recw = 0u;
+    auto rec = [&](int k) __attribute__((always_inline)) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)recw, k); };
     // list mode: the points another kernel handed over (u8_classify's rest list, the matrix-core kernel's hand-on list, PxU8o's fail
     // list into PxU16, ...).  Every such launch is sized for all N points, and every one gets the permutation below: it is a bijection on
     // [0, 8 (cnt >> 3)), so a list in atomic-append order is merely walked in another order
-    if (p.point_list) {
+    if (kRec || p.point_list) {
         const int cnt = *p.point_count;
         if (gidx >= cnt) return;
         const int per = cnt >> 3;
         if (gidx < per * 8) gidx = (gidx & 7) * per + (gidx >> 3);              // XCD-contiguous order of the list positions
-        gidx = p.point_list[gidx];
+        if constexpr (kRec) {
+            static_assert(sizeof(U8PointRec) == 64 && offsetof(U8PointRec, chipQ) == 40, "the dword numbers below");
+            recw = reinterpret_cast<const uint32_t *>(p.point_recs + gidx)[lane & 15];
+            gidx = (int)rec(0);
+        } else gidx = p.point_list[gidx];
     } else {
         const int nb = gridDim.x, per = nb >> 3;
         if (per > 0 && gidx < per * 8) gidx = (gidx & 7) * per + (gidx >> 3);   // XCD-contiguous point order
@@ -759,14 +779,22 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
     const int Wp = p.Wp, PAD = p.pad;
 
     // ---- point header -------------------------------------------------------------------------
-    const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;   // (u, v): columns 2, 3 of an xyuvav row, or a packed [N][2] array
-    const int u0 = (int)row[0], v0 = (int)row[1];
-    const int64_t pbeg = p.piv_off[gidx];
-    const int npiv = (int)(p.piv_off[gidx + 1] - pbeg);
+    int u0, v0, npiv, lu, lv;
+    int64_t pbeg;
+    if constexpr (kRec) {           // (the record's dwords by number, see U8PointRec)
+        u0 = (int)rec(1); v0 = (int)rec(2); lu = (int)rec(3); lv = (int)rec(4); npiv = (int)rec(5);
+        pbeg = (int64_t)(((unsigned long long)rec(7) << 32) | rec(6));
+    } else {
+        const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;   // (u, v): columns 2, 3 of an xyuvav row, or a packed [N][2] array
+        u0 = (int)row[0]; v0 = (int)row[1];
+        pbeg = p.piv_off[gidx];
+        npiv = (int)(p.piv_off[gidx + 1] - pbeg);
+        const int32_t *pv_l = p.piv_uv + 2 * pbeg;
+        lu = pv_l[2 * (npiv - 1)]; lv = pv_l[2 * (npiv - 1) + 1];
+    }
     const int32_t *pv_g = p.piv_uv + 2 * pbeg;
     U8Point pt;
     {
-        const int lu = pv_g[2 * (npiv - 1)], lv = pv_g[2 * (npiv - 1) + 1];
         pt.dx2 = (lu < 0 ? -lu : lu) + OCW + 2;
         pt.dy2 = (lv < 0 ? -lv : lv) + OCW + 2;
     }
@@ -796,6 +824,13 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
         sat_chip = reinterpret_cast<const SatT *>(p.swap ? p.sat1 : p.sat0);
         sat_win = reinterpret_cast<const SatT *>(p.swap ? p.sat0 : p.sat1);
         satz_win = reinterpret_cast<const uint32_t *>(p.swap ? p.satz0 : p.satz1);
+    }
+    if constexpr (kRec && kSat) {   // both queries are the classifier's (records only come with the DLC window: no full-square search area)
+        win_nulls = (int)rec(9);
+        chipQ = (SatT)(((unsigned long long)rec(11) << 32) | rec(10));
+        chip_nulls = P::sat_nulls(chipQ);
+    }
+    if constexpr (kSat && !kRec) {
         const int wc = 2 * pt.dx2 + (full_win ? 1 : 0), wr = 2 * pt.dy2 + (full_win ? 1 : 0);          // the written area (:869-886)
         if constexpr (kSatZ) win_nulls = (int)sat_box(satz_win, p.sat_ws, wu0, wv0, wc, wr);
         else if constexpr (std::is_same<SatT, unsigned long long>::value && !P::SATZ && P::BPP == 1)
@@ -2251,6 +2286,10 @@ static void px_set_lds_attr()
 template <class C>
 static hipError_t launch_cfg(MatchU8Args a, int max_abs_u, int max_abs_v, int max_npiv, hipStream_t stream)
 {
+    if constexpr (!C::REC && std::is_same<typename C::P, PxU8>::value && !C::MANYP) {
+        // the rest list of u8_classify with its point records: the instantiation that reads its header from them
+        if (a.point_recs && a.point_list && !a.point_flags && a.win_half <= 0) return launch_cfg<PxRec<C>>(a, max_abs_u, max_abs_v, max_npiv, stream);
+    }
     const size_t off = px_layout<C>(&a, max_abs_u, max_abs_v, max_npiv);
     static const bool lds_dbg = getenv("MIMC3_LDS_DEBUG") != nullptr;
     if (lds_dbg && !a.dry_run) fprintf(stderr, "[mimc3 lds] ocw %d: %zu bytes per workgroup\n", C::OCW, off);

@@ -7,8 +7,11 @@
 // per point that has already issued its first tile and chip loads.  Two launches:
 //   u8_classify_count   the class byte of every point (this store replaces the memset of the bytes) and, per block of 256 points,
 //                       how many are clean (class 0) and how many are the register-tiled kernel's (kMxRest); zeroes the overflow counter
+//                       -- and the point's record (U8PointRec, match_kernel.h: everything read and derived here that the matcher kernels'
+//                       headers would read and derive again) into a staging array, by point index
 //   u8_classify_fill    the two index lists in ascending point order: a block sums the counts of the blocks before it (a few hundred
-//                       words), ranks its own points by ballot, and writes them; the last block writes the two list lengths
+//                       words), ranks its own points by ballot, and writes them -- the index and, moved from the staging array, the
+//                       record at the same list position; the last block writes the two list lengths
 // No same-address atomic per point (100,000 of them serialise into a millisecond) and no spinning on another block: the order inside
 // both lists is the point order, whatever the order the blocks run in.
 #include <hip/hip_runtime.h>
@@ -22,7 +25,8 @@ namespace {
 
 constexpr int kClsThreads = 256, kClsWaves = kClsThreads / 64;
 
-__device__ __forceinline__ uint8_t classify_point(const MatchU8Args &p, int g)
+// the point's class, and in `r` everything that was read and derived on the way: the header of the kernel that takes the point
+__device__ __forceinline__ uint8_t classify_point(const MatchU8Args &p, int g, U8PointRec &r)
 {
     const int OCW = p.ocw, CW = 2 * OCW + 1, PAD = p.pad;
     typedef unsigned long long SatT;
@@ -36,16 +40,36 @@ __device__ __forceinline__ uint8_t classify_point(const MatchU8Args &p, int g)
     const int u0 = (int)row[0], v0 = (int)row[1];
     int2 last = make_int2(0, 0);
     if (npiv >= 1) last = *reinterpret_cast<const int2 *>(p.piv_uv + 2 * (pbeg + npiv - 1));      // (no pivot: nothing to read the search area from)
-    const int chip_nulls = (int)(sat_box(sat_chip, p.sat_ws, u0 - OCW + PAD, v0 - OCW + PAD, CW, CW) >> kSatNullShift8);
-    if (npiv < 1 || npiv > 64) return kMxRest;
+    const int cu0 = u0 - OCW + PAD, cv0 = v0 - OCW + PAD;
+    const SatT chipQ = sat_box(sat_chip, p.sat_ws, cu0, cv0, CW, CW);
+    const int chip_nulls = (int)(chipQ >> kSatNullShift8);
     const int lu = last.x, lv = last.y;
     const int dx2 = (lu < 0 ? -lu : lu) + OCW + 2, dy2 = (lv < 0 ? -lv : lv) + OCW + 2;
     const int csx = 2 * dx2 + 1 - 2 * OCW + 1, csy = 2 * dy2 + 1 - 2 * OCW + 1;
     int tx0, ty0;
-    if (!mx_takes(npiv, mx_tile_fit(lu, lv, OCW, dx2, dy2, csx, csy, 1, tx0, ty0))) return kMxRest;
-    // the window's written area (its last row and column are never written, MIMC_module.c:869-886)
+    const bool fits = mx_tile_fit(lu, lv, OCW, dx2, dy2, csx, csy, 1, tx0, ty0);
+    // the window's written area (its last row and column are never written, MIMC_module.c:869-886): the register-tiled kernel's header
+    // wants its null count of every point, so it is no longer skipped for the points the tests above already send there
     const int win_nulls = sat_nulls_u8_thread(sat_win, p.sat_ws, u0 + p.off_u - dx2 + PAD, v0 + p.off_v - dy2 + PAD, 2 * dx2, 2 * dy2);
-    return mx_null_class(win_nulls, chip_nulls, p.mx_wn_on, p.mx_gen_on);
+    const uint8_t cls = mx_takes(npiv, fits) ? mx_null_class(win_nulls, chip_nulls, p.mx_wn_on, p.mx_gen_on) : kMxRest;
+    r.g = g; r.u0 = u0; r.v0 = v0; r.lu = lu; r.lv = lv; r.npiv = npiv; r.pbeg = pbeg;
+    r.win_nulls = win_nulls; r.chipQ = chipQ; r.colQ = 0; r.rowQ = 0;
+    uint32_t corner = 0;
+    if (cls == 0) {     // the clean form's closed-form T4 terms: the chip's last column, last row and corner pixel
+        const unsigned char *chip_pl = p.swap ? p.p1 : p.p0;
+        r.colQ = sat_box(sat_chip, p.sat_ws, cu0 + CW - 1, cv0, 1, CW);
+        r.rowQ = sat_box(sat_chip, p.sat_ws, cu0, cv0 + CW - 1, CW, 1);
+        corner = chip_pl[(size_t)(cv0 + CW - 1) * p.Wp + cu0 + CW - 1];
+    }
+    r.tile = (uint32_t)tx0 | (uint32_t)ty0 << 10 | (fits ? 1u << 20 : 0u) | corner << 24;
+    return cls;
+}
+__device__ __forceinline__ void rec_copy(U8PointRec *dst, const U8PointRec *src)
+{
+    const uint4 *s = reinterpret_cast<const uint4 *>(src);
+    uint4 *d = reinterpret_cast<uint4 *>(dst);
+    const uint4 a = s[0], b = s[1], c = s[2], e = s[3];
+    d[0] = a; d[1] = b; d[2] = c; d[3] = e;
 }
 
 // the block's number of set predicates, in every thread (wave ballots, one LDS word per wave); *before = those of the lower threads
@@ -63,12 +87,17 @@ __device__ __forceinline__ int block_rank(bool on, int *wsum, int *before)
     return total;
 }
 
-__global__ __launch_bounds__(kClsThreads) void u8_classify_count(MatchU8Args p, int32_t *blk)
+__global__ __launch_bounds__(kClsThreads) void u8_classify_count(MatchU8Args p, int32_t *blk, U8PointRec *stage)
 {
     __shared__ int wsum[kClsWaves];
     const int g = blockIdx.x * kClsThreads + threadIdx.x;
     uint8_t cls = 0xff;
-    if (g < p.N) { cls = classify_point(p, g); p.mx_flags[g] = cls; }
+    if (g < p.N) {
+        U8PointRec r;
+        cls = classify_point(p, g, r);
+        p.mx_flags[g] = cls;
+        if (stage) rec_copy(stage + g, &r);
+    }
     int before;
     const int nclean = block_rank(cls == 0, wsum, &before);
     const int nrest = block_rank(cls == kMxRest, wsum, &before);
@@ -78,7 +107,7 @@ __global__ __launch_bounds__(kClsThreads) void u8_classify_count(MatchU8Args p, 
     }
 }
 
-__global__ __launch_bounds__(kClsThreads) void u8_classify_fill(MatchU8Args p, const int32_t *blk, int32_t *lists)
+__global__ __launch_bounds__(kClsThreads) void u8_classify_fill(MatchU8Args p, const int32_t *blk, int32_t *lists, const U8PointRec *stage)
 {
     __shared__ int wsum[kClsWaves];
     __shared__ int base[2];
@@ -98,9 +127,9 @@ __global__ __launch_bounds__(kClsThreads) void u8_classify_fill(MatchU8Args p, c
     int *clean = lists + kU8ListHead, *rest = lists + kU8ListHead + (size_t)p.N;
     int r;
     const int nclean = block_rank(cls == 0, wsum, &r);
-    if (cls == 0) clean[b0 + r] = g;
+    if (cls == 0) { clean[b0 + r] = g; if (stage) rec_copy(p.point_recs + (b0 + r), stage + g); }
     const int nrest = block_rank(cls == kMxRest, wsum, &r);
-    if (cls == kMxRest) rest[b1 + r] = g;
+    if (cls == kMxRest) { rest[b1 + r] = g; if (stage) rec_copy(p.rest_recs + (b1 + r), stage + g); }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) { lists[0] = b0 + nclean; lists[1] = b1 + nrest; }
 }
 
@@ -110,16 +139,23 @@ static inline unsigned classify_blocks(int N) { return (unsigned)((N + kClsThrea
 
 size_t u8_classify_scratch_ints(int N) { return 2 * (size_t)classify_blocks(N); }
 
+// the records sit behind the lists and the classifier's scratch, on a 64-byte boundary: [N] clean, [N] rest, [N] staging (by point index)
+static inline size_t recs_offset_ints(int N) { return (kU8ListHead + 2 * (size_t)N + u8_classify_scratch_ints(N) + 15) & ~(size_t)15; }
+size_t u8_lists_bytes(int N) { return sizeof(int32_t) * recs_offset_ints(N) + 3 * (size_t)N * sizeof(U8PointRec); }
+U8PointRec *u8_list_recs(int32_t *lists, int N) { return reinterpret_cast<U8PointRec *>(lists + recs_offset_ints(N)); }
+
 hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
     if (!a.mx_flags || !a.sat0 || !a.sat1 || !a.ovf_count || !lists || !a.piv_uv || !a.piv_off) return hipErrorInvalidValue;
+    if ((a.point_recs != nullptr) != (a.rest_recs != nullptr) || (a.point_recs && !a.p0)) return hipErrorInvalidValue;
     int32_t *blk = lists + kU8ListHead + 2 * (size_t)a.N;
+    U8PointRec *stage = a.point_recs ? u8_list_recs(lists, a.N) + 2 * (size_t)a.N : nullptr;
     const unsigned nb = classify_blocks(a.N);
-    hipLaunchKernelGGL(u8_classify_count, dim3(nb), dim3(kClsThreads), 0, stream, a, blk);
+    hipLaunchKernelGGL(u8_classify_count, dim3(nb), dim3(kClsThreads), 0, stream, a, blk, stage);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(u8_classify_fill, dim3(nb), dim3(kClsThreads), 0, stream, a, static_cast<const int32_t *>(blk), lists);
+    hipLaunchKernelGGL(u8_classify_fill, dim3(nb), dim3(kClsThreads), 0, stream, a, static_cast<const int32_t *>(blk), lists, static_cast<const U8PointRec *>(stage));
     return hipGetLastError();
 }
 
