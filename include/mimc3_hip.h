@@ -306,6 +306,50 @@ int mimc3_match_ncc_full_any_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t
                                  const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
                                  float *d_cand, float *d_surf, void *stream);
 
+/* ---- Forward-backward consistency of the exhaustive search: is a peak RECIPROCAL -- does matching back from where a point landed return
+ *      to where it started?  (The back-matching test AMPCOR and IMCORR users apply after the run; the record's quality columns all
+ *      describe one surface.)  One call: the forward search, then one backward search over the record and the candidates of every point,
+ *      seeded on the device.
+ *
+ *   Forward pass   exactly mimc3_match_ncc_full_any(swap = 0, mode, surf = NULL) with the same arguments: out [N][8] and cand [npeaks][N][3]
+ *                  are that call's bytes, on every pixel class; mimc3_ctx_last_path reports the forward path.
+ *   Back-match of a forward result (du, dv) -- the record's columns 0, 1 for plane 0 of fb, candidate j's for plane 1 + j -- of grid point i:
+ *     r  = ((int)rintf(du), (int)rintf(dv))          (f32, round half to even)
+ *     m  = uv0 + offset + r                          (uv0 = ((int)xyuvav[i][2], (int)xyuvav[i][3]))
+ *     the backward search is mimc3_match_ncc_full_any with swap = 1, the point's image coordinates replaced by m, offset' = -offset,
+ *     shift' = -r, the same ocw, R and mode, npeaks = 0: the chip is cut from i1 at m, the search runs in i0 around m - offset - r = uv0.
+ *     Its record is (du_b, dv_b, ncc_b, ...).
+ *   Output fb, f32 [(1 + npeaks)][N][4], plane-major: the row is (du_b, dv_b, ncc_b, err),
+ *     err = (float)hypot((double)du + (double)du_b, (double)dv + (double)dv_b): f64, rounded once; NaN unless du_b and dv_b are finite.
+ *     A consistent match has d_b ~ -d_f: err near 0.
+ *   Statuses, in column 2, with NaN in the other three columns:
+ *     -5   the forward result has no fit (du or dv not finite: the record's status -2 / -3 / -4, an empty candidate slot, a NaN fit);
+ *          nothing is searched;
+ *     -6   the chip at m would leave the image (decided per point on the device; a fitted |du| or |dv| of 2^30 or more is this case
+ *          too, without the conversion); nothing is searched.  The backward box itself always stays inside the 256-px zero border
+ *          (it is centred on uv0, whose chip is inside the image, and R <= 15);
+ *     -2 / -3 / -4   the backward search's own statuses pass through.
+ *   With npeaks = 0 fb has one plane and cand is NULL.  Where the record has a fit, plane 1 (candidate 0) equals plane 0 bit for bit.
+ *   Consequence: du_b, dv_b, ncc_b and the statuses equal bit for bit what a caller gets from two (with candidates 1 + npeaks) ordinary
+ *   mimc3_match_ncc_full_any calls with the seed arithmetic above done on the host.  err is the device library's f64 hypot, which is
+ *   accurate to an ulp of f64 but not documented as correctly rounded: against a host libm it can differ in the f32's last bit where the
+ *   f64 value falls within an f64 ulp of an f32 rounding boundary (about one value in 2^28; exact cases -- a zero component, err = 0 --
+ *   are exact on both sides).
+ *   Refusals: those of mimc3_match_ncc_full_any (the host entry checks the FORWARD bounds only); fb NULL: MIMC3_EINVAL.
+ *   Not covered: the pyramid entries, several GPUs, api.Context.full_candidates, any use of err inside the post-matcher chain. */
+int mimc3_match_ncc_full_fb(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                            const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                            int32_t mode, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
+                            float *fb /*[(1 + npeaks)][N][4] host*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_any_dev, plus d_fb [(1 + npeaks)][N][4].  Everything -- the forward
+ * search, the seed, the backward search over (1 + npeaks) N rows, the composition -- is enqueued on `stream`, no sync.  The backward
+ * rows, their records and one reason byte per row live in scratch of the context that grows on demand; all of it is sized before the
+ * first launch, so only a call that makes it grow waits for the device, and it does so before it enqueues anything.  The caller's arrays
+ * need no alignment beyond their element's: the two elementwise kernels read and write them element by element. */
+int mimc3_match_ncc_full_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t mode, float *d_out,
+                                float *d_cand, float *d_fb, void *stream);
+
 /* ---- Coarse-to-fine exhaustive search over an image pyramid (no reference counterpart: the reach of mimc3_match_ncc_full, +-R
  *      around uv0 + offset + shift, made about R (2^L - 1) px by searching a reduced pair first -- the offset trackers' standard).
  *

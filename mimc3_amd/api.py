@@ -63,6 +63,9 @@ _lib.mimc3_match_ncc_full_any_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.
                                               C.c_int32, _vp, _vp, _vp, _vp]
 _lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
+_lib.mimc3_match_ncc_full_fb.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
+_lib.mimc3_match_ncc_full_fb_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             _vp, _vp, _vp, _vp]
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
 _lib.mimc3_match_ncc_pyramid_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
@@ -582,6 +585,36 @@ class Context:
         _check(_lib.mimc3_match_ncc_full_any_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                                  npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
                "match_ncc_full_any_dev")
+
+    def match_ncc_full_fb(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, mode=0):
+        """Forward-backward consistency of the exhaustive search (mimc3_match_ncc_full_fb): the forward pass is match_ncc_full_any(swap
+        False, mode), bit for bit; every forward result -- the record and each of the npeaks candidates -- is then matched back from
+        where it landed (chip from i1, search in i0) in one backward pass on the device -> (float32[N][8] record,
+        float32[npeaks][N][3] candidates or None when npeaks == 0, float32[1 + npeaks][N][4] fb).  An fb row is (du_b, dv_b, ncc_b, err),
+        err = |d_forward + d_backward| (near 0 for a reciprocal peak); column 2 holds a status where there is no row: -5 the forward
+        result has no fit, -6 the chip at the landing point leaves the image, -2 / -3 / -4 the backward search's own."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        fb = np.empty((1 + max(npeaks, 0), n, 4), np.float32)
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_full_fb: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_full_fb(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
+                                            None if sh is None else sh.ctypes.data, ocw, radius, npeaks, int(mode), out,
+                                            None if cand is None else cand.ctypes.data, fb.ctypes.data),
+               "match_ncc_full_fb")
+        return out, cand, fb
+
+    def match_ncc_full_fb_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_fb, d_cand=0, d_shift=0, stream=0, mode=0):
+        """Device-pointer variant (enqueue only): as match_ncc_full_any_dev, plus d_fb float32[1 + npeaks][n][4]."""
+        _check(_lib.mimc3_match_ncc_full_fb_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                npeaks, int(mode), d_out, d_cand or None, d_fb, stream),
+               "match_ncc_full_fb_dev")
 
     def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None, any_pair=False):
         """The candidates of the exhaustive search over image variants and chip sizes -> dp float32[ndp][N][3], ndp = len(kernels) *

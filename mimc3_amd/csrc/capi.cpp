@@ -21,6 +21,7 @@
 #include "n1_kernel.h"
 #include "conv2_kernel.h"
 #include "cp_kernel.h"
+#include "fb_kernel.h"
 #include <ctime>
 #include <cstdlib>
 
@@ -137,6 +138,9 @@ struct mimc3_ctx {
     DevBuf pyr_pos, pyr_peak, pyr_sh;   // per point: position on the level (f64 [N][2]), arg-max cell, search shift (the host entry's)
     DevBuf full_cand;                   // mimc3_match_ncc_full_multi's host entry: the candidates, f32 [npeaks][N][3]
     DevBuf full_surf;                   // mimc3_match_ncc_full_any's host entry: the surfaces, f32 [N][(2R+1)^2]
+    // mimc3_match_ncc_full_fb: the backward search's rows ((1 + npeaks) N of them) -- xyuvav' [rows][6], shift' [rows][2], its records
+    // [rows][8], one reason byte per row -- and the host entry's fb [rows][4]
+    DevBuf fb_xy, fb_sh, fb_rec, fb_why, fb_out;
 };
 
 static constexpr size_t kPinChunk = 4u << 20;
@@ -813,10 +817,13 @@ static int full_dn_class(mimc3_ctx *c, const std::string &en);
 static int full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
                         int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out, float *d_cand, float *d_surf,
                         void *stream);
-// (kind 3: mimc3_match_ncc_full_any -- any f32 pair, with `mode` and the optional surfaces `surf`)
+static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
+                       int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream);
+// (kind 3: mimc3_match_ncc_full_any -- any f32 pair, with `mode` and the optional surfaces `surf`;
+//  kind 4: mimc3_match_ncc_full_fb -- kind 3 forward (swap 0, no surfaces), then the back-match of every result into fb)
 static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
                      int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, int kind = 0,
-                     int32_t mode = 0, float *surf = nullptr)
+                     int32_t mode = 0, float *surf = nullptr, float *fb = nullptr)
 {
     const bool planes = kind == 1;
     const std::string en(entry);
@@ -828,8 +835,9 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     if (planes && !c->u8_ok && !c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
     if (kind == 0 && !c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
     if (kind == 2) RC_TRY(full_dn_class(c, en));
-    if (kind == 3 && mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
-    if (kind == 3 && c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    if (kind >= 3 && mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
+    if (kind >= 3 && c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    if (kind == 4 && !fb) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
     RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
     const int64_t pad = mimc3::kU8Pad;
@@ -854,7 +862,11 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     float *d_cand = multi ? static_cast<float *>(c->full_cand.p) : nullptr;
     const size_t surf_bytes = sizeof(float) * (size_t)N * (size_t)((2 * R + 1) * (2 * R + 1));
     if (kind == 3 && surf) HIP_TRY(c->full_surf.reserve(surf_bytes));
-    const int rc = kind == 3 ? full_any_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap, mode,
+    const size_t fb_bytes = sizeof(float) * 4 * (size_t)(1 + npeaks) * (size_t)N;
+    if (kind == 4) HIP_TRY(c->fb_out.reserve(fb_bytes));
+    const int rc = kind == 4 ? full_fb_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, mode,
+                                           static_cast<float *>(c->out.p), d_cand, static_cast<float *>(c->fb_out.p), c->stream)
+                   : kind == 3 ? full_any_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap, mode,
                                             static_cast<float *>(c->out.p), d_cand, surf ? static_cast<float *>(c->full_surf.p) : nullptr,
                                             c->stream)
                    : kind == 2 ? full_dn_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
@@ -868,6 +880,7 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     RC_TRY(d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N));
     if (multi) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
     if (kind == 3 && surf) RC_TRY(d2h_copy(c, surf, c->full_surf.p, surf_bytes));
+    if (kind == 4) RC_TRY(d2h_copy(c, fb, c->fb_out.p, fb_bytes));
     return 0;
 }
 
@@ -1046,6 +1059,74 @@ extern "C" int mimc3_match_ncc_full_any(mimc3_ctx *c, const double *xyuvav, int3
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
     if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
     return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 3, mode, surf);
+}
+
+// ---------------------------------------------------------------------------------------------
+// forward-backward consistency of the exhaustive search (mimc3_match_ncc_full_fb, fb_kernel.hip): the forward pass of
+// mimc3_match_ncc_full_any, then ONE backward pass (swap 1) over the record and the candidates of every point -- (1 + npeaks) N rows,
+// seeded on the device from the forward results -- and the fb rows composed from it; all on the caller's stream, no host round trip
+// ---------------------------------------------------------------------------------------------
+static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
+                       int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream)
+{
+    const std::string en("mimc3_match_ncc_full_fb_dev");
+    // mimc3_match_ncc_full_any_dev's refusals, under this entry's name and before anything is allocated
+    if (!c || !d_xyuvav || !d_out || !d_fb || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
+    if (mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    const size_t rows = (size_t)(1 + npeaks) * (size_t)N;
+    if (rows > (size_t)INT32_MAX) return mimc3::fail(MIMC3_EINVAL, en + ": (1 + npeaks) N must fit an int32");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool timing = c->timing;
+    // all scratch before anything is enqueued (a buffer that grows is freed first, and hipFree waits for the device): the backward rows,
+    // and the class bytes of the matrix-core search at the backward pass's size, which the forward pass would otherwise size for N
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->fb_xy.reserve(sizeof(double) * 6 * rows));
+    HIP_TRY(c->fb_sh.reserve(sizeof(int32_t) * 2 * rows));
+    HIP_TRY(c->fb_rec.reserve(sizeof(float) * 8 * rows));
+    HIP_TRY(c->fb_why.reserve(rows));
+    if (c->u8_ok && mode == 0) HIP_TRY(c->mxl[0].reserve(rows));
+    if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    c->timing = false;                  // (the events bracket the whole call, not its last search)
+    // the forward pass: mimc3_match_ncc_full_any_dev itself, with its refusals
+    int rc = full_any_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, 0, mode, d_out, d_cand, nullptr, stream);
+    if (rc) { c->timing = timing; return rc; }
+    const int forward_path = c->last_path;
+    double *xy2 = static_cast<double *>(c->fb_xy.p);
+    int32_t *sh2 = static_cast<int32_t *>(c->fb_sh.p);
+    float *back = static_cast<float *>(c->fb_rec.p);
+    uint8_t *why = static_cast<uint8_t *>(c->fb_why.p);
+    hipError_t e = mimc3::launch_fb_seed(d_xyuvav, N, off_u, off_v, d_out, d_cand, npeaks, ocw, c->H, c->W, xy2, sh2, why, s);
+    if (e != hipSuccess) { c->timing = timing; return mimc3::hip_fail(e, "fb seed kernel launch"); }
+    // the backward pass: the chip from i1 at m, the search in i0 around m - offset - r = uv0 (inside the zero border: R <= 15)
+    rc = full_any_dev(c, xy2, (int32_t)rows, -off_u, -off_v, sh2, ocw, R, 0, 1, mode, back, nullptr, nullptr, stream);
+    c->timing = timing;
+    c->last_path = forward_path;
+    if (rc) return rc;
+    e = mimc3::launch_fb_compose(d_out, d_cand, N, npeaks, back, why, d_fb, s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "fb compose kernel launch");
+    if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                           const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t mode, float *d_out,
+                                           float *d_cand, float *d_fb, void *stream)
+{
+    return full_fb_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, mode, d_out, d_cand, d_fb, stream);
+}
+
+extern "C" int mimc3_match_ncc_full_fb(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                       int32_t ocw, int32_t R, int32_t npeaks, int32_t mode, float *out, float *cand, float *fb)
+{
+    const char *en = "mimc3_match_ncc_full_fb";
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
+    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, 0, out, cand, npeaks > 0, en, 4, mode, nullptr, fb);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // MIMC3_hip_offsets -- exhaustive-search NCC offsets with peak quality over libmimc3_hip.so (MI355X): the AMPCOR-style table that
 // MIMC_single_match.c:1-27 describes.
 //
-//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1] [filter=0]
+//     MIMC3_hip_offsets <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1] [filter=0] [fb=0]
 //
 // Inputs as for MIMC3_hip (the file names start with YYYYMMDDhhmmss; dt from the two timestamps); both images 8-bit, or both 16-bit
 // (see below).  Steps: the
@@ -24,6 +24,10 @@
 // Two 16-bit TIFFs (levels = 1 only: the pyramid stays 8-bit): the same steps and the same files, the search through
 //   mimc3_match_ncc_full_dn, which takes whatever the files hold -- 16-bit DN, or 8- and 12-bit DN in a 16-bit container -- raw or
 //   filtered.  One 8-bit and one 16-bit file are refused
+// fb = 1 (with levels = 1 only): the forward-backward consistency of every result (mimc3_match_ncc_full_fb: the same search, then every
+//   record and candidate matched back from where it landed) is also written, as fb_<t0>_<t1>.GMA (fb_<t0>_<t1>_f<k>.GMA with a filter): f32
+//   [(1 + K) N][4], plane-major, K = 0 for peaks = 1 and peaks otherwise -- row p N + i = (du_b, dv_b, ncc_b or status, err) of grid
+//   point i's record (p = 0) or candidate p - 1.  fb = 0 writes exactly the files of a run without the argument
 // Environment: MIMC3_HIP_DEVICE (default 0), MIMC3_CP_SEED (as for MIMC3_hip).
 #include <cstdint>
 #include <cstdio>
@@ -38,8 +42,8 @@
 int main(int argc, char *argv[])
 {
     printf("MIMC3_hip_offsets -- MI355X build (%s)\n", mimc3_version());
-    if (argc < 5 || argc > 10) {
-        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1] [filter=0]\n", argv[0]);
+    if (argc < 5 || argc > 11) {
+        fprintf(stderr, "usage: %s <i0.tif> <i1.tif> <xyuvav.GMA> <outdir> [ocw=15] [R=15] [levels=1] [peaks=1] [filter=0] [fb=0]\n", argv[0]);
         return 2;
     }
     const int32_t ocw = argc > 5 ? atoi(argv[5]) : 15, R = argc > 6 ? atoi(argv[6]) : 15, levels = argc > 7 ? atoi(argv[7]) : 1;
@@ -48,6 +52,12 @@ int main(int argc, char *argv[])
     if (filter < 0 || filter > 3) { fprintf(stderr, "filter must be 0 (raw), 1 (d/dx), 2 (d/dy) or 3 (Laplacian)\n"); return 2; }
     if (filter != 0 && levels != 1) {
         fprintf(stderr, "filter > 0 needs levels = 1: the coarse-to-fine search runs on the raw 8-bit pair only\n");
+        return 2;
+    }
+    const int32_t fbk = argc > 10 ? atoi(argv[10]) : 0;
+    if (fbk != 0 && fbk != 1) { fprintf(stderr, "fb must be 0 or 1\n"); return 2; }
+    if (fbk != 0 && levels != 1) {
+        fprintf(stderr, "fb = 1 needs levels = 1: the forward-backward check runs on the single-level search only\n");
         return 2;
     }
     if (peaks != 1 && levels != 1) {
@@ -111,8 +121,13 @@ int main(int argc, char *argv[])
     std::vector<float> rec(8 * (size_t)N);
     std::vector<float> cand(peaks != 1 ? 3 * (size_t)(peaks > 0 ? peaks : 0) * (size_t)N : 0);
     if (peaks != 1) printf("the %d best correlation peaks of every grid point as candidates\n", peaks);
+    const int32_t K = peaks != 1 ? (peaks > 0 ? peaks : 0) : 0;
+    std::vector<float> fb(fbk ? 4 * (size_t)(1 + K) * (size_t)N : 0);
+    if (fbk) printf("forward-backward consistency of every result\n");
     if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
-        (dn16 ? mimc3_match_ncc_full_dn(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
+        (fbk ? mimc3_match_ncc_full_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
+                                       K > 0 ? cand.data() : nullptr, fb.data())
+         : dn16 ? mimc3_match_ncc_full_dn(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
                                         peaks != 1 ? cand.data() : nullptr)
          : filter ? mimc3_match_ncc_full_planes(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
                                                 peaks != 1 ? cand.data() : nullptr)
@@ -132,6 +147,7 @@ int main(int argc, char *argv[])
     }
     bool ok = save_gma(base + ".GMA", out.data(), N, 10);
     if (peaks != 1) ok = save_gma(std::string(argv[4]) + "/candidates_" + tag + ".GMA", cand.data(), peaks * N, 3) && ok;
+    if (fbk) ok = save_gma(std::string(argv[4]) + "/fb_" + tag + ".GMA", fb.data(), (1 + K) * N, 4) && ok;
     FILE *f = fopen((base + ".txt").c_str(), "w");
     if (f) {
         fprintf(f, "# u du v dv snr h_uu h_vv h_uv   (du, dv include the control-point offset %d %d)\n", offset[0], offset[1]);
