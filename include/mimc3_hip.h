@@ -350,6 +350,62 @@ int mimc3_match_ncc_full_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
                                 const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t mode, float *d_out,
                                 float *d_cand, float *d_fb, void *stream);
 
+/* ---- NCC stacking (ensemble matching; MIMC = Multiple Image, Multiple Chip): the correlation surfaces of several pairs that see the
+ *      same motion -- a time series at equal separation, one pair at several chip sizes or after several filters -- are averaged cell by
+ *      cell, and the peak is searched ONCE, on the mean surface.  Noise peaks do not repeat from layer to layer, the true peak does.
+ *
+ *   The stack is state of one context, and it outlives the pair: mimc3_ctx_set_images* and mimc3_ctx_filter_images do not touch it.
+ *     N, R                   grid points and search radius; S = 2R + 1, cells in the surface's k order, k = (su + R) S + (sv + R)
+ *     shift  i32 [N][2]      the search shift of every layer (all zero when none is given)
+ *     sum    f64 [N][S^2]    cnt  u16 [N][S^2]    lay  u16 [N]    layers
+ *   10 bytes per cell: 1.9 GB at 200,000 points and R 15.
+ *
+ *   Adding a layer -- a surface array surf [N][S^2] and a flag refused [N]:
+ *     every cell v:   isfinite(v): sum += (double)v, cnt += 1;   any other cell (NaN, +-Inf) adds nothing;
+ *     every point:    not refused: lay += 1;
+ *     layers += 1.
+ *   Additions happen in the order of the add calls; that order is part of the definition, so a result is deterministic and a host
+ *   program that adds in f64 in the same order reproduces sum bit for bit.
+ *   Mean surface at min_count >= 1:  mean[k] = (float)(sum[k] / (double)cnt[k]) where cnt[k] >= min_count, NaN elsewhere (the division
+ *   is f64, rounded once to f32).
+ *   Result:  a point with lay == 0 gets status -3 in its record and in every candidate slot.  Any other point gets exactly what the
+ *   tail of the exhaustive search makes of mean with the stack's shift: the record of mimc3_match_ncc_full_any -- statuses -2 (no
+ *   finite cell) and -4 (peak on the border), the 3x3 fit, ncc_fit, SNR, the Hessian -- and the npeaks <= 8 ranked local maxima.
+ *   du, dv are relative to uv0 + offset, as everywhere; offset may differ from layer to layer (it is each pair's co-registration),
+ *   shift, N and R are the stack's.
+ *   Consequence: a stack of ONE layer at min_count 1 returns the record and the candidates of mimc3_match_ncc_full_any(mode 1) bit for
+ *   bit, because (float)((double)v / 1.0) == v.
+ *   Not covered: several GPUs, the pyramid entries, MIMC3_hip_offsets, weights per layer. */
+#define MIMC3_STACK_CHUNK 65536
+/* Sizes and zeroes the stack and uploads shift (host [N][2], or NULL).  1 <= R <= 15.  A second call discards the first stack; N = 0
+ * releases its memory (R and shift are then ignored).  A chip-atlas context: MIMC3_ESTATE.  Returns when the stack is ready. */
+int mimc3_stack_begin(mimc3_ctx *ctx, int32_t N, int32_t R, const int32_t *shift /*host [N][2] or NULL*/);
+/* One layer from the resident pair: mimc3_match_ncc_full_any(mode 1, npeaks 0, shift = the stack's, surf) with these arguments; a point
+ * is refused where that call's record has status -3.  Points go in chunks of MIMC3_STACK_CHUNK through a layer scratch of the context
+ * (a buffer of its own, at most 252 MB whatever N is).  Refusals: those of mimc3_match_ncc_full_any; N differs from the stack's:
+ * MIMC3_EINVAL; no stack: MIMC3_ESTATE; 65,535 layers added: MIMC3_ESTATE.  Everything is validated before the first launch: a refused
+ * add leaves the stack's bytes as they were. */
+int mimc3_stack_add(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap);
+/* Device-resident variant: everything is enqueued on `stream`, no sync (the first call on a pair builds its f32 planes on the context's
+ * own stream and waits for them first; a call that makes the layer scratch grow waits for the device before it enqueues anything).  A
+ * point that breaks the host entry's bounds has an all-NaN surface and counts as a layer (the contract of the _dev search entries). */
+int mimc3_stack_add_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
+                        void *stream);
+/* One layer from the caller's surfaces -- of another context, of a later kernel, crafted: surf [N][S^2] in k order, refused [N]
+ * (not 0 = refused) or NULL (no point is).  Refusals: the stack's, as above. */
+int mimc3_stack_add_surfaces(mimc3_ctx *ctx, const float *surf /*host [N][S^2]*/, const uint8_t *refused /*host [N] or NULL*/, int32_t N);
+int mimc3_stack_add_surfaces_dev(mimc3_ctx *ctx, const float *d_surf, const uint8_t *d_refused, int32_t N, void *stream);
+/* The result.  out [N][8]; cand [npeaks][N][3], NULL iff npeaks == 0 (npeaks 0..8); surf [N][S^2] gets mean and count [N] gets lay
+ * when given.  Reads the stack and leaves it unchanged: more layers may follow, and finishing twice gives the same bytes.
+ * min_count < 1 or > 65535: MIMC3_EINVAL; no stack: MIMC3_ESTATE. */
+int mimc3_stack_finish(mimc3_ctx *ctx, int32_t npeaks, int32_t min_count, float *out /*[N][8] host*/,
+                       float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/, float *surf /*[N][S^2] host, or NULL*/,
+                       uint16_t *count /*[N] host, or NULL*/);
+int mimc3_stack_finish_dev(mimc3_ctx *ctx, int32_t npeaks, int32_t min_count, float *d_out, float *d_cand, float *d_surf,
+                           uint16_t *d_count, void *stream);
+/* N, R and the number of layers added (each may be NULL); all 0 when the context has no stack. */
+int mimc3_stack_info(mimc3_ctx *ctx, int32_t *N, int32_t *R, int32_t *layers);
+
 /* ---- Coarse-to-fine exhaustive search over an image pyramid (no reference counterpart: the reach of mimc3_match_ncc_full, +-R
  *      around uv0 + offset + shift, made about R (2^L - 1) px by searching a reduced pair first -- the offset trackers' standard).
  *

@@ -66,6 +66,14 @@ _lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c
 _lib.mimc3_match_ncc_full_fb.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
 _lib.mimc3_match_ncc_full_fb_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp, _vp]
+_lib.mimc3_stack_begin.argtypes = [_vp, C.c_int32, C.c_int32, _vp]
+_lib.mimc3_stack_add.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32]
+_lib.mimc3_stack_add_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
+_lib.mimc3_stack_add_surfaces.argtypes = [_vp, _f32p, _vp, C.c_int32]
+_lib.mimc3_stack_add_surfaces_dev.argtypes = [_vp, _vp, _vp, C.c_int32, _vp]
+_lib.mimc3_stack_finish.argtypes = [_vp, C.c_int32, C.c_int32, _f32p, _vp, _vp, _vp]
+_lib.mimc3_stack_finish_dev.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]
+_lib.mimc3_stack_info.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
 _lib.mimc3_match_ncc_pyramid_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
@@ -221,6 +229,7 @@ def get_uv_pivot_counts(xyuvav, dt, mpp, ocw, H, W, aw_sf=1.8, aw_cre=10.0):
 
 
 CORRIDOR_BYTES = 24      # MIMC3_CORRIDOR_BYTES
+STACK_CHUNK = 65536      # MIMC3_STACK_CHUNK: the points of one launch of Context.stack_add
 
 
 def prior_shift(xyuvav, dt, mpp):
@@ -615,6 +624,75 @@ class Context:
         _check(_lib.mimc3_match_ncc_full_fb_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                                 npeaks, int(mode), d_out, d_cand or None, d_fb, stream),
                "match_ncc_full_fb_dev")
+
+    # ---- NCC stacking (mimc3_stack_*): the surfaces of several pairs averaged per cell, the peak searched once on the mean ----
+    def stack_begin(self, n, radius, shift=None):
+        """Size and zero the context's stack for n grid points and search radius `radius` (1..15); shift int32[n][2] is the search shift
+        of every layer (None = zero).  A second call discards the first stack, n = 0 releases its memory.  The stack outlives the pair:
+        set_images and filter_images leave it alone."""
+        n = int(n)
+        sh = None
+        if shift is not None and n > 0:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"stack_begin: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_stack_begin(self._h, n, int(radius), None if sh is None else sh.ctypes.data), "stack_begin")
+
+    def stack_add(self, xyuvav, offset, ocw, swap=False):
+        """One layer from the resident pair: the surfaces of match_ncc_full_any(mode=1) with the stack's shift and radius, accumulated
+        cell by cell (finite cells only); a point that call refuses (status -3) does not count as a layer of that point."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        _check(_lib.mimc3_stack_add(self._h, xy, xy.shape[0], np.ascontiguousarray(offset, np.int32), ocw, 1 if swap else 0), "stack_add")
+
+    def stack_add_dev(self, d_xyuvav, n, offset, ocw, stream=0, swap=False):
+        """Device-pointer variant (enqueue only)."""
+        _check(_lib.mimc3_stack_add_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), ocw, 1 if swap else 0, stream), "stack_add_dev")
+
+    def stack_add_surfaces(self, surf, refused=None):
+        """One layer from the caller's surfaces float32[n][(2 radius + 1)^2] in k order; refused bool[n] (None = no point is)."""
+        sf = np.ascontiguousarray(surf, np.float32)
+        if sf.ndim != 2:
+            raise ValueError(f"stack_add_surfaces: surf must be float32[n][cells], got {sf.shape}")
+        n, r = self.stack_info()[:2]
+        if n and sf.shape[1] != (2 * r + 1) ** 2:
+            raise ValueError(f"stack_add_surfaces: surf must have {(2 * r + 1) ** 2} cells per point, got {sf.shape[1]}")
+        rf = None
+        if refused is not None:
+            rf = np.ascontiguousarray(np.asarray(refused) != 0, np.uint8)
+            if rf.shape != (sf.shape[0],):
+                raise ValueError(f"stack_add_surfaces: refused must be [{sf.shape[0]}], got {rf.shape}")
+        _check(_lib.mimc3_stack_add_surfaces(self._h, sf, None if rf is None else rf.ctypes.data, sf.shape[0]), "stack_add_surfaces")
+
+    def stack_add_surfaces_dev(self, d_surf, n, d_refused=0, stream=0):
+        """Device-pointer variant (enqueue only): d_surf float32[n][cells], d_refused uint8[n] or 0."""
+        _check(_lib.mimc3_stack_add_surfaces_dev(self._h, d_surf, d_refused or None, n, stream), "stack_add_surfaces_dev")
+
+    def stack_finish(self, npeaks=0, min_count=1, surface=False):
+        """The result of the stack -> (float32[n][8] record, float32[npeaks][n][3] candidates or None when npeaks == 0, uint16[n] layers
+        per point[, float32[n][cells] mean surface with surface=True]): the tail of the exhaustive search over the mean surface, a
+        cell being the mean of its finite values where at least min_count layers had one and NaN elsewhere; status -3 for a point no
+        layer took.  Leaves the stack unchanged: more layers may follow."""
+        n, r, _ = self.stack_info()
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        count = np.empty(n, np.uint16)
+        surf = np.empty((n, (2 * r + 1) ** 2), np.float32) if surface else None
+        _check(_lib.mimc3_stack_finish(self._h, npeaks, int(min_count), out, None if cand is None else cand.ctypes.data,
+                                       None if surf is None else surf.ctypes.data, count.ctypes.data), "stack_finish")
+        return (out, cand, count, surf) if surface else (out, cand, count)
+
+    def stack_finish_dev(self, npeaks, min_count, d_out, d_cand=0, d_surf=0, d_count=0, stream=0):
+        """Device-pointer variant (enqueue only): d_out float32[n][8], d_cand float32[npeaks][n][3] (0 iff npeaks == 0), d_surf
+        float32[n][cells] or 0, d_count uint16[n] or 0."""
+        _check(_lib.mimc3_stack_finish_dev(self._h, int(npeaks), int(min_count), d_out, d_cand or None, d_surf or None, d_count or None,
+                                           stream), "stack_finish_dev")
+
+    def stack_info(self):
+        """(n, radius, layers) of the context's stack; (0, 0, 0) without one."""
+        n, r, k = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(_lib.mimc3_stack_info(self._h, C.byref(n), C.byref(r), C.byref(k)), "stack_info")
+        return n.value, r.value, k.value
 
     def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None, any_pair=False):
         """The candidates of the exhaustive search over image variants and chip sizes -> dp float32[ndp][N][3], ndp = len(kernels) *

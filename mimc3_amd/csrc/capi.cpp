@@ -22,6 +22,7 @@
 #include "conv2_kernel.h"
 #include "cp_kernel.h"
 #include "fb_kernel.h"
+#include "stack_kernel.h"
 #include <ctime>
 #include <cstdlib>
 
@@ -141,6 +142,16 @@ struct mimc3_ctx {
     // mimc3_match_ncc_full_fb: the backward search's rows ((1 + npeaks) N of them) -- xyuvav' [rows][6], shift' [rows][2], its records
     // [rows][8], one reason byte per row -- and the host entry's fb [rows][4]
     DevBuf fb_xy, fb_sh, fb_rec, fb_why, fb_out;
+    // mimc3_stack_*: the stack (NCC surfaces accumulated over several pairs; state of its own, which the image setters never touch) --
+    // sum f64 [N][S^2], cnt u16 [N][S^2], lay u16 [N], shift i32 [N][2] (zeros when none was given; a host copy for the host entry's
+    // bounds check); the layer scratch of an add (surfaces and records of one chunk of points) and the staging of the host entries
+    struct Stack {
+        DevBuf sum, cnt, lay, shift;
+        DevBuf layer, rec, ref;         // one chunk: f32 [chunk][S^2], f32 [chunk][8]; the host entry's refused flags [N]
+        DevBuf out, cand, surf, count;  // mimc3_stack_finish's host entry
+        std::vector<int32_t> h_shift;
+        int32_t N = 0, R = 0, layers = 0;
+    } stk;
 };
 
 static constexpr size_t kPinChunk = 4u << 20;
@@ -1127,6 +1138,236 @@ extern "C" int mimc3_match_ncc_full_fb(mimc3_ctx *c, const double *xyuvav, int32
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
     if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
     return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, 0, out, cand, npeaks > 0, en, 4, mode, nullptr, fb);
+}
+
+// ---------------------------------------------------------------------------------------------
+// NCC stacking (mimc3_stack_*, stack_kernel.hip): the surfaces of several pairs -- each a mimc3_match_ncc_full_any(mode 1) layer on the
+// pair that is resident, or a caller's array -- accumulated per cell in f64, and the tail of the exhaustive search over their mean.
+// The stack is state of the context that the image setters do not touch.  Every entry validates everything before its first launch.
+// ---------------------------------------------------------------------------------------------
+static void stack_release(mimc3_ctx *c)
+{
+    auto &k = c->stk;
+    for (DevBuf *b : {&k.sum, &k.cnt, &k.lay, &k.shift, &k.layer, &k.rec, &k.ref, &k.out, &k.cand, &k.surf, &k.count}) b->release();
+    std::vector<int32_t>().swap(k.h_shift);
+    k.N = 0; k.R = 0; k.layers = 0;
+}
+
+static inline size_t stack_cells(const mimc3_ctx *c) { return (size_t)((2 * c->stk.R + 1) * (2 * c->stk.R + 1)); }
+
+extern "C" int mimc3_stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift)
+{
+    const std::string en("mimc3_stack_begin");
+    if (!c || N < 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    HIP_TRY(hipSetDevice(c->device));
+    if (N == 0) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        stack_release(c);
+        return 0;
+    }
+    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
+    auto &k = c->stk;
+    k.N = 0; k.R = 0; k.layers = 0;                             // (no stack while this one is being sized)
+    const size_t NC = (size_t)((2 * R + 1) * (2 * R + 1)), cells = (size_t)N * NC;
+    HIP_TRY(k.sum.reserve(sizeof(double) * cells));
+    HIP_TRY(k.cnt.reserve(sizeof(uint16_t) * cells));
+    HIP_TRY(k.lay.reserve(sizeof(uint16_t) * (size_t)N));
+    HIP_TRY(k.shift.reserve(sizeof(int32_t) * 2 * (size_t)N));
+    HIP_TRY(hipMemsetAsync(k.sum.p, 0, sizeof(double) * cells, c->stream));
+    HIP_TRY(hipMemsetAsync(k.cnt.p, 0, sizeof(uint16_t) * cells, c->stream));
+    HIP_TRY(hipMemsetAsync(k.lay.p, 0, sizeof(uint16_t) * (size_t)N, c->stream));
+    k.h_shift.assign(2 * (size_t)N, 0);
+    if (shift) {
+        std::memcpy(k.h_shift.data(), shift, sizeof(int32_t) * 2 * (size_t)N);
+        RC_TRY(h2d_copy(c, k.shift.p, shift, sizeof(int32_t) * 2 * (size_t)N));
+    } else {
+        HIP_TRY(hipMemsetAsync(k.shift.p, 0, sizeof(int32_t) * 2 * (size_t)N, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));                   // (the adds may come in on another stream)
+    k.N = N; k.R = R;
+    return 0;
+}
+
+extern "C" int mimc3_stack_info(mimc3_ctx *c, int32_t *N, int32_t *R, int32_t *layers)
+{
+    if (!c) return mimc3::fail(MIMC3_EINVAL, "mimc3_stack_info: bad argument");
+    if (N) *N = c->stk.N;
+    if (R) *R = c->stk.R;
+    if (layers) *layers = c->stk.layers;
+    return 0;
+}
+
+// what every add checks about the stack itself
+static int stack_add_state(mimc3_ctx *c, int32_t N, const std::string &en)
+{
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    if (c->stk.N == 0) return mimc3::fail(MIMC3_ESTATE, en + ": no stack (mimc3_stack_begin)");
+    if (N != c->stk.N) return mimc3::fail(MIMC3_EINVAL, en + ": N differs from the stack's");
+    if (c->stk.layers >= 65535) return mimc3::fail(MIMC3_ESTATE, en + ": the stack holds 65,535 layers");
+    return 0;
+}
+
+static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
+                         void *stream, const char *entry)
+{
+    const std::string en(entry);
+    // mimc3_match_ncc_full_any_dev's refusals and the stack's own, before anything is allocated or enqueued
+    if (!c || !d_xyuvav || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    RC_TRY(stack_add_state(c, N, en));
+    auto &k = c->stk;
+    const size_t NC = stack_cells(c);
+    const size_t chunk = (size_t)(N < mimc3::kStackChunk ? N : mimc3::kStackChunk);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NC));
+    HIP_TRY(k.rec.reserve(sizeof(float) * 8 * chunk));
+    if (!c->fplanes_ok) RC_TRY(build_f32(c));                   // (the float kernel's planes: built on the context's stream, which it drains)
+    const bool timing = c->timing;
+    if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    c->timing = false;                  // (the events bracket the whole call)
+    float *layer = static_cast<float *>(k.layer.p), *rec = static_cast<float *>(k.rec.p);
+    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
+        const int32_t n = (int32_t)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
+        const int rc = full_any_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, static_cast<const int32_t *>(k.shift.p) + 2 * g0, ocw, k.R, 0, swap,
+                                    1, rec, nullptr, layer, stream);
+        if (rc) { c->timing = timing; return rc; }
+        const hipError_t e = mimc3::launch_stack_add(layer, rec, nullptr, n, (int)NC, static_cast<double *>(k.sum.p) + g0 * NC,
+                                                     static_cast<uint16_t *>(k.cnt.p) + g0 * NC, static_cast<uint16_t *>(k.lay.p) + g0, s);
+        if (e != hipSuccess) { c->timing = timing; return mimc3::hip_fail(e, "stack add kernel launch"); }
+    }
+    c->timing = timing;
+    k.layers++;
+    if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
+                                   void *stream)
+{
+    return stack_add_dev(c, d_xyuvav, N, off_u, off_v, ocw, swap, stream, "mimc3_stack_add_dev");
+}
+
+extern "C" int mimc3_stack_add(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap)
+{
+    const char *entry = "mimc3_stack_add";
+    const std::string en(entry);
+    if (!c || !xyuvav || !offset || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    RC_TRY(stack_add_state(c, N, en));
+    // the chip inside the image, the search box inside the planes' zero border (as mimc3_match_ncc_full_any's host entry)
+    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
+    const int64_t pad = mimc3::kU8Pad, h = c->stk.R + ocw;
+    const int32_t *shift = c->stk.h_shift.data();
+    for (int32_t g = 0; g < N; ++g) {
+        const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
+        const int64_t cu = (int64_t)u0 + offset[0] + shift[2 * (size_t)g], cv = (int64_t)v0 + offset[1] + shift[2 * (size_t)g + 1];
+        if (cu - h < -pad || cu + h >= c->W + pad || cv - h < -pad || cv + h >= c->H + pad)
+            return mimc3::fail(MIMC3_EBOUNDS, en + ": grid point " + std::to_string(g) + " search box leaves the zero border");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
+    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
+    RC_TRY(stack_add_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, swap, c->stream, entry));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int mimc3_stack_add_surfaces_dev(mimc3_ctx *c, const float *d_surf, const uint8_t *d_refused, int32_t N, void *stream)
+{
+    const std::string en("mimc3_stack_add_surfaces_dev");
+    if (!c || !d_surf || N <= 0 || (reinterpret_cast<uintptr_t>(d_surf) & 3u)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    RC_TRY(stack_add_state(c, N, en));
+    auto &k = c->stk;
+    const size_t NC = stack_cells(c), chunk = (size_t)mimc3::kStackChunk;
+    HIP_TRY(hipSetDevice(c->device));
+    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
+        const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
+        const hipError_t e = mimc3::launch_stack_add(d_surf + g0 * NC, nullptr, d_refused ? d_refused + g0 : nullptr, n, (int)NC,
+                                                     static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
+                                                     static_cast<uint16_t *>(k.lay.p) + g0, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess) return mimc3::hip_fail(e, "stack add kernel launch");
+    }
+    k.layers++;
+    return 0;
+}
+
+extern "C" int mimc3_stack_add_surfaces(mimc3_ctx *c, const float *surf, const uint8_t *refused, int32_t N)
+{
+    const std::string en("mimc3_stack_add_surfaces");
+    if (!c || !surf || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    RC_TRY(stack_add_state(c, N, en));
+    auto &k = c->stk;
+    const size_t NC = stack_cells(c);
+    const size_t chunk = (size_t)(N < mimc3::kStackChunk ? N : mimc3::kStackChunk);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NC));
+    if (refused) {
+        HIP_TRY(k.ref.reserve((size_t)N));
+        RC_TRY(h2d_copy(c, k.ref.p, refused, (size_t)N));
+    }
+    // one chunk of surfaces at a time through the layer scratch; copies and launches are ordered on the context's stream
+    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
+        const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
+        RC_TRY(h2d_copy(c, k.layer.p, surf + g0 * NC, sizeof(float) * (size_t)n * NC));
+        const hipError_t e = mimc3::launch_stack_add(static_cast<const float *>(k.layer.p), nullptr,
+                                                     refused ? static_cast<const uint8_t *>(k.ref.p) + g0 : nullptr, n, (int)NC,
+                                                     static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
+                                                     static_cast<uint16_t *>(k.lay.p) + g0, c->stream);
+        if (e != hipSuccess) return mimc3::hip_fail(e, "stack add kernel launch");
+    }
+    k.layers++;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static int stack_finish_check(mimc3_ctx *c, int32_t npeaks, int32_t min_count, const float *out, const float *cand, const std::string &en)
+{
+    if (!c || !out) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
+    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": cand goes with npeaks > 0");
+    if (min_count < 1 || min_count > 65535) return mimc3::fail(MIMC3_EINVAL, en + ": min_count must be in 1..65535");
+    if (c->stk.N == 0) return mimc3::fail(MIMC3_ESTATE, en + ": no stack (mimc3_stack_begin)");
+    return 0;
+}
+
+extern "C" int mimc3_stack_finish_dev(mimc3_ctx *c, int32_t npeaks, int32_t min_count, float *d_out, float *d_cand, float *d_surf,
+                                      uint16_t *d_count, void *stream)
+{
+    RC_TRY(stack_finish_check(c, npeaks, min_count, d_out, d_cand, "mimc3_stack_finish_dev"));
+    auto &k = c->stk;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    const hipError_t e = mimc3::launch_stack_tail(static_cast<const double *>(k.sum.p), static_cast<const uint16_t *>(k.cnt.p),
+                                                  static_cast<const uint16_t *>(k.lay.p), static_cast<const int32_t *>(k.shift.p), k.N, k.R,
+                                                  npeaks, min_count, d_out, d_cand, d_surf, d_count, s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "stack tail kernel launch");
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_stack_finish(mimc3_ctx *c, int32_t npeaks, int32_t min_count, float *out, float *cand, float *surf, uint16_t *count)
+{
+    RC_TRY(stack_finish_check(c, npeaks, min_count, out, cand, "mimc3_stack_finish"));
+    auto &k = c->stk;
+    const size_t N = (size_t)k.N, NC = stack_cells(c);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(k.out.reserve(sizeof(float) * 8 * N));
+    if (npeaks) HIP_TRY(k.cand.reserve(sizeof(float) * 3 * (size_t)npeaks * N));
+    if (surf) HIP_TRY(k.surf.reserve(sizeof(float) * N * NC));
+    if (count) HIP_TRY(k.count.reserve(sizeof(uint16_t) * N));
+    RC_TRY(mimc3_stack_finish_dev(c, npeaks, min_count, static_cast<float *>(k.out.p), npeaks ? static_cast<float *>(k.cand.p) : nullptr,
+                                  surf ? static_cast<float *>(k.surf.p) : nullptr, count ? static_cast<uint16_t *>(k.count.p) : nullptr,
+                                  c->stream));
+    RC_TRY(d2h_copy(c, out, k.out.p, sizeof(float) * 8 * N));
+    if (npeaks) RC_TRY(d2h_copy(c, cand, k.cand.p, sizeof(float) * 3 * (size_t)npeaks * N));
+    if (surf) RC_TRY(d2h_copy(c, surf, k.surf.p, sizeof(float) * N * NC));
+    if (count) RC_TRY(d2h_copy(c, count, k.count.p, sizeof(uint16_t) * N));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

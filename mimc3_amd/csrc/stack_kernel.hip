@@ -1,0 +1,141 @@
+// stack_kernel.hip -- NCC stacking (mimc3_stack_*; stack_kernel.h): stack_add_kernel accumulates one layer of surfaces into the stack's
+// f64 sums and u16 counts, stack_tail_kernel forms the mean surface of every point in LDS and hands it to the tail every front of the
+// exhaustive search shares (match_full_tail.h, unmodified: the record and the candidates of a stack are that text's).
+#include "stack_kernel.h"
+#include "match_full_tail.h"
+
+namespace mimc3 {
+
+namespace {
+
+// ---- the accumulation: elementwise over the chunk's flat cell array, 24 bytes of traffic per cell (4 read, 10 read and written) ------
+// a point's layer count: the lane that owns the point's cell k = 0 calls this
+__device__ __forceinline__ void stack_count_layer(const float *__restrict__ rec, const uint8_t *__restrict__ refused, uint32_t pt,
+                                                  uint16_t *__restrict__ lay)
+{
+    const bool ref = (rec && rec[8 * (size_t)pt + 2] == -3.0f) || (refused && refused[pt] != 0);
+    if (!ref) lay[pt] = (uint16_t)(lay[pt] + 1);
+}
+
+// Cells [head, head + 4 nvec) go four per lane (surf + head is 16-byte aligned; S^2 is odd, so a group of four may straddle two points);
+// the head and the total - head - 4 nvec cells behind them, six at most, go one per lane of block 0.  wide: sum + head and cnt + head
+// are 16- and 8-byte aligned as well (always so on the stack's own chunks)
+__global__ __launch_bounds__(256) void stack_add_kernel(const float *__restrict__ surf, const float *__restrict__ rec,
+                                                        const uint8_t *__restrict__ refused, uint32_t total, uint32_t NC, uint32_t head,
+                                                        uint32_t nvec, int wide, double *__restrict__ sum, uint16_t *__restrict__ cnt,
+                                                        uint16_t *__restrict__ lay)
+{
+    const uint32_t stride = gridDim.x * 256u;
+    for (uint32_t g = blockIdx.x * 256u + threadIdx.x; g < nvec; g += stride) {
+        const uint32_t i = head + 4u * g;
+        const float4 v = *reinterpret_cast<const float4 *>(surf + i);
+        const bool f0 = __builtin_isfinite(v.x), f1 = __builtin_isfinite(v.y), f2 = __builtin_isfinite(v.z), f3 = __builtin_isfinite(v.w);
+        if (wide) {
+            double2 a = *reinterpret_cast<const double2 *>(sum + i), b = *reinterpret_cast<const double2 *>(sum + i + 2);
+            ushort4 c = *reinterpret_cast<const ushort4 *>(cnt + i);
+            if (f0) { a.x += (double)v.x; c.x = (uint16_t)(c.x + 1); }
+            if (f1) { a.y += (double)v.y; c.y = (uint16_t)(c.y + 1); }
+            if (f2) { b.x += (double)v.z; c.z = (uint16_t)(c.z + 1); }
+            if (f3) { b.y += (double)v.w; c.w = (uint16_t)(c.w + 1); }
+            *reinterpret_cast<double2 *>(sum + i) = a;
+            *reinterpret_cast<double2 *>(sum + i + 2) = b;
+            *reinterpret_cast<ushort4 *>(cnt + i) = c;
+        } else {
+            if (f0) { sum[i] += (double)v.x; cnt[i] = (uint16_t)(cnt[i] + 1); }
+            if (f1) { sum[i + 1] += (double)v.y; cnt[i + 1] = (uint16_t)(cnt[i + 1] + 1); }
+            if (f2) { sum[i + 2] += (double)v.z; cnt[i + 2] = (uint16_t)(cnt[i + 2] + 1); }
+            if (f3) { sum[i + 3] += (double)v.w; cnt[i + 3] = (uint16_t)(cnt[i + 3] + 1); }
+        }
+        const uint32_t q = i / NC, r = i - q * NC;                // NC >= 9: at most one cell k = 0 among the four
+        if (r == 0) stack_count_layer(rec, refused, q, lay);
+        else if (r + 3u >= NC) stack_count_layer(rec, refused, q + 1u, lay);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < total - 4u * nvec) {
+        const uint32_t i = threadIdx.x < head ? threadIdx.x : 4u * nvec + threadIdx.x;
+        const float v = surf[i];
+        if (__builtin_isfinite(v)) { sum[i] += (double)v; cnt[i] = (uint16_t)(cnt[i] + 1); }
+        if (i % NC == 0) stack_count_layer(rec, refused, i / NC, lay);
+    }
+}
+
+// ---- the result: one wave64 per point, four points per workgroup -------------------------------------------------------------------
+template <bool MULTI_>
+struct StackCfg {                       // (what match_full_tail.h asks of a configuration)
+    static constexpr int VP = 33;       // pitch (words) of the surface
+    static constexpr bool PEAK = false, MULTI = MULTI_;
+};
+
+constexpr int kStackWaves = 4;
+
+template <bool MULTI>
+__global__ __launch_bounds__(64 * kStackWaves) void stack_tail_kernel(MatchU8Args p, const double *__restrict__ sum,
+                                                                      const uint16_t *__restrict__ cnt, const uint16_t *__restrict__ lay,
+                                                                      int min_count, float *__restrict__ surf, uint16_t *__restrict__ count)
+{
+    using C = StackCfg<MULTI>;
+    __shared__ float vals[kStackWaves][32 * C::VP];              // val[y * VP + x], x, y <= 30
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int gidx = blockIdx.x * kStackWaves + wave;
+    const int R = p.full_R, S = 2 * R + 1, NC = S * S;
+    float *val = vals[wave];
+    const bool live = gidx < p.N;
+    int layers = 0;
+    if (live) {
+        layers = lay[gidx];
+        if (count && lane == 0) count[gidx] = (uint16_t)layers;
+        const size_t base = (size_t)gidx * (size_t)NC;
+        for (int k = lane; k < NC; k += 64) {
+            const int c = cnt[base + k];
+            const float m = c >= min_count ? (float)(sum[base + k] / (double)c) : __builtin_nanf("");     // f64 division, rounded once
+            const int x = k / S, y = k - S * x;
+            val[y * C::VP + x] = m;
+            if (surf) surf[base + k] = m;
+        }
+    }
+    __syncthreads();                    // every wave, the ones beyond N too: the surface is in LDS before the tail reads it
+    if (!live) return;
+    if (layers == 0) {
+        if (lane == 0) { mx::full_store(p.out + 8 * (size_t)gidx, -3.0f); mx::full_cand_fill<C>(p, gidx, -3.0f); }
+        return;
+    }
+    const int shu = p.full_shift ? p.full_shift[2 * (size_t)gidx] : 0, shv = p.full_shift ? p.full_shift[2 * (size_t)gidx + 1] : 0;
+    mx::full_tail<C>(p, val, gidx, shu, shv, lane);
+    if constexpr (MULTI) mx::full_tail_multi<C>(p, val, gidx, shu, shv, lane);
+}
+
+}  // namespace
+
+hipError_t launch_stack_add(const float *surf, const float *rec, const uint8_t *refused, int n, int NC, double *sum, uint16_t *cnt,
+                            uint16_t *lay, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (!surf || !sum || !cnt || !lay || n > kStackChunk || NC < 9 || NC > 961) return hipErrorInvalidValue;
+    const uint32_t total = (uint32_t)n * (uint32_t)NC;            // <= 65536 * 961 < 2^26
+    uint32_t head = (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(surf) & 15u)) & 15u) / 4u;
+    if (reinterpret_cast<uintptr_t>(surf) & 3u) return hipErrorInvalidValue;
+    if (head > total) head = total;
+    const uint32_t nvec = (total - head) / 4u;
+    const int wide = (reinterpret_cast<uintptr_t>(sum + head) & 15u) == 0 && (reinterpret_cast<uintptr_t>(cnt + head) & 7u) == 0;
+    uint32_t nb = (nvec + 255u) / 256u;
+    nb = nb < 1u ? 1u : nb > 2048u ? 2048u : nb;                 // 256 CUs x 8 workgroups; the grid-stride loop takes the rest
+    hipLaunchKernelGGL(stack_add_kernel, dim3(nb), dim3(256), 0, s, surf, rec, refused, total, (uint32_t)NC, head, nvec, wide, sum, cnt, lay);
+    return hipGetLastError();
+}
+
+hipError_t launch_stack_tail(const double *sum, const uint16_t *cnt, const uint16_t *lay, const int32_t *shift, int N, int R, int npeaks,
+                             int min_count, float *out, float *cand, float *surf, uint16_t *count, hipStream_t s)
+{
+    if (N <= 0) return hipSuccess;
+    if (!sum || !cnt || !lay || !out || R < 1 || R > 15 || min_count < 1 || npeaks < 0 || npeaks > kFullMaxPeaks ||
+        (npeaks > 0) != (cand != nullptr))
+        return hipErrorInvalidValue;
+    MatchU8Args a{};
+    a.out = out; a.N = N; a.full_R = R; a.full_shift = shift;
+    if (cand) { a.full_cand = cand; a.full_npeaks = npeaks; }
+    const unsigned nb = (unsigned)(((size_t)N + kStackWaves - 1) / kStackWaves);
+    if (cand) hipLaunchKernelGGL(stack_tail_kernel<true>, dim3(nb), dim3(64 * kStackWaves), 0, s, a, sum, cnt, lay, min_count, surf, count);
+    else hipLaunchKernelGGL(stack_tail_kernel<false>, dim3(nb), dim3(64 * kStackWaves), 0, s, a, sum, cnt, lay, min_count, surf, count);
+    return hipGetLastError();
+}
+
+}  // namespace mimc3
