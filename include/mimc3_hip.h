@@ -82,7 +82,8 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *   8 = the exhaustive search of mimc3_match_ncc_full_dn on an integral-f32 pair (16-bit DN and its filtered forms): the f32 planes'
  *       search kernel;
  *   9 = the exhaustive search of mimc3_match_ncc_full_any on any other f32 pair (non-integral pixels, NaN or negative nulls), or on any
- *       pair with its mode 1: the float search kernel on the f32 planes, without tables.
+ *       pair with its mode 1: the float search kernel on the f32 planes, without tables;
+ *  10 = the exhaustive search beyond +-15 px (mimc3_match_ncc_wide at R >= 16): the wide float search kernel on the same planes.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -305,6 +306,41 @@ int mimc3_match_ncc_full_any(mimc3_ctx *ctx, const double *xyuvav, int32_t N, co
 int mimc3_match_ncc_full_any_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                  const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
                                  float *d_cand, float *d_surf, void *stream);
+
+/* ---- Exhaustive search beyond +-15 px: ONE exact pass at full resolution over a search range of up to +-47 px, with candidates from the
+ *      whole range -- for a displacement the a-priori shift misses by more than 15 px, which the entries above return as status -4 or
+ *      as a confident wrong peak, and which the pyramid reaches only by deciding on reduced images.
+ *
+ *   The definition is that of mimc3_match_ncc_full_any in mode 1, word for word (see there), with 1 <= R <= mimc3_wide_max_radius(ocw):
+ *   every pair runs on its zero-bordered f32 planes whatever its class; the two null rules (validity over the chip and over the whole
+ *   (2R + 2 ocw + 1)^2 box, status -3 above a ratio of 0.8; inclusion a >= 1e-10 && b >= 1e-10); the terms (f32 products widened to f64,
+ *   additions only) and the finish (the reference's f64 operations, correctly rounded); the first-wins arg-max in k = (su + R)(2R + 1) +
+ *   (sv + R); statuses -2 / -3 / -4, the 3 x 3 fit, ncc_fit, the Hessian, SNR; the local-maximum rule and the rank of the candidates; surf
+ *   [N][(2R+1)^2] in k order, all NaN at status -3; MIMC3_EBOUNDS (the search box must stay inside the planes' 256-px zero border) and
+ *   MIMC3_ESTATE as there.  The order of a float sum is the kernel's own, a function of (ocw, R, npeaks == 0) alone, additions only: the
+ *   bound (m - 1) 2^-53 of that text holds unchanged, because m <= 6,561 does not depend on R.
+ *   R <= 15    IS mimc3_match_ncc_full_any(mode 1): the same kernel, the same bytes.  mimc3_ctx_last_path reports 9.
+ *   R >= 16    the wide kernel (match_wide_kernel.hip).  mimc3_ctx_last_path reports 10.
+ *   mimc3_wide_max_radius(ocw)   the largest R taken at this chip size: 47 (a 95 x 95 surface) wherever box, chip and surface fit the
+ *              160 KB of LDS of a compute unit -- ocw 7, 15, 16, 30, 32 -- and 39 at ocw 40; 0 for an ocw that is not one of the six.
+ *   Refusals: R outside 1 .. mimc3_wide_max_radius(ocw), ocw not one of 7, 15, 16, 30, 32, 40, npeaks outside 0..8, cand NULL unless
+ *   npeaks == 0: MIMC3_EINVAL; a chip outside the image or a box outside the border: MIMC3_EBOUNDS; no images, or a chip-atlas context:
+ *   MIMC3_ESTATE.
+ *   mimc3_wide_lds_bytes(ocw, R)   the dynamic LDS (bytes) of the wide kernel's launch at this chip size and radius, from the layout the
+ *              launch uses (tools and documents quote it); 0 outside 1 .. mimc3_wide_max_radius(ocw).
+ *   Not covered: the stack (mimc3_stack_*), mimc3_match_ncc_full_fb and the pyramid entries keep R <= 15; several GPUs; MIMC3_hip_offsets;
+ *   Context.full_candidates of the Python layer. */
+int mimc3_wide_max_radius(int32_t ocw);
+int mimc3_wide_lds_bytes(int32_t ocw, int32_t R);
+int mimc3_match_ncc_wide(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                         const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                         int32_t swap, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
+                         float *surf /*[N][(2R+1)^2] host, or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_any_dev (a point that breaks the bounds gets the all-NaN record, NaN
+ * candidate slots and an all-NaN surface). */
+int mimc3_match_ncc_wide_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                             const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                             float *d_cand, float *d_surf, void *stream);
 
 /* ---- Forward-backward consistency of the exhaustive search: is a peak RECIPROCAL -- does matching back from where a point landed return
  *      to where it started?  (The back-matching test AMPCOR and IMCORR users apply after the run; the record's quality columns all

@@ -61,6 +61,11 @@ _lib.mimc3_match_ncc_full_any.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c
                                           _vp, _vp]
 _lib.mimc3_match_ncc_full_any_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_int32, _vp, _vp, _vp, _vp]
+_lib.mimc3_wide_max_radius.argtypes = [C.c_int32]
+_lib.mimc3_wide_lds_bytes.argtypes = [C.c_int32, C.c_int32]
+_lib.mimc3_match_ncc_wide.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
+_lib.mimc3_match_ncc_wide_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          _vp, _vp, _vp, _vp]
 _lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
 _lib.mimc3_match_ncc_full_fb.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
@@ -201,6 +206,16 @@ def _check(rc, where):
 
 def version():
     return _lib.mimc3_version().decode()
+
+
+def wide_max_radius(ocw):
+    """The largest radius match_ncc_wide takes at this chip size (mimc3_wide_max_radius); 0 for an ocw it does not take."""
+    return int(_lib.mimc3_wide_max_radius(int(ocw)))
+
+
+def wide_lds_bytes(ocw, radius):
+    """The dynamic LDS (bytes) of the wide kernel's launch (mimc3_wide_lds_bytes); 0 outside 1 .. wide_max_radius(ocw)."""
+    return int(_lib.mimc3_wide_lds_bytes(int(ocw), int(radius)))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -594,6 +609,35 @@ class Context:
         _check(_lib.mimc3_match_ncc_full_any_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                                  npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
                "match_ncc_full_any_dev")
+
+    def match_ncc_wide(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False, surface=False):
+        """The exhaustive search beyond +-15 px (mimc3_match_ncc_wide): match_ncc_full_any(mode=1) with 1 <= radius <=
+        wide_max_radius(ocw) -- up to +-47 px in one exact pass at full resolution, candidates from the whole range.  radius <= 15 is
+        that call, byte for byte ("f32g_full"); radius >= 16 runs the wide kernel ("f32g_wide") -> (float32[N][8] record,
+        float32[npeaks][N][3] candidates or None when npeaks == 0), and with surface=True every point's NCC surface
+        float32[N][(2 radius + 1)^2] in k order as a third item."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        surf = np.empty((n, (2 * int(radius) + 1) ** 2), np.float32) if surface else None
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_wide: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_wide(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
+                                         None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, out,
+                                         None if cand is None else cand.ctypes.data, None if surf is None else surf.ctypes.data),
+               "match_ncc_wide")
+        return (out, cand, surf) if surface else (out, cand)
+
+    def match_ncc_wide_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, d_surf=0):
+        """Device-pointer variant (enqueue only): as match_ncc_full_any_dev; d_surf 0 = no surfaces."""
+        _check(_lib.mimc3_match_ncc_wide_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                             npeaks, 1 if swap else 0, d_out, d_cand or None, d_surf or None, stream),
+               "match_ncc_wide_dev")
 
     def match_ncc_full_fb(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, mode=0):
         """Forward-backward consistency of the exhaustive search (mimc3_match_ncc_full_fb): the forward pass is match_ncc_full_any(swap
@@ -1049,7 +1093,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

@@ -93,7 +93,7 @@ struct mimc3_ctx {
     int32_t Wp = 0;
     bool u8_ok = false;                 // both images proven to be integers in [0,255]: the u8 planes are built with the classification
     int path_mode = 0;                  // 0 auto, 1 force the general f32 kernel, 2 no integer kernels, 3 no u8 kernel, 4 auto without the matrix-core kernel
-    int last_path = -1;                 // 0 general f32/f64 kernel, 1 exact u8 kernel, ... (mimc3_hip.h), 5 matrix-core u8 kernel, 9 float search kernel
+    int last_path = -1;                 // 0 general f32/f64 kernel, 1 exact u8 kernel, ... (mimc3_hip.h), 5 matrix-core u8 kernel, 9 float search kernel, 10 wide float search kernel
     DevBuf xy, puv, poff, out;          // matcher staging for the host-buffer entry point
     DevBuf pcor, pcnt, pext;            // device pivots: corridors [N] x 24 B, counts [N], extents + total (24 B)
     hipEvent_t ev_chunk[2][8] = {};     // mimc3_match_ncc_dlc_cor: "chunk uploaded + counted" / "chunk matched"
@@ -830,8 +830,12 @@ static int full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t
                         void *stream);
 static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
                        int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream);
+static int wide_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
+                    int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, float *d_surf, void *stream,
+                    const char *entry = "mimc3_match_ncc_wide_dev");
 // (kind 3: mimc3_match_ncc_full_any -- any f32 pair, with `mode` and the optional surfaces `surf`;
-//  kind 4: mimc3_match_ncc_full_fb -- kind 3 forward (swap 0, no surfaces), then the back-match of every result into fb)
+//  kind 4: mimc3_match_ncc_full_fb -- kind 3 forward (swap 0, no surfaces), then the back-match of every result into fb;
+//  kind 5: mimc3_match_ncc_wide -- kind 3 in mode 1 with R up to mimc3_wide_max_radius(ocw))
 static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
                      int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, int kind = 0,
                      int32_t mode = 0, float *surf = nullptr, float *fb = nullptr)
@@ -840,7 +844,8 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     const std::string en(entry);
     if (!c || !xyuvav || !offset || !out || N <= 0 || (multi && !cand)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
+    if (kind == 5 ? (R < 1 || R > mimc3::wide_max_radius(ocw)) : (R < 1 || R > 15))
+        return mimc3::fail(MIMC3_EINVAL, en + (kind == 5 ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
     if (multi && (npeaks < 1 || npeaks > mimc3::kFullMaxPeaks)) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 1..8");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
     if (planes && !c->u8_ok && !c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
@@ -872,11 +877,14 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     }
     float *d_cand = multi ? static_cast<float *>(c->full_cand.p) : nullptr;
     const size_t surf_bytes = sizeof(float) * (size_t)N * (size_t)((2 * R + 1) * (2 * R + 1));
-    if (kind == 3 && surf) HIP_TRY(c->full_surf.reserve(surf_bytes));
+    if ((kind == 3 || kind == 5) && surf) HIP_TRY(c->full_surf.reserve(surf_bytes));
     const size_t fb_bytes = sizeof(float) * 4 * (size_t)(1 + npeaks) * (size_t)N;
     if (kind == 4) HIP_TRY(c->fb_out.reserve(fb_bytes));
     const int rc = kind == 4 ? full_fb_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, mode,
                                            static_cast<float *>(c->out.p), d_cand, static_cast<float *>(c->fb_out.p), c->stream)
+                   : kind == 5 ? wide_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
+                                        static_cast<float *>(c->out.p), d_cand, surf ? static_cast<float *>(c->full_surf.p) : nullptr, c->stream,
+                                        entry)
                    : kind == 3 ? full_any_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap, mode,
                                             static_cast<float *>(c->out.p), d_cand, surf ? static_cast<float *>(c->full_surf.p) : nullptr,
                                             c->stream)
@@ -890,7 +898,7 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     if (rc) return rc;
     RC_TRY(d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N));
     if (multi) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
-    if (kind == 3 && surf) RC_TRY(d2h_copy(c, surf, c->full_surf.p, surf_bytes));
+    if ((kind == 3 || kind == 5) && surf) RC_TRY(d2h_copy(c, surf, c->full_surf.p, surf_bytes));
     if (kind == 4) RC_TRY(d2h_copy(c, fb, c->fb_out.p, fb_bytes));
     return 0;
 }
@@ -1070,6 +1078,56 @@ extern "C" int mimc3_match_ncc_full_any(mimc3_ctx *c, const double *xyuvav, int3
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
     if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
     return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 3, mode, surf);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the exhaustive search beyond +-15 px (mimc3_match_ncc_wide): mimc3_match_ncc_full_any in mode 1 with R up to
+// mimc3_wide_max_radius(ocw).  R <= 15 IS that entry (the float kernel, its bytes); R >= 16 runs match_wide_kernel.hip on the same planes
+// ---------------------------------------------------------------------------------------------
+extern "C" int mimc3_wide_max_radius(int32_t ocw) { return full_ocw_ok(ocw) ? mimc3::wide_max_radius(ocw) : 0; }
+extern "C" int mimc3_wide_lds_bytes(int32_t ocw, int32_t R) { return full_ocw_ok(ocw) ? mimc3::wide_lds_bytes(ocw, R) : 0; }
+
+static int wide_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
+                    int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, float *d_surf, void *stream, const char *entry)
+{
+    // (the refusals are the _dev entry's own; the host entry has made them already, under its name, before it uploads anything)
+    const std::string en(entry);
+    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (R < 1 || R > mimc3::wide_max_radius(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..mimc3_wide_max_radius(ocw)");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
+    if (R <= 15) return full_any_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, 1, d_out, d_cand, d_surf, stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->fplanes_ok) RC_TRY(build_f32(c));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
+    u.full_shift = d_shift; u.full_R = R;
+    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
+    u.p0 = static_cast<const unsigned char *>(c->fpl0.p); u.p1 = static_cast<const unsigned char *>(c->fpl1.p);
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    const hipError_t e = mimc3::launch_match_wide(u, d_surf, s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "wide-search kernel launch");
+    c->last_path = 10;
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_match_ncc_wide_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                        const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                                        float *d_cand, float *d_surf, void *stream)
+{
+    return wide_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, d_surf, stream);
+}
+
+extern "C" int mimc3_match_ncc_wide(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                    int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand, float *surf)
+{
+    const char *en = "mimc3_match_ncc_wide";
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
+    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 5, 1, surf);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -214,6 +214,12 @@ hipError_t launch_match_full_f32(MatchU8Args a, hipStream_t stream);
 // nulls): a.p0 / a.p1 the f32 planes, no tables; surf (optional, f32 [N][(2R+1)^2]) gets every point's surface in k order; a.full_peak
 // (optional; not together with full_cand or surf) the arg-max cells, summed in the order of the record-only form.  One launch
 hipError_t launch_match_full_f32g(MatchU8Args a, float *surf, hipStream_t stream);
+// the same search over a range of up to +-47 px (match_wide_kernel.hip; mimc3_match_ncc_wide): the arguments of launch_match_full_f32g
+// without a.full_peak, a.full_R in 1 .. wide_max_radius(a.ocw) -- the largest radius whose box, chip and surface fit a CU's LDS at this
+// chip size (0 for an ocw the kernel is not built for), from the constexpr layout the launch uses.  One launch, dynamic LDS sized by a.full_R
+int wide_max_radius(int ocw);
+int wide_lds_bytes(int ocw, int R);     // the dynamic LDS of a launch at radius R (0 outside 1 .. wide_max_radius(ocw))
+hipError_t launch_match_wide(MatchU8Args a, float *surf, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all

@@ -13,7 +13,7 @@ cur = {}
 for line in p.stderr.splitlines():
     t = line.strip()
     if "Function Name:" in t:
-        cur = {"name": t.split("Function Name:")[1].strip()}
+        cur = {"name": t.split("Function Name:")[1].split()[0]}     # (the remark's own tag follows the name)
     for key, tag in (("VGPRs:", "vgpr"), ("ScratchSize", "scratch"), ("Occupancy", "occ"), ("SGPRs:", "sgpr")):
         if key in t and "name" in cur and "AGPR" not in t.split(key)[0][-3:]:
             cur.setdefault(tag, t.split(":")[-1].split("[")[0].strip())
