@@ -328,8 +328,9 @@ int mimc3_match_ncc_full_any_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t
  *   MIMC3_ESTATE.
  *   mimc3_wide_lds_bytes(ocw, R)   the dynamic LDS (bytes) of the wide kernel's launch at this chip size and radius, from the layout the
  *              launch uses (tools and documents quote it); 0 outside 1 .. mimc3_wide_max_radius(ocw).
- *   Not covered: the stack (mimc3_stack_*), mimc3_match_ncc_full_fb and the pyramid entries keep R <= 15; several GPUs; MIMC3_hip_offsets;
- *   Context.full_candidates of the Python layer. */
+ *   The stack takes this range through mimc3_stack_begin_wide, forward-backward consistency through mimc3_match_ncc_wide_fb, and
+ *   MIMC3_hip_offsets accepts R up to mimc3_wide_max_radius(ocw) at levels = 1.
+ *   Not covered: the pyramid entries keep R <= 15; several GPUs; Context.full_candidates of the Python layer. */
 int mimc3_wide_max_radius(int32_t ocw);
 int mimc3_wide_lds_bytes(int32_t ocw, int32_t R);
 int mimc3_match_ncc_wide(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
@@ -385,6 +386,22 @@ int mimc3_match_ncc_full_fb(mimc3_ctx *ctx, const double *xyuvav, int32_t N, con
 int mimc3_match_ncc_full_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                 const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t mode, float *d_out,
                                 float *d_cand, float *d_fb, void *stream);
+/* Forward-backward consistency beyond +-15 px: the text above under mimc3_match_ncc_wide's definition, 1 <= R <=
+ * mimc3_wide_max_radius(ocw).  The forward pass is mimc3_match_ncc_wide(swap = 0, surf = NULL) -- out and cand are that call's bytes --
+ * and the ONE backward pass over the (1 + npeaks) N seeded rows is mimc3_match_ncc_wide(swap = 1, offset' = -offset, shift' = -r,
+ * npeaks = 0) on the same stream; seed, compose, err and the statuses -5 / -6 / -2 / -3 / -4 are as above.  R <= 15 returns the bytes of
+ * mimc3_match_ncc_full_fb(mode 1).  mimc3_ctx_last_path reports the forward pass (10 at R >= 16, 9 below).  The backward box stays
+ * inside the 256-px zero border: it is centred on uv0, which lies in the image, and R + ocw <= 79.  A wide box holds 9.4 times the
+ * cells of a 31 x 31 one and as many more places for a decoy peak: err is the check that a peak found there is reciprocal.
+ * Refusals: those of mimc3_match_ncc_wide (the host entry checks the FORWARD bounds only); fb NULL: MIMC3_EINVAL.
+ * Not covered: as mimc3_match_ncc_full_fb. */
+int mimc3_match_ncc_wide_fb(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                            const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                            float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
+                            float *fb /*[(1 + npeaks)][N][4] host*/);
+int mimc3_match_ncc_wide_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, float *d_out, float *d_cand,
+                                float *d_fb, void *stream);
 
 /* ---- NCC stacking (ensemble matching; MIMC = Multiple Image, Multiple Chip): the correlation surfaces of several pairs that see the
  *      same motion -- a time series at equal separation, one pair at several chip sizes or after several filters -- are averaged cell by
@@ -411,11 +428,25 @@ int mimc3_match_ncc_full_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *   shift, N and R are the stack's.
  *   Consequence: a stack of ONE layer at min_count 1 returns the record and the candidates of mimc3_match_ncc_full_any(mode 1) bit for
  *   bit, because (float)((double)v / 1.0) == v.
- *   Not covered: several GPUs, the pyramid entries, MIMC3_hip_offsets, weights per layer. */
+ *   Beyond R 15 (mimc3_stack_begin_wide, 16 <= R <= 47): the same state, layout and definition; a layer from the resident pair is
+ *   mimc3_match_ncc_wide's surface, and the tail is that entry's (one workgroup per point, the candidates from up to 95 x 95 cells), so
+ *   a stack of ONE layer returns the bytes of mimc3_match_ncc_wide.  The state is 10 bytes per cell whatever R is: 18 GB at 200,000
+ *   points and R 47.
+ *   Not covered: several GPUs, the pyramid entries, MIMC3_hip_offsets, weights per layer; an accumulation fused into the wide search
+ *   (a layer beyond R 15 is written to the layer scratch and read back once). */
 #define MIMC3_STACK_CHUNK 65536
 /* Sizes and zeroes the stack and uploads shift (host [N][2], or NULL).  1 <= R <= 15.  A second call discards the first stack; N = 0
  * releases its memory (R and shift are then ignored).  A chip-atlas context: MIMC3_ESTATE.  Returns when the stack is ready. */
 int mimc3_stack_begin(mimc3_ctx *ctx, int32_t N, int32_t R, const int32_t *shift /*host [N][2] or NULL*/);
+/* mimc3_stack_begin with 1 <= R <= 47 (the largest mimc3_wide_max_radius).  With R <= 15 it leaves the context exactly as
+ * mimc3_stack_begin does.  On a stack of R >= 16: mimc3_stack_add / _add_dev take a layer that is mimc3_match_ncc_wide(npeaks 0, shift =
+ * the stack's, surf) on the resident pair, and refuse an ocw with R > mimc3_wide_max_radius(ocw) (ocw 40 on a stack of R 40..47) with
+ * MIMC3_EINVAL, before anything is enqueued; points go in chunks of mimc3_stack_chunk(R); mimc3_stack_add_surfaces takes S^2 up to 9,025
+ * cells per point; mimc3_stack_finish runs the tail of mimc3_match_ncc_wide. */
+int mimc3_stack_begin_wide(mimc3_ctx *ctx, int32_t N, int32_t R, const int32_t *shift /*host [N][2] or NULL*/);
+/* The points of one accumulation launch at radius R: MIMC3_STACK_CHUNK for 1 <= R <= 15, floor(MIMC3_STACK_CHUNK 961 / (2R+1)^2) for
+ * 16 <= R <= 47 (57,832 at R 16, 6,978 at R 47: the layer scratch never exceeds the 252 MB of R 15), 0 for any other R. */
+int32_t mimc3_stack_chunk(int32_t R);
 /* One layer from the resident pair: mimc3_match_ncc_full_any(mode 1, npeaks 0, shift = the stack's, surf) with these arguments; a point
  * is refused where that call's record has status -3.  Points go in chunks of MIMC3_STACK_CHUNK through a layer scratch of the context
  * (a buffer of its own, at most 252 MB whatever N is).  Refusals: those of mimc3_match_ncc_full_any; N differs from the stack's:

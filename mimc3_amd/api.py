@@ -71,7 +71,13 @@ _lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c
 _lib.mimc3_match_ncc_full_fb.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
 _lib.mimc3_match_ncc_full_fb_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp, _vp]
+_lib.mimc3_match_ncc_wide_fb.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
+_lib.mimc3_match_ncc_wide_fb_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp,
+                                             _vp]
 _lib.mimc3_stack_begin.argtypes = [_vp, C.c_int32, C.c_int32, _vp]
+_lib.mimc3_stack_begin_wide.argtypes = [_vp, C.c_int32, C.c_int32, _vp]
+_lib.mimc3_stack_chunk.argtypes = [C.c_int32]
+_lib.mimc3_stack_chunk.restype = C.c_int32
 _lib.mimc3_stack_add.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32]
 _lib.mimc3_stack_add_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
 _lib.mimc3_stack_add_surfaces.argtypes = [_vp, _f32p, _vp, C.c_int32]
@@ -245,6 +251,12 @@ def get_uv_pivot_counts(xyuvav, dt, mpp, ocw, H, W, aw_sf=1.8, aw_cre=10.0):
 
 CORRIDOR_BYTES = 24      # MIMC3_CORRIDOR_BYTES
 STACK_CHUNK = 65536      # MIMC3_STACK_CHUNK: the points of one launch of Context.stack_add
+
+
+def stack_chunk(radius):
+    """The points of one accumulation launch of the stack at this radius (mimc3_stack_chunk): STACK_CHUNK up to 15, fewer beyond (57,832 at
+    16, 6,978 at 47), 0 for a radius no stack takes."""
+    return int(_lib.mimc3_stack_chunk(int(radius)))
 
 
 def prior_shift(xyuvav, dt, mpp):
@@ -669,6 +681,34 @@ class Context:
                                                 npeaks, int(mode), d_out, d_cand or None, d_fb, stream),
                "match_ncc_full_fb_dev")
 
+    def match_ncc_wide_fb(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None):
+        """Forward-backward consistency beyond +-15 px (mimc3_match_ncc_wide_fb): match_ncc_full_fb under match_ncc_wide's definition, 1 <=
+        radius <= wide_max_radius(ocw) -- the forward pass is match_ncc_wide(swap False), the one backward pass match_ncc_wide(swap True)
+        over the record and the candidates of every point -> (float32[N][8] record, float32[npeaks][N][3] candidates or None when
+        npeaks == 0, float32[1 + npeaks][N][4] fb); radius <= 15 returns the bytes of match_ncc_full_fb(mode=1)."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        n = xy.shape[0]
+        npeaks = int(npeaks)
+        out = np.empty((n, 8), np.float32)
+        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        fb = np.empty((1 + max(npeaks, 0), n, 4), np.float32)
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"match_ncc_wide_fb: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_match_ncc_wide_fb(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
+                                            None if sh is None else sh.ctypes.data, ocw, radius, npeaks, out,
+                                            None if cand is None else cand.ctypes.data, fb.ctypes.data),
+               "match_ncc_wide_fb")
+        return out, cand, fb
+
+    def match_ncc_wide_fb_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_fb, d_cand=0, d_shift=0, stream=0):
+        """Device-pointer variant (enqueue only): as match_ncc_wide_dev, plus d_fb float32[1 + npeaks][n][4]."""
+        _check(_lib.mimc3_match_ncc_wide_fb_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                npeaks, d_out, d_cand or None, d_fb, stream),
+               "match_ncc_wide_fb_dev")
+
     # ---- NCC stacking (mimc3_stack_*): the surfaces of several pairs averaged per cell, the peak searched once on the mean ----
     def stack_begin(self, n, radius, shift=None):
         """Size and zero the context's stack for n grid points and search radius `radius` (1..15); shift int32[n][2] is the search shift
@@ -681,6 +721,18 @@ class Context:
             if sh.shape != (n, 2):
                 raise ValueError(f"stack_begin: shift must be int32[{n}][2], got {sh.shape}")
         _check(_lib.mimc3_stack_begin(self._h, n, int(radius), None if sh is None else sh.ctypes.data), "stack_begin")
+
+    def stack_begin_wide(self, n, radius, shift=None):
+        """stack_begin with radius 1..47 (mimc3_stack_begin_wide).  radius <= 15 leaves the context exactly as stack_begin does; on a
+        stack of radius >= 16 a layer of stack_add is match_ncc_wide's surface (an ocw with radius > wide_max_radius(ocw) is refused) and
+        stack_finish runs that entry's tail."""
+        n = int(n)
+        sh = None
+        if shift is not None and n > 0:
+            sh = np.ascontiguousarray(shift, np.int32)
+            if sh.shape != (n, 2):
+                raise ValueError(f"stack_begin_wide: shift must be int32[{n}][2], got {sh.shape}")
+        _check(_lib.mimc3_stack_begin_wide(self._h, n, int(radius), None if sh is None else sh.ctypes.data), "stack_begin_wide")
 
     def stack_add(self, xyuvav, offset, ocw, swap=False):
         """One layer from the resident pair: the surfaces of match_ncc_full_any(mode=1) with the stack's shift and radius, accumulated

@@ -829,13 +829,14 @@ static int full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t
                         int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out, float *d_cand, float *d_surf,
                         void *stream);
 static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                       int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream);
+                       int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream, bool wide = false);
 static int wide_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
                     int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, float *d_surf, void *stream,
                     const char *entry = "mimc3_match_ncc_wide_dev");
 // (kind 3: mimc3_match_ncc_full_any -- any f32 pair, with `mode` and the optional surfaces `surf`;
 //  kind 4: mimc3_match_ncc_full_fb -- kind 3 forward (swap 0, no surfaces), then the back-match of every result into fb;
-//  kind 5: mimc3_match_ncc_wide -- kind 3 in mode 1 with R up to mimc3_wide_max_radius(ocw))
+//  kind 5: mimc3_match_ncc_wide -- kind 3 in mode 1 with R up to mimc3_wide_max_radius(ocw);
+//  kind 6: mimc3_match_ncc_wide_fb -- kind 4 over kind 5)
 static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
                      int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, int kind = 0,
                      int32_t mode = 0, float *surf = nullptr, float *fb = nullptr)
@@ -844,8 +845,8 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     const std::string en(entry);
     if (!c || !xyuvav || !offset || !out || N <= 0 || (multi && !cand)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (kind == 5 ? (R < 1 || R > mimc3::wide_max_radius(ocw)) : (R < 1 || R > 15))
-        return mimc3::fail(MIMC3_EINVAL, en + (kind == 5 ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
+    if (kind >= 5 ? (R < 1 || R > mimc3::wide_max_radius(ocw)) : (R < 1 || R > 15))
+        return mimc3::fail(MIMC3_EINVAL, en + (kind >= 5 ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
     if (multi && (npeaks < 1 || npeaks > mimc3::kFullMaxPeaks)) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 1..8");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
     if (planes && !c->u8_ok && !c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
@@ -853,7 +854,7 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     if (kind == 2) RC_TRY(full_dn_class(c, en));
     if (kind >= 3 && mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
     if (kind >= 3 && c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    if (kind == 4 && !fb) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if ((kind == 4 || kind == 6) && !fb) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
     RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
     const int64_t pad = mimc3::kU8Pad;
@@ -879,9 +880,10 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     const size_t surf_bytes = sizeof(float) * (size_t)N * (size_t)((2 * R + 1) * (2 * R + 1));
     if ((kind == 3 || kind == 5) && surf) HIP_TRY(c->full_surf.reserve(surf_bytes));
     const size_t fb_bytes = sizeof(float) * 4 * (size_t)(1 + npeaks) * (size_t)N;
-    if (kind == 4) HIP_TRY(c->fb_out.reserve(fb_bytes));
-    const int rc = kind == 4 ? full_fb_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, mode,
-                                           static_cast<float *>(c->out.p), d_cand, static_cast<float *>(c->fb_out.p), c->stream)
+    if (kind == 4 || kind == 6) HIP_TRY(c->fb_out.reserve(fb_bytes));
+    const int rc = kind == 4 || kind == 6
+                       ? full_fb_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, mode,
+                                     static_cast<float *>(c->out.p), d_cand, static_cast<float *>(c->fb_out.p), c->stream, kind == 6)
                    : kind == 5 ? wide_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
                                         static_cast<float *>(c->out.p), d_cand, surf ? static_cast<float *>(c->full_surf.p) : nullptr, c->stream,
                                         entry)
@@ -899,7 +901,7 @@ static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_
     RC_TRY(d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N));
     if (multi) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
     if ((kind == 3 || kind == 5) && surf) RC_TRY(d2h_copy(c, surf, c->full_surf.p, surf_bytes));
-    if (kind == 4) RC_TRY(d2h_copy(c, fb, c->fb_out.p, fb_bytes));
+    if (kind == 4 || kind == 6) RC_TRY(d2h_copy(c, fb, c->fb_out.p, fb_bytes));
     return 0;
 }
 
@@ -1133,18 +1135,21 @@ extern "C" int mimc3_match_ncc_wide(mimc3_ctx *c, const double *xyuvav, int32_t 
 // ---------------------------------------------------------------------------------------------
 // forward-backward consistency of the exhaustive search (mimc3_match_ncc_full_fb, fb_kernel.hip): the forward pass of
 // mimc3_match_ncc_full_any, then ONE backward pass (swap 1) over the record and the candidates of every point -- (1 + npeaks) N rows,
-// seeded on the device from the forward results -- and the fb rows composed from it; all on the caller's stream, no host round trip
+// seeded on the device from the forward results -- and the fb rows composed from it; all on the caller's stream, no host round trip.
+// wide (mimc3_match_ncc_wide_fb): the same under mimc3_match_ncc_wide's definition -- both passes are wide_dev (mode 1), R up to
+// mimc3_wide_max_radius(ocw); R <= 15 is then mimc3_match_ncc_full_fb(mode 1) call for call
 // ---------------------------------------------------------------------------------------------
 static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                       int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream)
+                       int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream, bool wide)
 {
-    const std::string en("mimc3_match_ncc_full_fb_dev");
-    // mimc3_match_ncc_full_any_dev's refusals, under this entry's name and before anything is allocated
+    const std::string en(wide ? "mimc3_match_ncc_wide_fb_dev" : "mimc3_match_ncc_full_fb_dev");
+    // mimc3_match_ncc_full_any_dev's refusals (wide: mimc3_match_ncc_wide_dev's), under this entry's name and before anything is allocated
     if (!c || !d_xyuvav || !d_out || !d_fb || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
     if (mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
     if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
+    if (wide ? (R < 1 || R > mimc3::wide_max_radius(ocw)) : (R < 1 || R > 15))
+        return mimc3::fail(MIMC3_EINVAL, en + (wide ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
     if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
     const size_t rows = (size_t)(1 + npeaks) * (size_t)N;
@@ -1161,8 +1166,9 @@ static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t 
     if (c->u8_ok && mode == 0) HIP_TRY(c->mxl[0].reserve(rows));
     if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
     c->timing = false;                  // (the events bracket the whole call, not its last search)
-    // the forward pass: mimc3_match_ncc_full_any_dev itself, with its refusals
-    int rc = full_any_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, 0, mode, d_out, d_cand, nullptr, stream);
+    // the forward pass: mimc3_match_ncc_full_any_dev (wide: mimc3_match_ncc_wide_dev) itself, with its refusals
+    int rc = wide ? wide_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, 0, d_out, d_cand, nullptr, stream, en.c_str())
+                  : full_any_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, 0, mode, d_out, d_cand, nullptr, stream);
     if (rc) { c->timing = timing; return rc; }
     const int forward_path = c->last_path;
     double *xy2 = static_cast<double *>(c->fb_xy.p);
@@ -1171,8 +1177,10 @@ static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t 
     uint8_t *why = static_cast<uint8_t *>(c->fb_why.p);
     hipError_t e = mimc3::launch_fb_seed(d_xyuvav, N, off_u, off_v, d_out, d_cand, npeaks, ocw, c->H, c->W, xy2, sh2, why, s);
     if (e != hipSuccess) { c->timing = timing; return mimc3::hip_fail(e, "fb seed kernel launch"); }
-    // the backward pass: the chip from i1 at m, the search in i0 around m - offset - r = uv0 (inside the zero border: R <= 15)
-    rc = full_any_dev(c, xy2, (int32_t)rows, -off_u, -off_v, sh2, ocw, R, 0, 1, mode, back, nullptr, nullptr, stream);
+    // the backward pass: the chip from i1 at m, the search in i0 around m - offset - r = uv0 (inside the 256-px zero border: the box is
+    // centred on uv0, which lies in the image, and R + ocw <= 15 + 40; wide: R + ocw <= 47 + 32 = 79)
+    rc = wide ? wide_dev(c, xy2, (int32_t)rows, -off_u, -off_v, sh2, ocw, R, 0, 1, back, nullptr, nullptr, stream, en.c_str())
+              : full_any_dev(c, xy2, (int32_t)rows, -off_u, -off_v, sh2, ocw, R, 0, 1, mode, back, nullptr, nullptr, stream);
     c->timing = timing;
     c->last_path = forward_path;
     if (rc) return rc;
@@ -1198,6 +1206,22 @@ extern "C" int mimc3_match_ncc_full_fb(mimc3_ctx *c, const double *xyuvav, int32
     return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, 0, out, cand, npeaks > 0, en, 4, mode, nullptr, fb);
 }
 
+extern "C" int mimc3_match_ncc_wide_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                           const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, float *d_out, float *d_cand,
+                                           float *d_fb, void *stream)
+{
+    return full_fb_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, 1, d_out, d_cand, d_fb, stream, true);
+}
+
+extern "C" int mimc3_match_ncc_wide_fb(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                       int32_t ocw, int32_t R, int32_t npeaks, float *out, float *cand, float *fb)
+{
+    const char *en = "mimc3_match_ncc_wide_fb";
+    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
+    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
+    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, 0, out, cand, npeaks > 0, en, 6, 1, nullptr, fb);
+}
+
 // ---------------------------------------------------------------------------------------------
 // NCC stacking (mimc3_stack_*, stack_kernel.hip): the surfaces of several pairs -- each a mimc3_match_ncc_full_any(mode 1) layer on the
 // pair that is resident, or a caller's array -- accumulated per cell in f64, and the tail of the exhaustive search over their mean.
@@ -1213,9 +1237,10 @@ static void stack_release(mimc3_ctx *c)
 
 static inline size_t stack_cells(const mimc3_ctx *c) { return (size_t)((2 * c->stk.R + 1) * (2 * c->stk.R + 1)); }
 
-extern "C" int mimc3_stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift)
+// (max_R 15: mimc3_stack_begin; 47: mimc3_stack_begin_wide -- one text, so a stack of R <= 15 is the same state through either)
+static int stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift, int max_R, const char *entry)
 {
-    const std::string en("mimc3_stack_begin");
+    const std::string en(entry);
     if (!c || N < 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
     HIP_TRY(hipSetDevice(c->device));
@@ -1224,7 +1249,7 @@ extern "C" int mimc3_stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32
         stack_release(c);
         return 0;
     }
-    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
+    if (R < 1 || R > max_R) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1.." + std::to_string(max_R));
     auto &k = c->stk;
     k.N = 0; k.R = 0; k.layers = 0;                             // (no stack while this one is being sized)
     const size_t NC = (size_t)((2 * R + 1) * (2 * R + 1)), cells = (size_t)N * NC;
@@ -1247,6 +1272,18 @@ extern "C" int mimc3_stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32
     return 0;
 }
 
+extern "C" int mimc3_stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift)
+{
+    return stack_begin(c, N, R, shift, 15, "mimc3_stack_begin");
+}
+
+extern "C" int mimc3_stack_begin_wide(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift)
+{
+    return stack_begin(c, N, R, shift, mimc3::kStackMaxRadius, "mimc3_stack_begin_wide");
+}
+
+extern "C" int32_t mimc3_stack_chunk(int32_t R) { return mimc3::stack_chunk(R); }
+
 extern "C" int mimc3_stack_info(mimc3_ctx *c, int32_t *N, int32_t *R, int32_t *layers)
 {
     if (!c) return mimc3::fail(MIMC3_EINVAL, "mimc3_stack_info: bad argument");
@@ -1266,6 +1303,14 @@ static int stack_add_state(mimc3_ctx *c, int32_t N, const std::string &en)
     return 0;
 }
 
+// a layer of a stack beyond R 15 is mimc3_match_ncc_wide's: the chip size must take the stack's radius (ocw is one of the six)
+static int stack_add_radius(mimc3_ctx *c, int32_t ocw, const std::string &en)
+{
+    if (c->stk.R > 15 && c->stk.R > mimc3::wide_max_radius(ocw))
+        return mimc3::fail(MIMC3_EINVAL, en + ": the stack's R exceeds mimc3_wide_max_radius(ocw)");
+    return 0;
+}
+
 static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
                          void *stream, const char *entry)
 {
@@ -1275,9 +1320,10 @@ static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_
     if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
     RC_TRY(stack_add_state(c, N, en));
+    RC_TRY(stack_add_radius(c, ocw, en));
     auto &k = c->stk;
     const size_t NC = stack_cells(c);
-    const size_t chunk = (size_t)(N < mimc3::kStackChunk ? N : mimc3::kStackChunk);
+    const size_t chunk = (size_t)(N < mimc3::stack_chunk(k.R) ? N : mimc3::stack_chunk(k.R));
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NC));
@@ -1289,8 +1335,10 @@ static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_
     float *layer = static_cast<float *>(k.layer.p), *rec = static_cast<float *>(k.rec.p);
     for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
         const int32_t n = (int32_t)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
-        const int rc = full_any_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, static_cast<const int32_t *>(k.shift.p) + 2 * g0, ocw, k.R, 0, swap,
-                                    1, rec, nullptr, layer, stream);
+        // (beyond R 15 the layer is mimc3_match_ncc_wide's, through the path that entry takes)
+        const int32_t *sh = static_cast<const int32_t *>(k.shift.p) + 2 * g0;
+        const int rc = k.R > 15 ? wide_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, sh, ocw, k.R, 0, swap, rec, nullptr, layer, stream, entry)
+                                : full_any_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, sh, ocw, k.R, 0, swap, 1, rec, nullptr, layer, stream);
         if (rc) { c->timing = timing; return rc; }
         const hipError_t e = mimc3::launch_stack_add(layer, rec, nullptr, n, (int)NC, static_cast<double *>(k.sum.p) + g0 * NC,
                                                      static_cast<uint16_t *>(k.cnt.p) + g0 * NC, static_cast<uint16_t *>(k.lay.p) + g0, s);
@@ -1316,6 +1364,7 @@ extern "C" int mimc3_stack_add(mimc3_ctx *c, const double *xyuvav, int32_t N, co
     if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
     if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
     RC_TRY(stack_add_state(c, N, en));
+    RC_TRY(stack_add_radius(c, ocw, en));
     // the chip inside the image, the search box inside the planes' zero border (as mimc3_match_ncc_full_any's host entry)
     RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
     const int64_t pad = mimc3::kU8Pad, h = c->stk.R + ocw;
@@ -1340,7 +1389,7 @@ extern "C" int mimc3_stack_add_surfaces_dev(mimc3_ctx *c, const float *d_surf, c
     if (!c || !d_surf || N <= 0 || (reinterpret_cast<uintptr_t>(d_surf) & 3u)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
     RC_TRY(stack_add_state(c, N, en));
     auto &k = c->stk;
-    const size_t NC = stack_cells(c), chunk = (size_t)mimc3::kStackChunk;
+    const size_t NC = stack_cells(c), chunk = (size_t)mimc3::stack_chunk(k.R);
     HIP_TRY(hipSetDevice(c->device));
     for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
         const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
@@ -1360,7 +1409,7 @@ extern "C" int mimc3_stack_add_surfaces(mimc3_ctx *c, const float *surf, const u
     RC_TRY(stack_add_state(c, N, en));
     auto &k = c->stk;
     const size_t NC = stack_cells(c);
-    const size_t chunk = (size_t)(N < mimc3::kStackChunk ? N : mimc3::kStackChunk);
+    const size_t chunk = (size_t)(N < mimc3::stack_chunk(k.R) ? N : mimc3::stack_chunk(k.R));
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NC));
     if (refused) {

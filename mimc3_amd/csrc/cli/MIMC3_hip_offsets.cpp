@@ -6,7 +6,7 @@
 // Inputs as for MIMC3_hip (the file names start with YYYYMMDDhhmmss; dt from the two timestamps); both images 8-bit, or both 16-bit
 // (see below).  Steps: the
 // control-point offset (mimc3_vmap_cp, as the reference program measures it), the a-priori shift of every grid point
-// (mimc3_prior_shift), then every offset in [-R, R]^2 around uv0 + offset + shift (mimc3_match_ncc_full), or -- levels > 1 -- the
+// (mimc3_prior_shift), then every offset in [-R, R]^2 around uv0 + offset + shift (mimc3_match_ncc_full; R > 15: see below), or -- levels > 1 -- the
 // coarse-to-fine search that starts there on a pair reduced levels - 1 times (mimc3_match_ncc_pyramid: a reach of about
 // R (2^levels - 1) px).  Outputs in <outdir>:
 //   offsets_<t0>_<t1>.GMA  f32 [N][10]: the [N][8] record of mimc3_match_ncc_full / _pyramid (du, dv, ncc_peak / status, ncc_fit, snr,
@@ -28,6 +28,9 @@
 //   record and candidate matched back from where it landed) is also written, as fb_<t0>_<t1>.GMA (fb_<t0>_<t1>_f<k>.GMA with a filter): f32
 //   [(1 + K) N][4], plane-major, K = 0 for peaks = 1 and peaks otherwise -- row p N + i = (du_b, dv_b, ncc_b or status, err) of grid
 //   point i's record (p = 0) or candidate p - 1.  fb = 0 writes exactly the files of a run without the argument
+// R = 16 .. mimc3_wide_max_radius(ocw) (47; 39 at ocw 40; with levels = 1 only): one exact pass over the whole range
+//   (mimc3_match_ncc_wide, with fb = 1 mimc3_match_ncc_wide_fb) on 8-bit and 16-bit pairs, raw or filtered; the same files, peaks and
+//   filter as above.  R <= 15 takes exactly the calls of a build without this range and writes the same bytes
 // Environment: MIMC3_HIP_DEVICE (default 0), MIMC3_CP_SEED (as for MIMC3_hip).
 #include <cstdint>
 #include <cstdio>
@@ -63,6 +66,16 @@ int main(int argc, char *argv[])
     if (peaks != 1 && levels != 1) {
         fprintf(stderr, "peaks > 1 needs levels = 1: candidates on a pyramid's level 0 are not supported\n");
         return 2;
+    }
+    const bool wide = R > 15;               // beyond +-15 px: the wide entries, whatever the pixel class
+    if (wide) {
+        const int32_t max_r = mimc3_wide_max_radius(ocw);
+        if (max_r == 0) { fprintf(stderr, "R > 15 needs ocw one of 7, 15, 16, 30, 32, 40\n"); return 2; }
+        if (R > max_r) { fprintf(stderr, "R must be at most %d at ocw %d (mimc3_wide_max_radius)\n", max_r, ocw); return 2; }
+        if (levels != 1) {
+            fprintf(stderr, "R > 15 needs levels = 1: the coarse-to-fine search keeps R <= 15 on every level\n");
+            return 2;
+        }
     }
     char t0[15], t1[15];
     if (!timestamp_of(argv[1], t0) || !timestamp_of(argv[2], t1)) {
@@ -124,8 +137,13 @@ int main(int argc, char *argv[])
     const int32_t K = peaks != 1 ? (peaks > 0 ? peaks : 0) : 0;
     std::vector<float> fb(fbk ? 4 * (size_t)(1 + K) * (size_t)N : 0);
     if (fbk) printf("forward-backward consistency of every result\n");
+    if (wide) printf("one exact pass over +-%d px\n", R);
     if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
-        (fbk ? mimc3_match_ncc_full_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
+        (wide ? (fbk ? mimc3_match_ncc_wide_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, rec.data(),
+                                               K > 0 ? cand.data() : nullptr, fb.data())
+                     : mimc3_match_ncc_wide(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
+                                            K > 0 ? cand.data() : nullptr, nullptr))
+         : fbk ? mimc3_match_ncc_full_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
                                        K > 0 ? cand.data() : nullptr, fb.data())
          : dn16 ? mimc3_match_ncc_full_dn(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
                                         peaks != 1 ? cand.data() : nullptr)

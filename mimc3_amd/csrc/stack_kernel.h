@@ -6,9 +6,20 @@
 
 namespace mimc3 {
 
-constexpr int kStackChunk = 65536;      // MIMC3_STACK_CHUNK: the points of one launch of the accumulation
+constexpr int kStackChunk = 65536;      // MIMC3_STACK_CHUNK: the points of one launch of the accumulation (R <= 15)
+constexpr int kStackMaxRadius = 47;     // the largest mimc3_wide_max_radius: a 95 x 95 surface
+constexpr int64_t kStackChunkCells = (int64_t)kStackChunk * 961;      // the cells of one launch: what a chunk holds at R 15
 
-// One layer over n <= kStackChunk points, NC = (2R+1)^2 cells each, in the surface's k order: for every cell of surf [n][NC] that is
+// mimc3_stack_chunk: the points of one launch of the accumulation at radius R -- kStackChunk up to R 15, beyond it as many as keep the
+// launch's cells at kStackChunkCells (the layer scratch stays at 252 MB, n NC below 2^26 for stack_add_kernel's 32-bit indices);
+// 0 for an R that no stack takes
+constexpr int stack_chunk(int R)
+{
+    return R < 1 || R > kStackMaxRadius ? 0 : R <= 15 ? kStackChunk : (int)(kStackChunkCells / ((2 * R + 1) * (2 * R + 1)));
+}
+static_assert(stack_chunk(16) == 57832 && stack_chunk(47) == 6978, "mimc3_hip.h quotes these");
+
+// One layer over n <= stack_chunk(R) points, NC = (2R+1)^2 <= 9,025 cells each, in the surface's k order: for every cell of surf [n][NC] that is
 // finite, sum += (double)v and cnt += 1 (NaN and +-Inf add nothing); for every point that is not refused, lay += 1.  A point is refused
 // when rec (the search's records [n][8], or null) has -3 in column 2, or when refused ([n], or null) is not 0; with both null no point is.
 // sum, cnt and lay point at the first of the n points.  One lane owns a cell: plain read-modify-writes, no atomics.  surf needs no
@@ -18,7 +29,7 @@ hipError_t launch_stack_add(const float *surf, const float *rec, const uint8_t *
 
 // The result over all N points: mean[k] = (float)(sum[k] / (double)cnt[k]) where cnt[k] >= min_count (>= 1), NaN elsewhere; a point with
 // lay == 0 gets status -3 in its record and every candidate slot, any other the tail of match_full_tail.h over mean with shift [N][2]
-// (or null).  out [N][8]; cand [npeaks][N][3], null iff npeaks == 0; surf [N][NC] (mean) and count [N] (lay) optional.  Reads the stack
+// (or null).  R <= 15: one wave per point; 16 <= R <= kStackMaxRadius: one workgroup per point, the candidates by match_wide_tail.h.  out [N][8]; cand [npeaks][N][3], null iff npeaks == 0; surf [N][NC] (mean) and count [N] (lay) optional.  Reads the stack
 // and leaves it unchanged.
 hipError_t launch_stack_tail(const double *sum, const uint16_t *cnt, const uint16_t *lay, const int32_t *shift, int N, int R, int npeaks,
                              int min_count, float *out, float *cand, float *surf, uint16_t *count, hipStream_t s);

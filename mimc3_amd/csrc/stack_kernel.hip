@@ -1,8 +1,10 @@
 // stack_kernel.hip -- NCC stacking (mimc3_stack_*; stack_kernel.h): stack_add_kernel accumulates one layer of surfaces into the stack's
 // f64 sums and u16 counts, stack_tail_kernel forms the mean surface of every point in LDS and hands it to the tail every front of the
-// exhaustive search shares (match_full_tail.h, unmodified: the record and the candidates of a stack are that text's).
+// exhaustive search shares (match_full_tail.h, unmodified: the record and the candidates of a stack are that text's).  Beyond R 15
+// stack_tail_wide_kernel does the same with one workgroup per point and the candidate tail of match_wide_tail.h, unmodified as well.
 #include "stack_kernel.h"
 #include "match_full_tail.h"
+#include "match_wide_tail.h"
 
 namespace mimc3 {
 
@@ -103,14 +105,69 @@ __global__ __launch_bounds__(64 * kStackWaves) void stack_tail_kernel(MatchU8Arg
     if constexpr (MULTI) mx::full_tail_multi<C>(p, val, gidx, shu, shv, lane);
 }
 
+// ---- the result beyond R 15: one workgroup of four wave64 per point --------------------------------------------------------------
+// A surface of up to 95 x 95 cells does not fit a wave's share of LDS four times over, and its candidate tail (match_wide_tail.h) wants
+// every wave of the workgroup for the bit plane.  The configuration is the one match_wide_kernel.hip hands the two tails: pitch 96,
+// 256 threads.  Dynamic LDS, sized by R at the launch: the bit plane (kWideLmBytes), then S rows of VP words -- 37,760 bytes at S = 95,
+// 13,952 at S = 33 (four and eleven workgroups per CU by LDS; the kernel streams 10 bytes per cell and is expected to follow that).
+template <bool MULTI_>
+struct StackWideCfg {
+    static constexpr int VP = 96, NT = 256;
+    static constexpr bool PEAK = false, MULTI = MULTI_;
+    static constexpr int lds_bytes(int R) { return mx::kWideLmBytes + (2 * R + 1) * VP * 4; }
+};
+static_assert(mx::kWideLmBytes % 16 == 0, "the surface behind the bit plane stays 16-byte aligned");
+static_assert(2 * kStackMaxRadius + 1 < StackWideCfg<false>::VP, "the surface pitch");
+static_assert((2 * kStackMaxRadius + 1) * (2 * kStackMaxRadius + 1) <= 64 * 32 * mx::kWideLmWords, "the bit plane of the candidate tail");
+
+template <bool MULTI>
+__global__ __launch_bounds__(StackWideCfg<MULTI>::NT) void stack_tail_wide_kernel(MatchU8Args p, const double *__restrict__ sum,
+                                                                                  const uint16_t *__restrict__ cnt,
+                                                                                  const uint16_t *__restrict__ lay, int min_count,
+                                                                                  float *__restrict__ surf, uint16_t *__restrict__ count)
+{
+    using C = StackWideCfg<MULTI>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char stack_smem[];
+    uint32_t *bits = reinterpret_cast<uint32_t *>(stack_smem);
+    float *val = reinterpret_cast<float *>(stack_smem + mx::kWideLmBytes);       // val[y * VP + x], x, y <= 94
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int gidx = blockIdx.x;                                 // the grid is N workgroups
+    const int R = p.full_R, S = 2 * R + 1, NC = S * S;
+    const int layers = lay[gidx];
+    if (count && tid == 0) count[gidx] = (uint16_t)layers;
+    const size_t base = (size_t)gidx * (size_t)NC;
+    for (int k = tid; k < NC; k += C::NT) {                      // k contiguous over the threads: sum, cnt and surf are coalesced
+        const int c = cnt[base + k];
+        const float m = c >= min_count ? (float)(sum[base + k] / (double)c) : __builtin_nanf("");     // f64 division, rounded once
+        const int x = k / S, y = k - S * x;
+        val[y * C::VP + x] = m;
+        if (surf) surf[base + k] = m;
+    }
+    if (layers == 0) {                  // (uniform over the workgroup: nobody waits at a barrier below)
+        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, -3.0f); mx::full_cand_fill<C>(p, gidx, -3.0f); }
+        return;
+    }
+    __syncthreads();                    // the surface is in LDS before any tail reads it
+    if constexpr (MULTI) {
+        mx::wide_lm_plane<C>(p, val, bits, tid);
+        __syncthreads();
+    }
+    if (wave != 0) return;
+    const int shu = p.full_shift ? p.full_shift[2 * (size_t)gidx] : 0, shv = p.full_shift ? p.full_shift[2 * (size_t)gidx + 1] : 0;
+    mx::full_tail<C>(p, val, gidx, shu, shv, lane);
+    if constexpr (MULTI) mx::wide_tail_multi<C>(p, val, bits, gidx, shu, shv, lane);
+}
+
 }  // namespace
 
 hipError_t launch_stack_add(const float *surf, const float *rec, const uint8_t *refused, int n, int NC, double *sum, uint16_t *cnt,
                             uint16_t *lay, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    if (!surf || !sum || !cnt || !lay || n > kStackChunk || NC < 9 || NC > 961) return hipErrorInvalidValue;
-    const uint32_t total = (uint32_t)n * (uint32_t)NC;            // <= 65536 * 961 < 2^26
+    constexpr int kMaxNC = (2 * kStackMaxRadius + 1) * (2 * kStackMaxRadius + 1);
+    if (!surf || !sum || !cnt || !lay || n > kStackChunk || NC < 9 || NC > kMaxNC || (int64_t)n * NC > kStackChunkCells)
+        return hipErrorInvalidValue;
+    const uint32_t total = (uint32_t)n * (uint32_t)NC;            // <= 65536 * 961 < 2^26 (stack_chunk)
     uint32_t head = (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(surf) & 15u)) & 15u) / 4u;
     if (reinterpret_cast<uintptr_t>(surf) & 3u) return hipErrorInvalidValue;
     if (head > total) head = total;
@@ -126,12 +183,18 @@ hipError_t launch_stack_tail(const double *sum, const uint16_t *cnt, const uint1
                              int min_count, float *out, float *cand, float *surf, uint16_t *count, hipStream_t s)
 {
     if (N <= 0) return hipSuccess;
-    if (!sum || !cnt || !lay || !out || R < 1 || R > 15 || min_count < 1 || npeaks < 0 || npeaks > kFullMaxPeaks ||
+    if (!sum || !cnt || !lay || !out || R < 1 || R > kStackMaxRadius || min_count < 1 || npeaks < 0 || npeaks > kFullMaxPeaks ||
         (npeaks > 0) != (cand != nullptr))
         return hipErrorInvalidValue;
     MatchU8Args a{};
     a.out = out; a.N = N; a.full_R = R; a.full_shift = shift;
     if (cand) { a.full_cand = cand; a.full_npeaks = npeaks; }
+    if (R > 15) {
+        const int lds = StackWideCfg<false>::lds_bytes(R);       // (below the default limit of dynamic LDS: no attribute to set)
+        if (cand) hipLaunchKernelGGL(stack_tail_wide_kernel<true>, dim3((unsigned)N), dim3(256), lds, s, a, sum, cnt, lay, min_count, surf, count);
+        else hipLaunchKernelGGL(stack_tail_wide_kernel<false>, dim3((unsigned)N), dim3(256), lds, s, a, sum, cnt, lay, min_count, surf, count);
+        return hipGetLastError();
+    }
     const unsigned nb = (unsigned)(((size_t)N + kStackWaves - 1) / kStackWaves);
     if (cand) hipLaunchKernelGGL(stack_tail_kernel<true>, dim3(nb), dim3(64 * kStackWaves), 0, s, a, sum, cnt, lay, min_count, surf, count);
     else hipLaunchKernelGGL(stack_tail_kernel<false>, dim3(nb), dim3(64 * kStackWaves), 0, s, a, sum, cnt, lay, min_count, surf, count);
