@@ -404,7 +404,8 @@ int mimc3_match_ncc_wide_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
                                 float *d_fb, void *stream);
 
 /* ---- NCC stacking (ensemble matching; MIMC = Multiple Image, Multiple Chip): the correlation surfaces of several pairs that see the
- *      same motion -- a time series at equal separation, one pair at several chip sizes or after several filters -- are averaged cell by
+ *      same motion -- a time series at equal separation, one pair at several chip sizes or after several filters; pairs of other
+ *      separations through the scaled layers below -- are averaged cell by
  *      cell, and the peak is searched ONCE, on the mean surface.  Noise peaks do not repeat from layer to layer, the true peak does.
  *
  *   The stack is state of one context, and it outlives the pair: mimc3_ctx_set_images* and mimc3_ctx_filter_images do not touch it.
@@ -432,8 +433,44 @@ int mimc3_match_ncc_wide_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *   mimc3_match_ncc_wide's surface, and the tail is that entry's (one workgroup per point, the candidates from up to 95 x 95 cells), so
  *   a stack of ONE layer returns the bytes of mimc3_match_ncc_wide.  The state is 10 bytes per cell whatever R is: 18 GB at 200,000
  *   points and R 47.
- *   Not covered: several GPUs, the pyramid entries, MIMC3_hip_offsets, weights per layer; an accumulation fused into the wide search
- *   (a layer beyond R 15 is written to the layer scratch and read back once). */
+ *   Not covered: several GPUs, the pyramid entries, MIMC3_hip_offsets; an accumulation fused into the search (a layer beyond R 15, and
+ *   every scaled layer, is written to the layer scratch and read back once).
+ *
+ *   Layers of another time baseline: scaled and weighted (mimc3_stack_add_scaled, mimc3_stack_add_surfaces_scaled).  Pairs of different
+ *   separation share a velocity, not a displacement: what moved d px in the stack's interval moved s d px in a pair s times as long.
+ *   A scaled layer has
+ *     a scale s (f64: the layer's time separation over the stack's), finite, 2^-6 <= s <= 2^6;
+ *     a weight w (f64), finite, > 0;
+ *     a layer radius Rl, Sl = 2 Rl + 1;
+ *     surfaces L [N][Sl^2] in k order, k = ju Sl + jv, ju, jv in 0..2 Rl;   a flag refused [N].
+ *   The layer was searched around the layer shift, once per point:
+ *     Lsh[i] = ((int32)rint(s * (double)shift[i][0]), (int32)rint(s * (double)shift[i][1]))
+ *   -- the product is f64, rint rounds half to even; |s * shift| >= 2^30 is refused with MIMC3_EINVAL by every entry (the context keeps a
+ *   host copy of the shift).  Every operation below is a single f64 operation, rounded, in the order written (the library is built
+ *   with -ffp-contract=off: nothing fuses).  For stack cell (su, sv) in [-R, R]^2 of point i:
+ *     pu = s * (double)(shift[i][0] + su) - (double)Lsh[i][0]      fu = floor(pu)   au = pu - fu   ju = (int)fu + Rl
+ *     pv = s * (double)(shift[i][1] + sv) - (double)Lsh[i][1]      fv = floor(pv)   av = pv - fv   jv = (int)fv + Rl
+ *     row(j) = av == 0 ? (double)L[j][jv]  : (1 - av) * (double)L[j][jv] + av * (double)L[j][jv + 1]
+ *     value  = au == 0 ? row(ju)           : (1 - au) * row(ju)          + au * row(ju + 1)
+ *   A tap with weight zero is NOT read: at au == 0 the row ju + 1 is not read, at av == 0 the column jv + 1 is not read; such a tap
+ *   may be NaN or lie outside the layer.  The cell is finite when every tap that is read lies inside 0..2 Rl on both axes and value is
+ *   finite.
+ *     a finite cell:   sum += w * value (one product, one addition), cnt += 1, wsum += w;   any other cell adds nothing;
+ *     every point:     not refused: lay += 1;
+ *     layers += 1.
+ *   The order of the adds is part of the definition, as above.
+ *   wsum is a third per-cell plane, f64 [N][S^2], and it exists only on a WEIGHTED stack: the first add whose w != 1.0 allocates it and
+ *   initialises it to (double)cnt (one elementwise kernel, enqueued on that add's stream before the add); from then on every add of
+ *   either kind maintains it -- mimc3_stack_add and mimc3_stack_add_surfaces add 1.0.  mimc3_stack_begin* and the release forget it.
+ *   Mean surface:  (float)(sum / wsum) on a weighted stack, (float)(sum / (double)cnt) otherwise; where cnt >= min_count, NaN elsewhere.
+ *   The state is 10 bytes per cell until the first weighted add, then 18.
+ *   Consequences:
+ *     s == 1, w == 1, Rl == R:  pu, pv are integers ((double)(shift + su) - (double)shift is exact), every cell is one tap, value ==
+ *       (double)v, and the stack's bytes are those of mimc3_stack_add / mimc3_stack_add_surfaces.
+ *     every layer at the same power-of-two weight:  sum and wsum are the unweighted sum and cnt times that power, exactly, and the mean
+ *       is the unweighted mean bit for bit.
+ *   Not covered by the scaled layers: several GPUs, the pyramid entries, forward-backward, MIMC3_hip_offsets, and fusing the
+ *   accumulation into the search. */
 #define MIMC3_STACK_CHUNK 65536
 /* Sizes and zeroes the stack and uploads shift (host [N][2], or NULL).  1 <= R <= 15.  A second call discards the first stack; N = 0
  * releases its memory (R and shift are then ignored).  A chip-atlas context: MIMC3_ESTATE.  Returns when the stack is ready. */
@@ -472,6 +509,35 @@ int mimc3_stack_finish_dev(mimc3_ctx *ctx, int32_t npeaks, int32_t min_count, fl
                            uint16_t *d_count, void *stream);
 /* N, R and the number of layers added (each may be NULL); all 0 when the context has no stack. */
 int mimc3_stack_info(mimc3_ctx *ctx, int32_t *N, int32_t *R, int32_t *layers);
+/* The smallest layer radius that serves every cell of a stack of radius R at this scale, whatever the shift: R when scale == 1, else
+ * (int32_t)floor(scale R + 0.5) + 1 -- a stack cell su lands at pu = s su + (s sh - rint(s sh)), and |s sh - rint(s sh)| <= 0.5, so
+ * |pu| <= s R + 0.5 and the taps floor(pu), floor(pu) + 1 lie within floor(s R + 0.5) + 1 of the layer's centre.  0 for R outside 1..47
+ * or a scale outside 2^-6..2^6.  The result may exceed 47 (or mimc3_wide_max_radius(ocw)): the caller then passes a smaller layer_R, and
+ * the outer cells of the stack get no count from that layer -- count, cnt and min_count express that. */
+int32_t mimc3_stack_layer_radius(int32_t R, double scale);
+/* Lsh of the definition, from the stack's host shift.  No stack: MIMC3_ESTATE; a bad scale or |scale shift| >= 2^30: MIMC3_EINVAL. */
+int mimc3_stack_layer_shift(mimc3_ctx *ctx, double scale, int32_t *out /*host [N][2]*/);
+/* 1 when the context's stack is weighted (it has a wsum plane), else 0. */
+int mimc3_stack_weighted(mimc3_ctx *ctx);
+/* One scaled layer from the resident pair: mimc3_match_ncc_wide(npeaks 0, shift = Lsh, R = layer_R, surf) with these arguments (the
+ * float kernel up to layer_R 15, the wide kernel beyond), resampled into the stack by the definition above; a point is refused where
+ * that call's record has status -3.  1 <= layer_R <= mimc3_wide_max_radius(ocw), whatever the stack's R (1..47, begun by either
+ * mimc3_stack_begin or _begin_wide).  Points go in chunks of min(mimc3_stack_chunk(R), mimc3_stack_chunk(layer_R)) through the layer
+ * scratch.  The host entry checks the chips and the layer's box (layer_R + ocw around uv0 + offset + Lsh) against the zero border as
+ * mimc3_stack_add does: MIMC3_EBOUNDS.  A bad scale, weight or layer_R, |scale shift| >= 2^30, N differs: MIMC3_EINVAL; no stack, no
+ * images, 65,535 layers: MIMC3_ESTATE.  Everything is validated before the first launch or allocation that touches the stack: a refused
+ * add leaves the stack's bytes, and whether it is weighted, as they were. */
+int mimc3_stack_add_scaled(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t layer_R,
+                           int32_t swap, double scale, double weight);
+/* Device-resident variant, under the contract of mimc3_stack_add_dev. */
+int mimc3_stack_add_scaled_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
+                               int32_t layer_R, int32_t swap, double scale, double weight, void *stream);
+/* One scaled layer from the caller's surfaces, which the caller searched around mimc3_stack_layer_shift: surf [N][Sl^2] in k order,
+ * 1 <= layer_R <= 47, refused [N] or NULL.  Refusals: as above, without those of the search. */
+int mimc3_stack_add_surfaces_scaled(mimc3_ctx *ctx, const float *surf /*host [N][Sl^2]*/, const uint8_t *refused /*host [N] or NULL*/,
+                                    int32_t N, int32_t layer_R, double scale, double weight);
+int mimc3_stack_add_surfaces_scaled_dev(mimc3_ctx *ctx, const float *d_surf, const uint8_t *d_refused, int32_t N, int32_t layer_R,
+                                        double scale, double weight, void *stream);
 
 /* ---- Coarse-to-fine exhaustive search over an image pyramid (no reference counterpart: the reach of mimc3_match_ncc_full, +-R
  *      around uv0 + offset + shift, made about R (2^L - 1) px by searching a reduced pair first -- the offset trackers' standard).

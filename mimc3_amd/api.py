@@ -85,6 +85,15 @@ _lib.mimc3_stack_add_surfaces_dev.argtypes = [_vp, _vp, _vp, C.c_int32, _vp]
 _lib.mimc3_stack_finish.argtypes = [_vp, C.c_int32, C.c_int32, _f32p, _vp, _vp, _vp]
 _lib.mimc3_stack_finish_dev.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]
 _lib.mimc3_stack_info.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+_lib.mimc3_stack_layer_radius.argtypes = [C.c_int32, C.c_double]
+_lib.mimc3_stack_layer_radius.restype = C.c_int32
+_lib.mimc3_stack_layer_shift.argtypes = [_vp, C.c_double, _i32p]
+_lib.mimc3_stack_weighted.argtypes = [_vp]
+_lib.mimc3_stack_add_scaled.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double]
+_lib.mimc3_stack_add_scaled_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                            C.c_double, _vp]
+_lib.mimc3_stack_add_surfaces_scaled.argtypes = [_vp, _f32p, _vp, C.c_int32, C.c_int32, C.c_double, C.c_double]
+_lib.mimc3_stack_add_surfaces_scaled_dev.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_double, _vp]
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
 _lib.mimc3_match_ncc_pyramid_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
@@ -257,6 +266,13 @@ def stack_chunk(radius):
     """The points of one accumulation launch of the stack at this radius (mimc3_stack_chunk): STACK_CHUNK up to 15, fewer beyond (57,832 at
     16, 6,978 at 47), 0 for a radius no stack takes."""
     return int(_lib.mimc3_stack_chunk(int(radius)))
+
+
+def stack_layer_radius(radius, scale):
+    """The smallest layer radius that serves every cell of a stack of this radius from a layer at `scale` (mimc3_stack_layer_radius):
+    radius at scale 1, else floor(scale radius + 0.5) + 1; 0 for a radius outside 1..47 or a scale outside 1/64..64.  May exceed what a
+    search takes (wide_max_radius(ocw)): pass a smaller radius then, and the stack's outer cells get no count from that layer."""
+    return int(_lib.mimc3_stack_layer_radius(int(radius), float(scale)))
 
 
 def prior_shift(xyuvav, dt, mpp):
@@ -762,6 +778,61 @@ class Context:
     def stack_add_surfaces_dev(self, d_surf, n, d_refused=0, stream=0):
         """Device-pointer variant (enqueue only): d_surf float32[n][cells], d_refused uint8[n] or 0."""
         _check(_lib.mimc3_stack_add_surfaces_dev(self._h, d_surf, d_refused or None, n, stream), "stack_add_surfaces_dev")
+
+    # ---- layers of another time baseline: a pair `scale` times as long as the stack's moved scale x as far ----
+    def stack_layer_shift(self, scale):
+        """int32[n][2]: the shift a layer at `scale` is searched around, rint(scale * the stack's shift) (mimc3_stack_layer_shift)."""
+        out = np.empty((self.stack_info()[0], 2), np.int32)
+        _check(_lib.mimc3_stack_layer_shift(self._h, float(scale), out), "stack_layer_shift")
+        return out
+
+    def stack_weighted(self):
+        """True once a layer with a weight other than 1 was added: the stack then keeps the weights' sum per cell (18 bytes per cell)."""
+        return bool(_lib.mimc3_stack_weighted(self._h))
+
+    def _scaled_radius(self, what, scale, radius, ocw):
+        if radius is not None:
+            return int(radius)
+        r = stack_layer_radius(self.stack_info()[1], scale)
+        if r > wide_max_radius(ocw):
+            raise ValueError(f"{what}: scale {scale} wants a layer radius of {r}, beyond wide_max_radius({ocw}) = {wide_max_radius(ocw)}: "
+                             f"pass a radius explicitly (the stack's outer cells then get no count from this layer)")
+        return r
+
+    def stack_add_scaled(self, xyuvav, offset, ocw, scale, weight=1.0, radius=None, swap=False):
+        """One layer from the resident pair, whose time separation is `scale` times the stack's: match_ncc_wide's surfaces at `radius`
+        (None: stack_layer_radius of the stack's radius) around stack_layer_shift(scale), resampled bilinearly onto the stack's cells
+        and accumulated with `weight` (mimc3_stack_add_scaled)."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        r = self._scaled_radius("stack_add_scaled", scale, radius, ocw)
+        _check(_lib.mimc3_stack_add_scaled(self._h, xy, xy.shape[0], np.ascontiguousarray(offset, np.int32), ocw, r, 1 if swap else 0,
+                                           float(scale), float(weight)), "stack_add_scaled")
+
+    def stack_add_scaled_dev(self, d_xyuvav, n, offset, ocw, scale, weight=1.0, radius=None, stream=0, swap=False):
+        """Device-pointer variant (enqueue only)."""
+        r = self._scaled_radius("stack_add_scaled_dev", scale, radius, ocw)
+        _check(_lib.mimc3_stack_add_scaled_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), ocw, r, 1 if swap else 0, float(scale),
+                                               float(weight), stream), "stack_add_scaled_dev")
+
+    def stack_add_surfaces_scaled(self, surf, radius, scale, weight=1.0, refused=None):
+        """One scaled layer from the caller's surfaces float32[n][(2 radius + 1)^2] in k order, searched around
+        stack_layer_shift(scale); refused bool[n] (None = no point is)."""
+        sf = np.ascontiguousarray(surf, np.float32)
+        radius = int(radius)
+        if sf.ndim != 2 or (1 <= radius <= 47 and sf.shape[1] != (2 * radius + 1) ** 2):
+            raise ValueError(f"stack_add_surfaces_scaled: surf must be float32[n][(2 radius + 1)^2], got {sf.shape} at radius {radius}")
+        rf = None
+        if refused is not None:
+            rf = np.ascontiguousarray(np.asarray(refused) != 0, np.uint8)
+            if rf.shape != (sf.shape[0],):
+                raise ValueError(f"stack_add_surfaces_scaled: refused must be [{sf.shape[0]}], got {rf.shape}")
+        _check(_lib.mimc3_stack_add_surfaces_scaled(self._h, sf, None if rf is None else rf.ctypes.data, sf.shape[0], radius, float(scale),
+                                                    float(weight)), "stack_add_surfaces_scaled")
+
+    def stack_add_surfaces_scaled_dev(self, d_surf, n, radius, scale, weight=1.0, d_refused=0, stream=0):
+        """Device-pointer variant (enqueue only): d_surf float32[n][(2 radius + 1)^2], d_refused uint8[n] or 0."""
+        _check(_lib.mimc3_stack_add_surfaces_scaled_dev(self._h, d_surf, d_refused or None, n, int(radius), float(scale), float(weight),
+                                                        stream), "stack_add_surfaces_scaled_dev")
 
     def stack_finish(self, npeaks=0, min_count=1, surface=False):
         """The result of the stack -> (float32[n][8] record, float32[npeaks][n][3] candidates or None when npeaks == 0, uint16[n] layers

@@ -144,9 +144,13 @@ struct mimc3_ctx {
     DevBuf fb_xy, fb_sh, fb_rec, fb_why, fb_out;
     // mimc3_stack_*: the stack (NCC surfaces accumulated over several pairs; state of its own, which the image setters never touch) --
     // sum f64 [N][S^2], cnt u16 [N][S^2], lay u16 [N], shift i32 [N][2] (zeros when none was given; a host copy for the host entry's
-    // bounds check); the layer scratch of an add (surfaces and records of one chunk of points) and the staging of the host entries
+    // bounds check); the layer scratch of an add (surfaces and records of one chunk of points) and the staging of the host entries.
+    // A weighted stack (the first add with a weight other than 1 makes it one) has wsum f64 [N][S^2] as well; lsh i32 [N][2] is the
+    // layer shift of the scaled add that is under way
     struct Stack {
         DevBuf sum, cnt, lay, shift;
+        DevBuf wsum, lsh;
+        bool weighted = false;
         DevBuf layer, rec, ref;         // one chunk: f32 [chunk][S^2], f32 [chunk][8]; the host entry's refused flags [N]
         DevBuf out, cand, surf, count;  // mimc3_stack_finish's host entry
         std::vector<int32_t> h_shift;
@@ -1230,12 +1234,18 @@ extern "C" int mimc3_match_ncc_wide_fb(mimc3_ctx *c, const double *xyuvav, int32
 static void stack_release(mimc3_ctx *c)
 {
     auto &k = c->stk;
-    for (DevBuf *b : {&k.sum, &k.cnt, &k.lay, &k.shift, &k.layer, &k.rec, &k.ref, &k.out, &k.cand, &k.surf, &k.count}) b->release();
+    for (DevBuf *b : {&k.sum, &k.cnt, &k.lay, &k.shift, &k.wsum, &k.lsh, &k.layer, &k.rec, &k.ref, &k.out, &k.cand, &k.surf, &k.count})
+        b->release();
     std::vector<int32_t>().swap(k.h_shift);
-    k.N = 0; k.R = 0; k.layers = 0;
+    k.N = 0; k.R = 0; k.layers = 0; k.weighted = false;
 }
 
 static inline size_t stack_cells(const mimc3_ctx *c) { return (size_t)((2 * c->stk.R + 1) * (2 * c->stk.R + 1)); }
+// the weights' sums from cell `cell0` on; null on a stack that is not weighted
+static inline double *stack_wsum(const mimc3_ctx *c, size_t cell0)
+{
+    return c->stk.weighted ? static_cast<double *>(c->stk.wsum.p) + cell0 : nullptr;
+}
 
 // (max_R 15: mimc3_stack_begin; 47: mimc3_stack_begin_wide -- one text, so a stack of R <= 15 is the same state through either)
 static int stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift, int max_R, const char *entry)
@@ -1252,6 +1262,11 @@ static int stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift,
     if (R < 1 || R > max_R) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1.." + std::to_string(max_R));
     auto &k = c->stk;
     k.N = 0; k.R = 0; k.layers = 0;                             // (no stack while this one is being sized)
+    if (k.weighted || k.wsum.p) {                               // the new stack is not weighted: 10 bytes per cell again
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        k.wsum.release();
+        k.weighted = false;
+    }
     const size_t NC = (size_t)((2 * R + 1) * (2 * R + 1)), cells = (size_t)N * NC;
     HIP_TRY(k.sum.reserve(sizeof(double) * cells));
     HIP_TRY(k.cnt.reserve(sizeof(uint16_t) * cells));
@@ -1341,7 +1356,8 @@ static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_
                                 : full_any_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, sh, ocw, k.R, 0, swap, 1, rec, nullptr, layer, stream);
         if (rc) { c->timing = timing; return rc; }
         const hipError_t e = mimc3::launch_stack_add(layer, rec, nullptr, n, (int)NC, static_cast<double *>(k.sum.p) + g0 * NC,
-                                                     static_cast<uint16_t *>(k.cnt.p) + g0 * NC, static_cast<uint16_t *>(k.lay.p) + g0, s);
+                                                     static_cast<uint16_t *>(k.cnt.p) + g0 * NC, static_cast<uint16_t *>(k.lay.p) + g0,
+                                                     stack_wsum(c, g0 * NC), s);
         if (e != hipSuccess) { c->timing = timing; return mimc3::hip_fail(e, "stack add kernel launch"); }
     }
     c->timing = timing;
@@ -1395,7 +1411,8 @@ extern "C" int mimc3_stack_add_surfaces_dev(mimc3_ctx *c, const float *d_surf, c
         const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
         const hipError_t e = mimc3::launch_stack_add(d_surf + g0 * NC, nullptr, d_refused ? d_refused + g0 : nullptr, n, (int)NC,
                                                      static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
-                                                     static_cast<uint16_t *>(k.lay.p) + g0, static_cast<hipStream_t>(stream));
+                                                     static_cast<uint16_t *>(k.lay.p) + g0, stack_wsum(c, g0 * NC),
+                                                     static_cast<hipStream_t>(stream));
         if (e != hipSuccess) return mimc3::hip_fail(e, "stack add kernel launch");
     }
     k.layers++;
@@ -1423,8 +1440,210 @@ extern "C" int mimc3_stack_add_surfaces(mimc3_ctx *c, const float *surf, const u
         const hipError_t e = mimc3::launch_stack_add(static_cast<const float *>(k.layer.p), nullptr,
                                                      refused ? static_cast<const uint8_t *>(k.ref.p) + g0 : nullptr, n, (int)NC,
                                                      static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
-                                                     static_cast<uint16_t *>(k.lay.p) + g0, c->stream);
+                                                     static_cast<uint16_t *>(k.lay.p) + g0, stack_wsum(c, g0 * NC), c->stream);
         if (e != hipSuccess) return mimc3::hip_fail(e, "stack add kernel launch");
+    }
+    k.layers++;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- layers of another time baseline: scaled and weighted (the definition is in include/mimc3_hip.h) ----
+static inline bool stack_scale_ok(double s) { return s >= 1.0 / 64 && s <= 64.0; }                // (false for NaN)
+static inline bool stack_weight_ok(double w) { return w > 0.0 && std::isfinite(w); }
+
+extern "C" int32_t mimc3_stack_layer_radius(int32_t R, double scale)
+{
+    if (R < 1 || R > mimc3::kStackMaxRadius || !stack_scale_ok(scale)) return 0;
+    return scale == 1.0 ? R : (int32_t)std::floor(scale * (double)R + 0.5) + 1;
+}
+
+// the layer shift of every point from the stack's host shift; MIMC3_EINVAL where |scale shift| >= 2^30.  out may be null (the check alone)
+static int stack_layer_shift(const mimc3_ctx *c, double scale, int32_t *out, const std::string &en)
+{
+    const std::vector<int32_t> &sh = c->stk.h_shift;
+    for (size_t i = 0; i < sh.size(); ++i) {
+        const double p = scale * (double)sh[i];
+        if (!(std::fabs(p) < 1073741824.0)) return mimc3::fail(MIMC3_EINVAL, en + ": |scale x shift| must be below 2^30");
+        if (out) out[i] = (int32_t)std::nearbyint(p);           // (half to even: the default rounding mode, which nothing here changes)
+    }
+    return 0;
+}
+
+// what every scaled add checks beyond its pointers, before anything is allocated or enqueued
+static int stack_scaled_check(mimc3_ctx *c, int32_t N, int32_t layer_R, int32_t max_R, double scale, double weight, const std::string &en)
+{
+    RC_TRY(stack_add_state(c, N, en));
+    if (!stack_scale_ok(scale)) return mimc3::fail(MIMC3_EINVAL, en + ": scale must be in 1/64..64");
+    if (!stack_weight_ok(weight)) return mimc3::fail(MIMC3_EINVAL, en + ": weight must be finite and > 0");
+    if (layer_R < 1 || layer_R > max_R)
+        return mimc3::fail(MIMC3_EINVAL, en + ": layer_R must be in 1.." + std::to_string(max_R));
+    return stack_layer_shift(c, scale, nullptr, en);
+}
+
+extern "C" int mimc3_stack_layer_shift(mimc3_ctx *c, double scale, int32_t *out)
+{
+    const std::string en("mimc3_stack_layer_shift");
+    if (!c || !out) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (c->stk.N == 0) return mimc3::fail(MIMC3_ESTATE, en + ": no stack (mimc3_stack_begin)");
+    if (!stack_scale_ok(scale)) return mimc3::fail(MIMC3_EINVAL, en + ": scale must be in 1/64..64");
+    return stack_layer_shift(c, scale, out, en);
+}
+
+extern "C" int mimc3_stack_weighted(mimc3_ctx *c) { return c && c->stk.N != 0 && c->stk.weighted ? 1 : 0; }
+
+// the points of one launch of a scaled add: neither the layer's slice nor the stack's exceeds kStackChunkCells
+static inline size_t stack_scaled_chunk(const mimc3_ctx *c, int32_t N, int32_t layer_R)
+{
+    const int a = mimc3::stack_chunk(c->stk.R), b = mimc3::stack_chunk(layer_R);
+    const int m = a < b ? a : b;
+    return (size_t)(N < m ? N : m);
+}
+
+// What a scaled add enqueues on `s` before its first chunk: the wsum plane of a stack that this add makes weighted, and the layer shift.
+// Called after every check has passed.
+static int stack_scaled_prepare(mimc3_ctx *c, double scale, double weight, hipStream_t s)
+{
+    auto &k = c->stk;
+    const size_t cells = (size_t)k.N * stack_cells(c);
+    HIP_TRY(k.lsh.reserve(sizeof(int32_t) * 2 * (size_t)k.N));
+    if (weight != 1.0 && !k.weighted) {
+        HIP_TRY(k.wsum.reserve(sizeof(double) * cells));
+        const hipError_t e = mimc3::launch_stack_wsum_init(static_cast<const uint16_t *>(k.cnt.p), cells, static_cast<double *>(k.wsum.p), s);
+        if (e != hipSuccess) return mimc3::hip_fail(e, "stack wsum kernel launch");
+        k.weighted = true;
+    }
+    const hipError_t e = mimc3::launch_stack_layer_shift(static_cast<const int32_t *>(k.shift.p), k.N, scale, static_cast<int32_t *>(k.lsh.p), s);
+    if (e != hipSuccess) return mimc3::hip_fail(e, "stack layer-shift kernel launch");
+    return 0;
+}
+
+static int stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t layer_R,
+                                int32_t swap, double scale, double weight, void *stream, const char *entry)
+{
+    const std::string en(entry);
+    if (!c || !d_xyuvav || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::wide_max_radius(ocw), scale, weight, en));
+    auto &k = c->stk;
+    const size_t NC = stack_cells(c), NCl = (size_t)((2 * layer_R + 1) * (2 * layer_R + 1));
+    const size_t chunk = stack_scaled_chunk(c, N, layer_R);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NCl));
+    HIP_TRY(k.rec.reserve(sizeof(float) * 8 * chunk));
+    if (!c->fplanes_ok) RC_TRY(build_f32(c));                   // (as mimc3_stack_add_dev)
+    const bool timing = c->timing;
+    if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    c->timing = false;                  // (the events bracket the whole call)
+    const int rp = stack_scaled_prepare(c, scale, weight, s);
+    if (rp) { c->timing = timing; return rp; }
+    float *layer = static_cast<float *>(k.layer.p), *rec = static_cast<float *>(k.rec.p);
+    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
+        const int32_t n = (int32_t)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
+        const int32_t *lsh = static_cast<const int32_t *>(k.lsh.p) + 2 * g0;
+        // mimc3_match_ncc_wide(npeaks 0, shift = the layer shift, R = layer_R, surf): the float kernel up to 15, the wide kernel beyond
+        const int rc = wide_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, lsh, ocw, layer_R, 0, swap, rec, nullptr, layer, stream, entry);
+        if (rc) { c->timing = timing; return rc; }
+        const hipError_t e = mimc3::launch_stack_add_scaled(layer, rec, nullptr, static_cast<const int32_t *>(k.shift.p) + 2 * g0, lsh, n, k.R,
+                                                            layer_R, scale, weight, static_cast<double *>(k.sum.p) + g0 * NC,
+                                                            static_cast<uint16_t *>(k.cnt.p) + g0 * NC, stack_wsum(c, g0 * NC),
+                                                            static_cast<uint16_t *>(k.lay.p) + g0, s);
+        if (e != hipSuccess) { c->timing = timing; return mimc3::hip_fail(e, "scaled stack add kernel launch"); }
+    }
+    c->timing = timing;
+    k.layers++;
+    if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
+                                          int32_t layer_R, int32_t swap, double scale, double weight, void *stream)
+{
+    return stack_add_scaled_dev(c, d_xyuvav, N, off_u, off_v, ocw, layer_R, swap, scale, weight, stream, "mimc3_stack_add_scaled_dev");
+}
+
+extern "C" int mimc3_stack_add_scaled(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t layer_R,
+                                      int32_t swap, double scale, double weight)
+{
+    const char *entry = "mimc3_stack_add_scaled";
+    const std::string en(entry);
+    if (!c || !xyuvav || !offset || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
+    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::wide_max_radius(ocw), scale, weight, en));
+    // the chip inside the image, the layer's search box inside the planes' zero border (as mimc3_stack_add, around the layer shift)
+    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
+    const int64_t pad = mimc3::kU8Pad, h = layer_R + ocw;
+    const int32_t *shift = c->stk.h_shift.data();
+    for (int32_t g = 0; g < N; ++g) {
+        const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
+        const int64_t lu = (int64_t)std::nearbyint(scale * (double)shift[2 * (size_t)g]);
+        const int64_t lv = (int64_t)std::nearbyint(scale * (double)shift[2 * (size_t)g + 1]);
+        const int64_t cu = (int64_t)u0 + offset[0] + lu, cv = (int64_t)v0 + offset[1] + lv;
+        if (cu - h < -pad || cu + h >= c->W + pad || cv - h < -pad || cv + h >= c->H + pad)
+            return mimc3::fail(MIMC3_EBOUNDS, en + ": grid point " + std::to_string(g) + " search box leaves the zero border");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
+    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
+    RC_TRY(stack_add_scaled_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, layer_R, swap, scale, weight,
+                                c->stream, entry));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int mimc3_stack_add_surfaces_scaled_dev(mimc3_ctx *c, const float *d_surf, const uint8_t *d_refused, int32_t N, int32_t layer_R,
+                                                   double scale, double weight, void *stream)
+{
+    const std::string en("mimc3_stack_add_surfaces_scaled_dev");
+    if (!c || !d_surf || N <= 0 || (reinterpret_cast<uintptr_t>(d_surf) & 3u)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::kStackMaxRadius, scale, weight, en));
+    auto &k = c->stk;
+    const size_t NC = stack_cells(c), NCl = (size_t)((2 * layer_R + 1) * (2 * layer_R + 1)), chunk = stack_scaled_chunk(c, N, layer_R);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(stack_scaled_prepare(c, scale, weight, s));
+    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
+        const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
+        const hipError_t e = mimc3::launch_stack_add_scaled(d_surf + g0 * NCl, nullptr, d_refused ? d_refused + g0 : nullptr,
+                                                            static_cast<const int32_t *>(k.shift.p) + 2 * g0,
+                                                            static_cast<const int32_t *>(k.lsh.p) + 2 * g0, n, k.R, layer_R, scale, weight,
+                                                            static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
+                                                            stack_wsum(c, g0 * NC), static_cast<uint16_t *>(k.lay.p) + g0, s);
+        if (e != hipSuccess) return mimc3::hip_fail(e, "scaled stack add kernel launch");
+    }
+    k.layers++;
+    return 0;
+}
+
+extern "C" int mimc3_stack_add_surfaces_scaled(mimc3_ctx *c, const float *surf, const uint8_t *refused, int32_t N, int32_t layer_R,
+                                               double scale, double weight)
+{
+    const std::string en("mimc3_stack_add_surfaces_scaled");
+    if (!c || !surf || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::kStackMaxRadius, scale, weight, en));
+    auto &k = c->stk;
+    const size_t NC = stack_cells(c), NCl = (size_t)((2 * layer_R + 1) * (2 * layer_R + 1)), chunk = stack_scaled_chunk(c, N, layer_R);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NCl));
+    if (refused) {
+        HIP_TRY(k.ref.reserve((size_t)N));
+        RC_TRY(h2d_copy(c, k.ref.p, refused, (size_t)N));
+    }
+    RC_TRY(stack_scaled_prepare(c, scale, weight, c->stream));
+    // one chunk of surfaces at a time through the layer scratch; copies and launches are ordered on the context's stream
+    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
+        const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
+        RC_TRY(h2d_copy(c, k.layer.p, surf + g0 * NCl, sizeof(float) * (size_t)n * NCl));
+        const hipError_t e = mimc3::launch_stack_add_scaled(static_cast<const float *>(k.layer.p), nullptr,
+                                                            refused ? static_cast<const uint8_t *>(k.ref.p) + g0 : nullptr,
+                                                            static_cast<const int32_t *>(k.shift.p) + 2 * g0,
+                                                            static_cast<const int32_t *>(k.lsh.p) + 2 * g0, n, k.R, layer_R, scale, weight,
+                                                            static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
+                                                            stack_wsum(c, g0 * NC), static_cast<uint16_t *>(k.lay.p) + g0, c->stream);
+        if (e != hipSuccess) return mimc3::hip_fail(e, "scaled stack add kernel launch");
     }
     k.layers++;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1450,8 +1669,9 @@ extern "C" int mimc3_stack_finish_dev(mimc3_ctx *c, int32_t npeaks, int32_t min_
     HIP_TRY(hipSetDevice(c->device));
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     const hipError_t e = mimc3::launch_stack_tail(static_cast<const double *>(k.sum.p), static_cast<const uint16_t *>(k.cnt.p),
-                                                  static_cast<const uint16_t *>(k.lay.p), static_cast<const int32_t *>(k.shift.p), k.N, k.R,
-                                                  npeaks, min_count, d_out, d_cand, d_surf, d_count, s);
+                                                  static_cast<const uint16_t *>(k.lay.p), stack_wsum(c, 0),
+                                                  static_cast<const int32_t *>(k.shift.p), k.N, k.R, npeaks, min_count, d_out, d_cand,
+                                                  d_surf, d_count, s);
     if (e != hipSuccess) return mimc3::hip_fail(e, "stack tail kernel launch");
     if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
     return 0;
