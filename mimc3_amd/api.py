@@ -223,6 +223,29 @@ def version():
     return _lib.mimc3_version().decode()
 
 
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _search_arrays(what, xyuvav, shift, npeaks=0, radius=0, surface=False, fb=False):
+    """What a host wrapper of the exhaustive-search family hands to the library -> (xy float64[n][6], n, out float32[n][8], cand
+    float32[npeaks][n][3] or None when npeaks <= 0, surf float32[n][(2 radius + 1)^2] or None, fb float32[1 + npeaks][n][4] or None,
+    shift int32[n][2] or None -- checked: ValueError on another shape)."""
+    xy = np.ascontiguousarray(xyuvav, np.float64)
+    n = xy.shape[0]
+    npeaks = int(npeaks)
+    out = np.empty((n, 8), np.float32)
+    cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+    surf = np.empty((n, (2 * int(radius) + 1) ** 2), np.float32) if surface else None
+    rows = np.empty((1 + max(npeaks, 0), n, 4), np.float32) if fb else None
+    sh = None
+    if shift is not None:
+        sh = np.ascontiguousarray(shift, np.int32)
+        if sh.shape != (n, 2):
+            raise ValueError(f"{what}: shift must be int32[{n}][2], got {sh.shape}")
+    return xy, n, out, cand, surf, rows, sh
+
+
 def wide_max_radius(ocw):
     """The largest radius match_ncc_wide takes at this chip size (mimc3_wide_max_radius); 0 for an ocw it does not take."""
     return int(_lib.mimc3_wide_max_radius(int(ocw)))
@@ -520,16 +543,9 @@ class Context:
         """Exhaustive-search NCC offsets with peak quality (mimc3_match_ncc_full) on the resident 8-bit pair -> float32[N][8]:
         du, dv, ncc_peak (or the status -2 / -3 / -4), ncc_fit, snr, h_uu, h_uv, h_vv.  Every offset in [-radius, radius]^2
         around uv0 + offset + shift[i] (shift int32[N][2] or None)."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        out = np.empty((n, 8), np.float32)
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_full: shift must be int32[{n}][2], got {sh.shape}")
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full", xyuvav, shift)
         _check(_lib.mimc3_match_ncc_full(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
-                                         None if sh is None else sh.ctypes.data, ocw, radius, 1 if swap else 0, out), "match_ncc_full")
+                                         _ptr(sh), ocw, radius, 1 if swap else 0, out), "match_ncc_full")
         return out
 
     def match_ncc_full_dev(self, d_xyuvav, n, offset, ocw, radius, d_out, d_shift=0, stream=0, swap=False):
@@ -542,18 +558,10 @@ class Context:
         float32[npeaks][N][3] candidates): per point the best npeaks (1..8) local maxima of its correlation surface as (du, dv, ncc),
         by NCC descending, pass-major -- the dp that cluster_candidates / mimc2_postprocess read.  Slots without a peak are
         (NaN, NaN, -2), or (NaN, NaN, -3) at an invalid point."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((max(int(npeaks), 0), n, 3), np.float32)
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_full_multi: shift must be int32[{n}][2], got {sh.shape}")
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_multi", xyuvav, shift, npeaks=npeaks)
         _check(_lib.mimc3_match_ncc_full_multi(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
-                                               None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, out,
-                                               cand.reshape(-1) if cand.size else np.empty(1, np.float32)), "match_ncc_full_multi")
+                                               _ptr(sh), ocw, radius, int(npeaks), 1 if swap else 0, out,
+                                               np.empty(1, np.float32) if cand is None else cand.reshape(-1)), "match_ncc_full_multi")
         return out, cand
 
     def match_ncc_full_multi_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand, d_shift=0, stream=0, swap=False):
@@ -565,19 +573,9 @@ class Context:
         """The exhaustive search on the pair the context matches on (mimc3_match_ncc_full_planes): an 8-bit pair, or a scaled-integer
         one -- 12-bit DN, the pair after filter_images -> (float32[N][8] record as match_ncc_full, float32[npeaks][N][3] candidates
         as match_ncc_full_multi, or None when npeaks == 0)."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        npeaks = int(npeaks)
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_full_planes: shift must be int32[{n}][2], got {sh.shape}")
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_planes", xyuvav, shift, npeaks=npeaks)
         _check(_lib.mimc3_match_ncc_full_planes(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
-                                                None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, out,
-                                                None if cand is None else cand.ctypes.data), "match_ncc_full_planes")
+                                                _ptr(sh), ocw, radius, int(npeaks), 1 if swap else 0, out, _ptr(cand)), "match_ncc_full_planes")
         return out, cand
 
     def match_ncc_full_planes_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False):
@@ -589,19 +587,9 @@ class Context:
         """The exhaustive search on every pair the planes' matchers take (mimc3_match_ncc_full_dn): what match_ncc_full_planes takes,
         bit for bit, and an integral-f32 pair -- 16-bit DN, and what filter_images makes of it -> (float32[N][8] record,
         float32[npeaks][N][3] candidates, or None when npeaks == 0)."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        npeaks = int(npeaks)
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_full_dn: shift must be int32[{n}][2], got {sh.shape}")
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_dn", xyuvav, shift, npeaks=npeaks)
         _check(_lib.mimc3_match_ncc_full_dn(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
-                                            None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, out,
-                                            None if cand is None else cand.ctypes.data), "match_ncc_full_dn")
+                                            _ptr(sh), ocw, radius, int(npeaks), 1 if swap else 0, out, _ptr(cand)), "match_ncc_full_dn")
         return out, cand
 
     def match_ncc_full_dn_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False):
@@ -614,21 +602,9 @@ class Context:
         bit for bit, and every other pair -- non-integral pixels, NaN or negative nulls -- through the float kernel ("f32g_full"); mode 1
         sends any pair through the float kernel -> (float32[N][8] record, float32[npeaks][N][3] candidates or None when npeaks == 0),
         and with surface=True (float kernel only) every point's NCC surface float32[N][(2 radius + 1)^2] in k order as a third item."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        npeaks = int(npeaks)
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
-        surf = np.empty((n, (2 * int(radius) + 1) ** 2), np.float32) if surface else None
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_full_any: shift must be int32[{n}][2], got {sh.shape}")
-        _check(_lib.mimc3_match_ncc_full_any(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
-                                             None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, int(mode), out,
-                                             None if cand is None else cand.ctypes.data, None if surf is None else surf.ctypes.data),
-               "match_ncc_full_any")
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_any", xyuvav, shift, npeaks=npeaks, radius=radius, surface=surface)
+        _check(_lib.mimc3_match_ncc_full_any(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh), ocw, radius, int(npeaks),
+                                             1 if swap else 0, int(mode), out, _ptr(cand), _ptr(surf)), "match_ncc_full_any")
         return (out, cand, surf) if surface else (out, cand)
 
     def match_ncc_full_any_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, mode=0,
@@ -644,21 +620,9 @@ class Context:
         that call, byte for byte ("f32g_full"); radius >= 16 runs the wide kernel ("f32g_wide") -> (float32[N][8] record,
         float32[npeaks][N][3] candidates or None when npeaks == 0), and with surface=True every point's NCC surface
         float32[N][(2 radius + 1)^2] in k order as a third item."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        npeaks = int(npeaks)
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
-        surf = np.empty((n, (2 * int(radius) + 1) ** 2), np.float32) if surface else None
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_wide: shift must be int32[{n}][2], got {sh.shape}")
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_wide", xyuvav, shift, npeaks=npeaks, radius=radius, surface=surface)
         _check(_lib.mimc3_match_ncc_wide(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
-                                         None if sh is None else sh.ctypes.data, ocw, radius, npeaks, 1 if swap else 0, out,
-                                         None if cand is None else cand.ctypes.data, None if surf is None else surf.ctypes.data),
-               "match_ncc_wide")
+                                         _ptr(sh), ocw, radius, int(npeaks), 1 if swap else 0, out, _ptr(cand), _ptr(surf)), "match_ncc_wide")
         return (out, cand, surf) if surface else (out, cand)
 
     def match_ncc_wide_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, d_surf=0):
@@ -674,21 +638,9 @@ class Context:
         float32[npeaks][N][3] candidates or None when npeaks == 0, float32[1 + npeaks][N][4] fb).  An fb row is (du_b, dv_b, ncc_b, err),
         err = |d_forward + d_backward| (near 0 for a reciprocal peak); column 2 holds a status where there is no row: -5 the forward
         result has no fit, -6 the chip at the landing point leaves the image, -2 / -3 / -4 the backward search's own."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        npeaks = int(npeaks)
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
-        fb = np.empty((1 + max(npeaks, 0), n, 4), np.float32)
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_full_fb: shift must be int32[{n}][2], got {sh.shape}")
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_fb", xyuvav, shift, npeaks=npeaks, fb=True)
         _check(_lib.mimc3_match_ncc_full_fb(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
-                                            None if sh is None else sh.ctypes.data, ocw, radius, npeaks, int(mode), out,
-                                            None if cand is None else cand.ctypes.data, fb.ctypes.data),
-               "match_ncc_full_fb")
+                                            _ptr(sh), ocw, radius, int(npeaks), int(mode), out, _ptr(cand), _ptr(fb)), "match_ncc_full_fb")
         return out, cand, fb
 
     def match_ncc_full_fb_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_fb, d_cand=0, d_shift=0, stream=0, mode=0):
@@ -702,21 +654,9 @@ class Context:
         radius <= wide_max_radius(ocw) -- the forward pass is match_ncc_wide(swap False), the one backward pass match_ncc_wide(swap True)
         over the record and the candidates of every point -> (float32[N][8] record, float32[npeaks][N][3] candidates or None when
         npeaks == 0, float32[1 + npeaks][N][4] fb); radius <= 15 returns the bytes of match_ncc_full_fb(mode=1)."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        npeaks = int(npeaks)
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
-        fb = np.empty((1 + max(npeaks, 0), n, 4), np.float32)
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_wide_fb: shift must be int32[{n}][2], got {sh.shape}")
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_wide_fb", xyuvav, shift, npeaks=npeaks, fb=True)
         _check(_lib.mimc3_match_ncc_wide_fb(self._h, xy, n, np.ascontiguousarray(offset, np.int32),
-                                            None if sh is None else sh.ctypes.data, ocw, radius, npeaks, out,
-                                            None if cand is None else cand.ctypes.data, fb.ctypes.data),
-               "match_ncc_wide_fb")
+                                            _ptr(sh), ocw, radius, int(npeaks), out, _ptr(cand), _ptr(fb)), "match_ncc_wide_fb")
         return out, cand, fb
 
     def match_ncc_wide_fb_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_fb, d_cand=0, d_shift=0, stream=0):
@@ -736,7 +676,7 @@ class Context:
             sh = np.ascontiguousarray(shift, np.int32)
             if sh.shape != (n, 2):
                 raise ValueError(f"stack_begin: shift must be int32[{n}][2], got {sh.shape}")
-        _check(_lib.mimc3_stack_begin(self._h, n, int(radius), None if sh is None else sh.ctypes.data), "stack_begin")
+        _check(_lib.mimc3_stack_begin(self._h, n, int(radius), _ptr(sh)), "stack_begin")
 
     def stack_begin_wide(self, n, radius, shift=None):
         """stack_begin with radius 1..47 (mimc3_stack_begin_wide).  radius <= 15 leaves the context exactly as stack_begin does; on a
@@ -748,7 +688,7 @@ class Context:
             sh = np.ascontiguousarray(shift, np.int32)
             if sh.shape != (n, 2):
                 raise ValueError(f"stack_begin_wide: shift must be int32[{n}][2], got {sh.shape}")
-        _check(_lib.mimc3_stack_begin_wide(self._h, n, int(radius), None if sh is None else sh.ctypes.data), "stack_begin_wide")
+        _check(_lib.mimc3_stack_begin_wide(self._h, n, int(radius), _ptr(sh)), "stack_begin_wide")
 
     def stack_add(self, xyuvav, offset, ocw, swap=False):
         """One layer from the resident pair: the surfaces of match_ncc_full_any(mode=1) with the stack's shift and radius, accumulated
@@ -845,8 +785,8 @@ class Context:
         cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
         count = np.empty(n, np.uint16)
         surf = np.empty((n, (2 * r + 1) ** 2), np.float32) if surface else None
-        _check(_lib.mimc3_stack_finish(self._h, npeaks, int(min_count), out, None if cand is None else cand.ctypes.data,
-                                       None if surf is None else surf.ctypes.data, count.ctypes.data), "stack_finish")
+        _check(_lib.mimc3_stack_finish(self._h, npeaks, int(min_count), out, _ptr(cand),
+                                       _ptr(surf), count.ctypes.data), "stack_finish")
         return (out, cand, count, surf) if surface else (out, cand, count)
 
     def stack_finish_dev(self, npeaks, min_count, d_out, d_cand=0, d_surf=0, d_count=0, stream=0):
@@ -890,16 +830,9 @@ class Context:
         """Coarse-to-fine exhaustive search over an image pyramid (mimc3_match_ncc_pyramid) on the resident 8-bit pair ->
         (float32[N][8] record as match_ncc_full, int32[N][2] shift_out).  The search at +-radius runs on the pair reduced levels - 1
         times first, then each finer level around twice the coarser result; the record is match_ncc_full's with shift = shift_out."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        out = np.empty((n, 8), np.float32)
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_pyramid", xyuvav, shift)
         sh_out = np.empty((n, 2), np.int32)
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_pyramid: shift must be int32[{n}][2], got {sh.shape}")
-        _check(_lib.mimc3_match_ncc_pyramid(self._h, xy, n, np.ascontiguousarray(offset, np.int32), None if sh is None else sh.ctypes.data,
+        _check(_lib.mimc3_match_ncc_pyramid(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh),
                                             ocw, radius, levels, 1 if swap else 0, out, sh_out), "match_ncc_pyramid")
         return out, sh_out
 
@@ -914,20 +847,11 @@ class Context:
         integral-f32 (16-bit DN and its filtered forms) -> (float32[N][8] record, float32[npeaks][N][3] candidates or None when
         npeaks == 0, int32[N][2] shift_out).  The levels are reductions of the pair currently matched on (filter, then reduce); record
         and candidates are match_ncc_full_dn's with shift = shift_out."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        npeaks = int(npeaks)
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_pyramid_dn", xyuvav, shift, npeaks=npeaks)
         sh_out = np.empty((n, 2), np.int32)
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_pyramid_dn: shift must be int32[{n}][2], got {sh.shape}")
-        _check(_lib.mimc3_match_ncc_pyramid_dn(self._h, xy, n, np.ascontiguousarray(offset, np.int32), None if sh is None else sh.ctypes.data,
-                                               ocw, radius, levels, npeaks, 1 if swap else 0, out,
-                                               None if cand is None else cand.ctypes.data, sh_out), "match_ncc_pyramid_dn")
+        _check(_lib.mimc3_match_ncc_pyramid_dn(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh),
+                                               ocw, radius, levels, int(npeaks), 1 if swap else 0, out,
+                                               _ptr(cand), sh_out), "match_ncc_pyramid_dn")
         return out, cand, sh_out
 
     def match_ncc_pyramid_dn_dev(self, d_xyuvav, n, offset, ocw, radius, levels, npeaks, d_out, d_cand=0, d_shift=0, d_shift_out=0, stream=0,
@@ -949,20 +873,11 @@ class Context:
         candidates or None when npeaks == 0, int32[N][2] shift_out).  mode 0: match_ncc_pyramid_dn on the pairs that takes, bit for bit,
         and float levels with the float kernel ("f32g_full") on every other pair -- non-integral pixels, NaN or negative nulls; mode 1:
         the float levels and the float kernel on any pair.  Record and candidates are match_ncc_full_any's with shift = shift_out."""
-        xy = np.ascontiguousarray(xyuvav, np.float64)
-        n = xy.shape[0]
-        npeaks = int(npeaks)
-        out = np.empty((n, 8), np.float32)
-        cand = np.empty((npeaks, n, 3), np.float32) if npeaks > 0 else None
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_pyramid_any", xyuvav, shift, npeaks=npeaks)
         sh_out = np.empty((n, 2), np.int32)
-        sh = None
-        if shift is not None:
-            sh = np.ascontiguousarray(shift, np.int32)
-            if sh.shape != (n, 2):
-                raise ValueError(f"match_ncc_pyramid_any: shift must be int32[{n}][2], got {sh.shape}")
-        _check(_lib.mimc3_match_ncc_pyramid_any(self._h, xy, n, np.ascontiguousarray(offset, np.int32), None if sh is None else sh.ctypes.data,
-                                                ocw, radius, levels, npeaks, 1 if swap else 0, int(mode), out,
-                                                None if cand is None else cand.ctypes.data, sh_out), "match_ncc_pyramid_any")
+        _check(_lib.mimc3_match_ncc_pyramid_any(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh),
+                                                ocw, radius, levels, int(npeaks), 1 if swap else 0, int(mode), out,
+                                                _ptr(cand), sh_out), "match_ncc_pyramid_any")
         return out, cand, sh_out
 
     def match_ncc_pyramid_any_dev(self, d_xyuvav, n, offset, ocw, radius, levels, npeaks, d_out, d_cand=0, d_shift=0, d_shift_out=0, stream=0,

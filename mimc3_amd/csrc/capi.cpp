@@ -1,5 +1,6 @@
 // capi.cpp -- the C ABI of libmimc3_hip.so (include/mimc3_hip.h): context, resident images,
 // host-buffer (drop-in) and device-buffer (resident) entry points of the matcher and QM paths.
+// The exhaustive-search entries are in search.cpp and the stack in stack.cpp; the three share ctx_internal.h.
 // No CPU fallback: every compute entry point needs a HIP device and fails loudly without one.
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -12,151 +13,30 @@
 #include <string>
 #include <thread>
 #include <vector>
-#include "../../include/mimc3_hip.h"
-#include "host_util.h"
-#include "match_kernel.h"
+#include "ctx_internal.h"
 #include "sat_kernel.h"
 #include "pivot_kernel.h"
 #include "qm_kernel.h"
 #include "n1_kernel.h"
 #include "conv2_kernel.h"
 #include "cp_kernel.h"
-#include "fb_kernel.h"
-#include "stack_kernel.h"
 #include <ctime>
 #include <cstdlib>
+
+// (defined here, declared in ctx_internal.h for search.cpp and stack.cpp)
+using mimc3::h2d_copy; using mimc3::d2h_copy; using mimc3::check_chips; using mimc3::u8_args;
+using mimc3::build_u8_tables; using mimc3::build_u16; using mimc3::build_f32;
 
 namespace mimc3 {
 static thread_local std::string g_err;
 int fail(int code, const char *msg) { g_err = msg ? msg : ""; return code; }
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
-static int hip_fail(hipError_t e, const char *what)
+int hip_fail(hipError_t e, const char *what)
 {
     g_err = std::string(what) + ": " + hipGetErrorString(e);
     return (int)e > 0 ? (int)e : MIMC3_ENODEV;
 }
 }  // namespace mimc3
-
-#define HIP_TRY(expr)                                                        \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) return mimc3::hip_fail(e_, #expr);             \
-    } while (0)
-
-// growable device buffer
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    // owned: a context's buffers go with the context (mimc3_ctx_destroy selects the device first), so a member added later cannot be
-    // forgotten there
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-};
-
-struct mimc3_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;       // owned; host-buffer entry points run here
-    const float *d_i0 = nullptr, *d_i1 = nullptr;
-    DevBuf own_i0, own_i1;              // used when images were uploaded from the host
-    int32_t H = 0, W = 0;
-    // The pair's plane sets, one builder each (prepare_pair, build_u8_tables, build_u16, build_f32).  A builder works on `stream` and
-    // drains it before it sets its ready flag, so a set is complete whatever stream a matcher call comes in on.
-    DevBuf pl0, pl1, flag;              // zero-bordered u8 planes (exact-integer path) + the device tests' flags
-    DevBuf sat0, sat1, sat_tmp;         // packed summed-area tables of pl0 / pl1 (sum b | sum b^2 | nulls; sat_kernel.hip), built with the planes
-    DevBuf hsat0, hsat1, hsz0, hsz1;    // the same for the u16 planes hpl0 / hpl1: sum q | sum q^2, and the null counts
-    bool sat_u8_ok = false, sat_u16_ok = false;   // tables hold the CURRENT planes (chip-atlas contexts build them only if a call needs them)
-    DevBuf ovf;                         // [0] count, [1..] indices of points the u8 kernel handed back
-    DevBuf fail;                        // [0] count, [1..] points the offset-u8 kernel handed to the u16 kernel
-    bool u8o_ok = false;                // integer (shift 0) u16 planes whose local range mostly fits 8 bits: try PxU8o first
-    DevBuf hpl0, hpl1;                  // zero-bordered u16 planes of scaled integers (q = value * 2^shift < 4096)
-    DevBuf rt0, rt1;                    // PxU8o: min | max << 16 of every 16x16-pixel tile of hpl0 / hpl1 (valid while u8o_ok)
-    bool u16_ok = false;                // the pair is scaled-integer (and not 8-bit): its u16 planes are built with the classification
-    bool hpl_valid = false;             // u16 planes hold the CURRENT pair
-    int shift0 = 0, shift1 = 0;         // scaled integers: pixel x 2^shift is the u16 plane's value (0 for an 8-bit pair)
-    DevBuf fpl0, fpl1;                  // zero-bordered f32 planes (register-tiled f32 kernel), built on first use
-    bool fplanes_ok = false;
-    DevBuf fsat0, fsat1;                // their 16-byte summed-area tables when every pixel (x 1 or x 8) is an integer in [0, 2^20) (16-bit DN and its filtered forms)
-    bool f32i_ok = false;
-    int fshift0 = 0, fshift1 = 0;      // pixel x 2^shift is the integer the table sums
-    int32_t Wp = 0;
-    bool u8_ok = false;                 // both images proven to be integers in [0,255]: the u8 planes are built with the classification
-    int path_mode = 0;                  // 0 auto, 1 force the general f32 kernel, 2 no integer kernels, 3 no u8 kernel, 4 auto without the matrix-core kernel
-    int last_path = -1;                 // 0 general f32/f64 kernel, 1 exact u8 kernel, ... (mimc3_hip.h), 5 matrix-core u8 kernel, 9 float search kernel, 10 wide float search kernel
-    DevBuf xy, puv, poff, out;          // matcher staging for the host-buffer entry point
-    DevBuf pcor, pcnt, pext;            // device pivots: corridors [N] x 24 B, counts [N], extents + total (24 B)
-    hipEvent_t ev_chunk[2][8] = {};     // mimc3_match_ncc_dlc_cor: "chunk uploaded + counted" / "chunk matched"
-    DevBuf qm_io, qm_work;              // QM staging / workspace
-    DevBuf n1_io, n1_work;              // clustering / dpf0 / dpf1 staging and workspace
-    const float *raw_i0 = nullptr, *raw_i1 = nullptr;   // the pair as handed over (before any pre-filter)
-    DevBuf filt0, filt1, conv_io;       // pre-filtered pair (mimc3_ctx_filter_images), conv2 staging
-    DevBuf cp_buf;                      // control-point stage: one arena carved per call
-    DevBuf cp_pre;                      // control-point stage: the filtered planes of a whole segment (their minima are settled before the slices start)
-    bool filt_live = false;             // filt0/filt1 hold the output planes of an earlier filter pass on this pair
-    hipStream_t side[3] = {nullptr, nullptr, nullptr};   // CP stage: its 16 small matcher launches per segment overlap on 4 streams
-    hipEvent_t ev_side[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};   // mimc3_ctx_aux_stream: copy streams of the drivers' host threads
-    bool child = false;                 // a control-point child context: no streams / children of its own beyond `stream`
-    bool timing = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    // host -> device staging: two pinned chunks that a pageable source is pipelined through (a pinned source is DMA'd directly)
-    void *pin[2] = {nullptr, nullptr};
-    hipEvent_t ev_pin[2] = {nullptr, nullptr};
-    void *hslot[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // mimc3_ctx_host_workspace: pinned host scratch
-    size_t hslot_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    DevBuf slot[24];                    // mimc3_ctx_workspace: named scratch the drivers built on the ABI keep across calls
-    DevBuf ovf_alt[3], fail_alt[3];     // the overflow lists of matcher lanes 1..3: calls on different streams of one context must not share them
-    DevBuf mxl[4];                      // matrix-core kernel: one class byte per grid point (one buffer per lane)
-    DevBuf u8l[4];                      // u8_classify: the clean and rest lists of a call with their counts (int32; one buffer per lane)
-    mimc3_ctx *cp_child[4] = {nullptr, nullptr, nullptr, nullptr};   // CP stage: one context per image variant for its chip atlas (planes, kernel selection)
-    DevBuf cellws;                      // general matcher: global cell-grid workspace for corridors whose cell grid outgrows LDS
-    DevBuf raw_dn;                      // raw 8/16-bit DN as uploaded (mimc3_ctx_set_images_u8/_u16), widened on the device
-    // coarse-to-fine search (mimc3_match_ncc_pyramid): pyramid levels 1..4 of the u8 pair, each a zero-bordered plane pair (kU8Pad border,
-    // prepare_pair's pitch rule) with its tables; levels 1..pyr_levels hold the CURRENT pair (built on first use by build_levels)
-    struct PyrLevel { DevBuf pl0, pl1, sat0, sat1; int32_t H = 0, W = 0, Wp = 0; } pyr[4];
-    int pyr_levels = 0;
-    // mimc3_match_ncc_pyramid_dn: the same for the other two classes -- u16 planes with packed and null tables (a scaled-integer pair),
-    // f32 planes with 16-byte tables (an integral-f32 pair).  A pair has one class, so pyr_levels counts the levels of whichever set is its
-    struct PyrLevel16 { DevBuf pl0, pl1, sat0, sat1, sz0, sz1; int32_t H = 0, W = 0, Wp = 0; } pyr16[4];
-    struct PyrLevelF { DevBuf pl0, pl1, sat0, sat1; int32_t H = 0, W = 0, Wp = 0; } pyrf[4];
-    // mimc3_match_ncc_pyramid_any: float levels 1..pyrg_levels of the f32 planes (build_f32), planes alone -- the float kernel reads no
-    // tables.  A set and a counter of their own: mode 1 on an integer-class pair builds them beside that class's levels, and both stay
-    // valid until the pair changes
-    struct PyrLevelG { DevBuf pl0, pl1; int32_t H = 0, W = 0, Wp = 0; } pyrg[4];
-    int pyrg_levels = 0;
-    DevBuf pyr_pos, pyr_peak, pyr_sh;   // per point: position on the level (f64 [N][2]), arg-max cell, search shift (the host entry's)
-    DevBuf full_cand;                   // mimc3_match_ncc_full_multi's host entry: the candidates, f32 [npeaks][N][3]
-    DevBuf full_surf;                   // mimc3_match_ncc_full_any's host entry: the surfaces, f32 [N][(2R+1)^2]
-    // mimc3_match_ncc_full_fb: the backward search's rows ((1 + npeaks) N of them) -- xyuvav' [rows][6], shift' [rows][2], its records
-    // [rows][8], one reason byte per row -- and the host entry's fb [rows][4]
-    DevBuf fb_xy, fb_sh, fb_rec, fb_why, fb_out;
-    // mimc3_stack_*: the stack (NCC surfaces accumulated over several pairs; state of its own, which the image setters never touch) --
-    // sum f64 [N][S^2], cnt u16 [N][S^2], lay u16 [N], shift i32 [N][2] (zeros when none was given; a host copy for the host entry's
-    // bounds check); the layer scratch of an add (surfaces and records of one chunk of points) and the staging of the host entries.
-    // A weighted stack (the first add with a weight other than 1 makes it one) has wsum f64 [N][S^2] as well; lsh i32 [N][2] is the
-    // layer shift of the scaled add that is under way
-    struct Stack {
-        DevBuf sum, cnt, lay, shift;
-        DevBuf wsum, lsh;
-        bool weighted = false;
-        DevBuf layer, rec, ref;         // one chunk: f32 [chunk][S^2], f32 [chunk][8]; the host entry's refused flags [N]
-        DevBuf out, cand, surf, count;  // mimc3_stack_finish's host entry
-        std::vector<int32_t> h_shift;
-        int32_t N = 0, R = 0, layers = 0;
-    } stk;
-};
 
 static constexpr size_t kPinChunk = 4u << 20;
 
@@ -164,7 +44,7 @@ static constexpr size_t kPinChunk = 4u << 20;
 // pageable ones are pipelined through two pinned 4 MiB chunks (host memcpy of chunk k+1 overlaps the DMA of chunk k),
 // which is ~10x the rate hipMemcpy reaches from pageable memory on this platform.  Returns after enqueueing (pinned) or
 // after the last chunk was handed to the DMA engine (pageable); the caller synchronises the stream.
-static int h2d_copy(mimc3_ctx *c, void *dst, const void *src, size_t bytes)
+int mimc3::h2d_copy(mimc3_ctx *c, void *dst, const void *src, size_t bytes)
 {
     if (bytes == 0) return 0;
     hipPointerAttribute_t at{};
@@ -193,7 +73,7 @@ static int h2d_copy(mimc3_ctx *c, void *dst, const void *src, size_t bytes)
     return 0;
 }
 // Device -> host, synchronous (returns with the bytes in `dst`): through the pinned chunks when `dst` is pageable.
-static int d2h_copy(mimc3_ctx *c, void *dst, const void *src, size_t bytes)
+int mimc3::d2h_copy(mimc3_ctx *c, void *dst, const void *src, size_t bytes)
 {
     if (bytes == 0) return 0;
     hipPointerAttribute_t at{};
@@ -226,7 +106,6 @@ static int d2h_copy(mimc3_ctx *c, void *dst, const void *src, size_t bytes)
     }
     return 0;
 }
-#define RC_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 extern "C" void *mimc3_host_alloc(size_t bytes)
 {
@@ -331,7 +210,7 @@ static int detect_shifts(mimc3_ctx *c, detect_launcher detect, int shift[2])
 }
 
 // The u8 form's summed-area tables (its planes come with the classification, prepare_pair).
-static int build_u8_tables(mimc3_ctx *c)
+int mimc3::build_u8_tables(mimc3_ctx *c)
 {
     const int Hp = c->H + 2 * mimc3::kU8Pad;
     HIP_TRY(c->sat0.reserve(mimc3::sat_bytes(Hp, c->Wp)));
@@ -349,7 +228,7 @@ static int build_u8_tables(mimc3_ctx *c)
 // almost everywhere: the u8 kernels then run it through per-point offsets (PxU8o) and the few points that do not fit go to PxU16.
 // (Not on a chip-atlas context: over a whole 85x85 search area a gradient's range rarely fits 8 bits, and a second launch for the
 // points that do not costs a full kernel latency.)
-static int build_u16(mimc3_ctx *c, bool tables)
+int mimc3::build_u16(mimc3_ctx *c, bool tables)
 {
     const int pad = mimc3::kU8Pad, Hp = c->H + 2 * pad;
     if (!c->hpl_valid) {
@@ -400,7 +279,7 @@ static int build_u16(mimc3_ctx *c, bool tables)
 // filtered forms (every pixel, x 1 or x 8, an integer in [0, 2^20)) also get summed-area tables like the integer planes: the f64
 // sums of the reference are exact integers in any order.  (Not for the control-point stage's chip atlases: a few hundred
 // latency-bound points.)
-static int build_f32(mimc3_ctx *c)
+int mimc3::build_f32(mimc3_ctx *c)
 {
     const size_t bytes = sizeof(float) * (size_t)(c->H + 2 * mimc3::kU8Pad) * c->Wp;
     HIP_TRY(c->fpl0.reserve(bytes));
@@ -577,7 +456,7 @@ extern "C" int mimc3_ctx_last_kernel_ms(mimc3_ctx *c, float *ms)
 // The reference reads the chip without any bounds check (MIMC_module.c:852): refuse a grid point g0 <= g < g1 of the xyuvav rows
 // whose chip leaves the image instead of reproducing undefined behaviour.  With `uv`, the points' (u, v) are packed there in the
 // same pass ([N][2], indexed by g).
-static int check_chips(const mimc3_ctx *c, const double *xyuvav, int32_t g0, int32_t g1, int32_t ocw, const char *entry, double *uv = nullptr)
+int mimc3::check_chips(const mimc3_ctx *c, const double *xyuvav, int32_t g0, int32_t g1, int32_t ocw, const char *entry, double *uv)
 {
     for (int32_t g = g0; g < g1; ++g) {
         const double gu = xyuvav[6 * (size_t)g + 2], gv = xyuvav[6 * (size_t)g + 3];
@@ -590,7 +469,7 @@ static int check_chips(const mimc3_ctx *c, const double *xyuvav, int32_t g0, int
 }
 
 // the MatchU8Args fields the DLC and exhaustive-search entries share: plane geometry and the grid
-static mimc3::MatchU8Args u8_args(const mimc3_ctx *c, const double *d_xy, int32_t xy_stride, int32_t xy_col, int32_t N, int32_t off_u, int32_t off_v,
+mimc3::MatchU8Args mimc3::u8_args(const mimc3_ctx *c, const double *d_xy, int32_t xy_stride, int32_t xy_col, int32_t N, int32_t off_u, int32_t off_v,
                                   int32_t ocw, int32_t swap, float *d_out)
 {
     mimc3::MatchU8Args u{};
@@ -768,1326 +647,7 @@ extern "C" int mimc3_match_ncc_dlc(mimc3_ctx *c, const double *xyuvav, int32_t N
     return d2h_copy(c, out, c->out.p, sizeof(float) * 3 * (size_t)N);
 }
 
-// ---------------------------------------------------------------------------------------------
-// exhaustive-search NCC offsets with peak quality (match_mx_kernel.hip, full mode): every (2R+1)^2 cell of a point on the
-// matrix cores, 8-bit pairs only
-// ---------------------------------------------------------------------------------------------
-static bool full_ocw_ok(int32_t ocw) { return ocw == 7 || ocw == 15 || ocw == 16 || ocw == 30 || ocw == 32 || ocw == 40; }
-
-// the device entry of the exhaustive search, without (d_cand null) or with the candidates of its best npeaks local maxima
-static int full_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                    int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream, const char *entry)
-{
-    const std::string en(entry);
-    if (!c || !d_xyuvav || !d_out || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
-    if (d_cand && (npeaks < 1 || npeaks > mimc3::kFullMaxPeaks)) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 1..8");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    if (!c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
-    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
-    u.full_shift = d_shift; u.full_R = R;
-    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
-    u.p0 = static_cast<const unsigned char *>(c->pl0.p); u.p1 = static_cast<const unsigned char *>(c->pl1.p);
-    u.sat0 = c->sat0.p; u.sat1 = c->sat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
-    DevBuf &ml = c->mxl[0];
-    HIP_TRY(ml.reserve((size_t)N));
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
-    u.mx_flags = static_cast<uint8_t *>(ml.p);
-    const hipError_t e = mimc3::launch_match_full_mx(u, s);
-    if (e != hipSuccess) return mimc3::hip_fail(e, "full-search kernel launch");
-    c->last_path = 6;
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_full_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                        const int32_t *d_shift, int32_t ocw, int32_t R, int32_t swap, float *d_out, void *stream)
-{
-    return full_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, 0, swap, d_out, nullptr, stream, "mimc3_match_ncc_full_dev");
-}
-
-extern "C" int mimc3_match_ncc_full_multi_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                              const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
-                                              float *d_cand, void *stream)
-{
-    if (!d_cand) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_full_multi_dev: bad argument");
-    return full_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream, "mimc3_match_ncc_full_multi_dev");
-}
-
-// the host entry of the exhaustive search: its checks, the uploads, the device entry and the copies back (cand null: the record alone)
-// (kind 1: mimc3_match_ncc_full_planes -- a scaled-integer pair is taken too, on its u16 planes; kind 2: mimc3_match_ncc_full_dn -- and an
-//  integral-f32 pair on its f32 planes)
-static int full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream,
-                           const char *entry = "mimc3_match_ncc_full_planes_dev");
-static int full_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                       int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream);
-static int full_dn_class(mimc3_ctx *c, const std::string &en);
-static int full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                        int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out, float *d_cand, float *d_surf,
-                        void *stream);
-static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                       int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream, bool wide = false);
-static int wide_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                    int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, float *d_surf, void *stream,
-                    const char *entry = "mimc3_match_ncc_wide_dev");
-// (kind 3: mimc3_match_ncc_full_any -- any f32 pair, with `mode` and the optional surfaces `surf`;
-//  kind 4: mimc3_match_ncc_full_fb -- kind 3 forward (swap 0, no surfaces), then the back-match of every result into fb;
-//  kind 5: mimc3_match_ncc_wide -- kind 3 in mode 1 with R up to mimc3_wide_max_radius(ocw);
-//  kind 6: mimc3_match_ncc_wide_fb -- kind 4 over kind 5)
-static int full_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
-                     int32_t npeaks, int32_t swap, float *out, float *cand, bool multi, const char *entry, int kind = 0,
-                     int32_t mode = 0, float *surf = nullptr, float *fb = nullptr)
-{
-    const bool planes = kind == 1;
-    const std::string en(entry);
-    if (!c || !xyuvav || !offset || !out || N <= 0 || (multi && !cand)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (kind >= 5 ? (R < 1 || R > mimc3::wide_max_radius(ocw)) : (R < 1 || R > 15))
-        return mimc3::fail(MIMC3_EINVAL, en + (kind >= 5 ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
-    if (multi && (npeaks < 1 || npeaks > mimc3::kFullMaxPeaks)) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 1..8");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    if (planes && !c->u8_ok && !c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
-    if (kind == 0 && !c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is not 8-bit (u8 planes only)");
-    if (kind == 2) RC_TRY(full_dn_class(c, en));
-    if (kind >= 3 && mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
-    if (kind >= 3 && c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    if ((kind == 4 || kind == 6) && !fb) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    // the chip inside the image (as mimc3_match_ncc_dlc), the search box inside the planes' zero border
-    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
-    const int64_t pad = mimc3::kU8Pad;
-    for (int32_t g = 0; g < N; ++g) {
-        const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
-        const int64_t cu = (int64_t)u0 + offset[0] + (shift ? shift[2 * (size_t)g] : 0), cv = (int64_t)v0 + offset[1] + (shift ? shift[2 * (size_t)g + 1] : 0);
-        const int64_t h = R + ocw;
-        if (cu - h < -pad || cu + h >= c->W + pad || cv - h < -pad || cv + h >= c->H + pad)
-            return mimc3::fail(MIMC3_EBOUNDS, en + ": grid point " + std::to_string(g) + " search box leaves the zero border");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
-    HIP_TRY(c->out.reserve(sizeof(float) * 8 * (size_t)N));
-    if (multi) HIP_TRY(c->full_cand.reserve(sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
-    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
-    const int32_t *d_shift = nullptr;
-    if (shift) {
-        HIP_TRY(c->puv.reserve(sizeof(int32_t) * 2 * (size_t)N));
-        RC_TRY(h2d_copy(c, c->puv.p, shift, sizeof(int32_t) * 2 * (size_t)N));
-        d_shift = static_cast<const int32_t *>(c->puv.p);
-    }
-    float *d_cand = multi ? static_cast<float *>(c->full_cand.p) : nullptr;
-    const size_t surf_bytes = sizeof(float) * (size_t)N * (size_t)((2 * R + 1) * (2 * R + 1));
-    if ((kind == 3 || kind == 5) && surf) HIP_TRY(c->full_surf.reserve(surf_bytes));
-    const size_t fb_bytes = sizeof(float) * 4 * (size_t)(1 + npeaks) * (size_t)N;
-    if (kind == 4 || kind == 6) HIP_TRY(c->fb_out.reserve(fb_bytes));
-    const int rc = kind == 4 || kind == 6
-                       ? full_fb_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, mode,
-                                     static_cast<float *>(c->out.p), d_cand, static_cast<float *>(c->fb_out.p), c->stream, kind == 6)
-                   : kind == 5 ? wide_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
-                                        static_cast<float *>(c->out.p), d_cand, surf ? static_cast<float *>(c->full_surf.p) : nullptr, c->stream,
-                                        entry)
-                   : kind == 3 ? full_any_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap, mode,
-                                            static_cast<float *>(c->out.p), d_cand, surf ? static_cast<float *>(c->full_surf.p) : nullptr,
-                                            c->stream)
-                   : kind == 2 ? full_dn_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
-                                           static_cast<float *>(c->out.p), d_cand, c->stream)
-                   : planes ? full_planes_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
-                                              static_cast<float *>(c->out.p), d_cand, c->stream)
-                          : full_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, npeaks, swap,
-                                     static_cast<float *>(c->out.p), d_cand, c->stream,
-                                     multi ? "mimc3_match_ncc_full_multi_dev" : "mimc3_match_ncc_full_dev");
-    if (rc) return rc;
-    RC_TRY(d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N));
-    if (multi) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
-    if ((kind == 3 || kind == 5) && surf) RC_TRY(d2h_copy(c, surf, c->full_surf.p, surf_bytes));
-    if (kind == 4 || kind == 6) RC_TRY(d2h_copy(c, fb, c->fb_out.p, fb_bytes));
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_full(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                    int32_t ocw, int32_t R, int32_t swap, float *out)
-{
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, 0, swap, out, nullptr, false, "mimc3_match_ncc_full");
-}
-
-extern "C" int mimc3_match_ncc_full_multi(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                          int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand)
-{
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, true, "mimc3_match_ncc_full_multi");
-}
-
-// ---------------------------------------------------------------------------------------------
-// the exhaustive search on the planes the context matches on (mimc3_match_ncc_full_planes): an 8-bit pair through the entries above,
-// untouched; a scaled-integer pair (12-bit DN, a filtered 8-bit pair) through match_full_u16_kernel.hip on its u16 planes
-// ---------------------------------------------------------------------------------------------
-static int full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream, const char *entry)
-{
-    const std::string en(entry);
-    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
-    if (c->u8_ok || !c->d_i0 || !c->d_i1 || c->child || !full_ocw_ok(ocw) || R < 1 || R > 15)      // (the 8-bit path, and every refusal it shares)
-        return full_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream, en.c_str());
-    if (!c->u16_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit nor scaled-integer (u8 or u16 planes only)");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!c->hpl_valid || !c->sat_u16_ok) RC_TRY(build_u16(c, true));
-    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
-    u.full_shift = d_shift; u.full_R = R;
-    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
-    u.p0 = static_cast<const unsigned char *>(c->hpl0.p); u.p1 = static_cast<const unsigned char *>(c->hpl1.p);
-    u.sat0 = c->hsat0.p; u.sat1 = c->hsat1.p; u.satz0 = c->hsz0.p; u.satz1 = c->hsz1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    const hipError_t e = mimc3::launch_match_full_u16(u, s);
-    if (e != hipSuccess) return mimc3::hip_fail(e, "full-search u16 kernel launch");
-    c->last_path = 7;
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_full_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                               const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap,
-                                               float *d_out, float *d_cand, void *stream)
-{
-    return full_planes_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream);
-}
-
-extern "C" int mimc3_match_ncc_full_planes(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand)
-{
-    const char *en = "mimc3_match_ncc_full_planes";
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 1);
-}
-
-// ---------------------------------------------------------------------------------------------
-// the exhaustive search on every class the planes' matchers take (mimc3_match_ncc_full_dn): 8-bit and scaled-integer pairs through the
-// entries above, untouched; an integral-f32 pair (16-bit DN and its filtered forms: every pixel x 1 or x 8 an integer in [0, 2^20))
-// through match_full_f32_kernel.hip on its f32 planes and 16-byte tables (build_f32)
-// ---------------------------------------------------------------------------------------------
-// the class of a pair that is neither 8-bit nor scaled-integer: its f32 planes and tables are built on first use (drains the stream)
-static int full_dn_class(mimc3_ctx *c, const std::string &en)
-{
-    if (c->u8_ok || c->u16_ok) return 0;
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->fplanes_ok) RC_TRY(build_f32(c));
-    if (!c->f32i_ok)
-        return mimc3::fail(MIMC3_EUNSUPPORTED, en + ": the pair is neither 8-bit, scaled-integer nor integral f32 (pixels x 1 or x 8 integers below 2^20)");
-    return 0;
-}
-
-static int full_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                       int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, void *stream)
-{
-    const char *entry = "mimc3_match_ncc_full_dn_dev";
-    const std::string en(entry);
-    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
-    if (c->u8_ok || c->u16_ok || !c->d_i0 || !c->d_i1 || c->child || !full_ocw_ok(ocw) || R < 1 || R > 15)      // (the other classes, and every refusal they share)
-        return full_planes_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream, entry);
-    RC_TRY(full_dn_class(c, en));
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
-    u.full_shift = d_shift; u.full_R = R;
-    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
-    u.p0 = static_cast<const unsigned char *>(c->fpl0.p); u.p1 = static_cast<const unsigned char *>(c->fpl1.p);
-    u.sat0 = c->fsat0.p; u.sat1 = c->fsat1.p; u.sat_ws = mimc3::sat_pitch(c->Wp);
-    u.scale0 = 1.0 / (double)(1 << c->fshift0); u.scale1 = 1.0 / (double)(1 << c->fshift1);
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    const hipError_t e = mimc3::launch_match_full_f32(u, s);
-    if (e != hipSuccess) return mimc3::hip_fail(e, "full-search f32 kernel launch");
-    c->last_path = 8;
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_full_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                           const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap,
-                                           float *d_out, float *d_cand, void *stream)
-{
-    return full_dn_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream);
-}
-
-extern "C" int mimc3_match_ncc_full_dn(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                       int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand)
-{
-    const char *en = "mimc3_match_ncc_full_dn";
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 2);
-}
-
-// ---------------------------------------------------------------------------------------------
-// the exhaustive search on any f32 pair (mimc3_match_ncc_full_any): mode 0 sends the classes above where mimc3_match_ncc_full_dn sends
-// them, untouched, and every other pair (non-integral pixels, NaN or negative nulls, values of 2^20 and above) through
-// match_full_f32g_kernel.hip on its f32 planes (build_f32; no tables); mode 1 sends any pair through that kernel.  Only that kernel
-// serves the surfaces
-// ---------------------------------------------------------------------------------------------
-static int full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                        int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out, float *d_cand, float *d_surf,
-                        void *stream)
-{
-    const std::string en("mimc3_match_ncc_full_any_dev");
-    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
-    if (mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..15");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    HIP_TRY(hipSetDevice(c->device));
-    bool general = mode == 1;
-    if (!general && !c->u8_ok && !c->u16_ok) {          // the class of an f32 pair: its planes are built on first use (drains the stream)
-        if (!c->fplanes_ok) RC_TRY(build_f32(c));
-        general = !c->f32i_ok;
-    }
-    if (!general) {
-        if (d_surf) return mimc3::fail(MIMC3_EINVAL, en + ": only the float kernel serves the surfaces (mode 1, or a pair of no integer class)");
-        return full_dn_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, stream);
-    }
-    // (mode 1 on an 8-bit or scaled-integer pair: build_f32 also classifies the pair as integral f32 and builds the 16-byte tables, which
-    //  this kernel never reads -- once per pair, on the path of tests and surfaces; the planes are the same ones either way)
-    if (!c->fplanes_ok) RC_TRY(build_f32(c));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
-    u.full_shift = d_shift; u.full_R = R;
-    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
-    u.p0 = static_cast<const unsigned char *>(c->fpl0.p); u.p1 = static_cast<const unsigned char *>(c->fpl1.p);
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    const hipError_t e = mimc3::launch_match_full_f32g(u, d_surf, s);
-    if (e != hipSuccess) return mimc3::hip_fail(e, "full-search general f32 kernel launch");
-    c->last_path = 9;
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_full_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                            const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
-                                            float *d_out, float *d_cand, float *d_surf, void *stream)
-{
-    return full_any_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, d_surf, stream);
-}
-
-extern "C" int mimc3_match_ncc_full_any(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                        int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *out, float *cand,
-                                        float *surf)
-{
-    const char *en = "mimc3_match_ncc_full_any";
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 3, mode, surf);
-}
-
-// ---------------------------------------------------------------------------------------------
-// the exhaustive search beyond +-15 px (mimc3_match_ncc_wide): mimc3_match_ncc_full_any in mode 1 with R up to
-// mimc3_wide_max_radius(ocw).  R <= 15 IS that entry (the float kernel, its bytes); R >= 16 runs match_wide_kernel.hip on the same planes
-// ---------------------------------------------------------------------------------------------
-extern "C" int mimc3_wide_max_radius(int32_t ocw) { return full_ocw_ok(ocw) ? mimc3::wide_max_radius(ocw) : 0; }
-extern "C" int mimc3_wide_lds_bytes(int32_t ocw, int32_t R) { return full_ocw_ok(ocw) ? mimc3::wide_lds_bytes(ocw, R) : 0; }
-
-static int wide_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                    int32_t R, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, float *d_surf, void *stream, const char *entry)
-{
-    // (the refusals are the _dev entry's own; the host entry has made them already, under its name, before it uploads anything)
-    const std::string en(entry);
-    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (R < 1 || R > mimc3::wide_max_radius(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1..mimc3_wide_max_radius(ocw)");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    if (R <= 15) return full_any_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, 1, d_out, d_cand, d_surf, stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->fplanes_ok) RC_TRY(build_f32(c));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    mimc3::MatchU8Args u = u8_args(c, d_xyuvav, 6, 2, N, off_u, off_v, ocw, swap, d_out);
-    u.full_shift = d_shift; u.full_R = R;
-    if (d_cand) { u.full_cand = d_cand; u.full_npeaks = npeaks; }
-    u.p0 = static_cast<const unsigned char *>(c->fpl0.p); u.p1 = static_cast<const unsigned char *>(c->fpl1.p);
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    const hipError_t e = mimc3::launch_match_wide(u, d_surf, s);
-    if (e != hipSuccess) return mimc3::hip_fail(e, "wide-search kernel launch");
-    c->last_path = 10;
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_wide_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                        const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
-                                        float *d_cand, float *d_surf, void *stream)
-{
-    return wide_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, d_out, d_cand, d_surf, stream);
-}
-
-extern "C" int mimc3_match_ncc_wide(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                    int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand, float *surf)
-{
-    const char *en = "mimc3_match_ncc_wide";
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, swap, out, cand, npeaks > 0, en, 5, 1, surf);
-}
-
-// ---------------------------------------------------------------------------------------------
-// forward-backward consistency of the exhaustive search (mimc3_match_ncc_full_fb, fb_kernel.hip): the forward pass of
-// mimc3_match_ncc_full_any, then ONE backward pass (swap 1) over the record and the candidates of every point -- (1 + npeaks) N rows,
-// seeded on the device from the forward results -- and the fb rows composed from it; all on the caller's stream, no host round trip.
-// wide (mimc3_match_ncc_wide_fb): the same under mimc3_match_ncc_wide's definition -- both passes are wide_dev (mode 1), R up to
-// mimc3_wide_max_radius(ocw); R <= 15 is then mimc3_match_ncc_full_fb(mode 1) call for call
-// ---------------------------------------------------------------------------------------------
-static int full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                       int32_t R, int32_t npeaks, int32_t mode, float *d_out, float *d_cand, float *d_fb, void *stream, bool wide)
-{
-    const std::string en(wide ? "mimc3_match_ncc_wide_fb_dev" : "mimc3_match_ncc_full_fb_dev");
-    // mimc3_match_ncc_full_any_dev's refusals (wide: mimc3_match_ncc_wide_dev's), under this entry's name and before anything is allocated
-    if (!c || !d_xyuvav || !d_out || !d_fb || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
-    if (mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (wide ? (R < 1 || R > mimc3::wide_max_radius(ocw)) : (R < 1 || R > 15))
-        return mimc3::fail(MIMC3_EINVAL, en + (wide ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    const size_t rows = (size_t)(1 + npeaks) * (size_t)N;
-    if (rows > (size_t)INT32_MAX) return mimc3::fail(MIMC3_EINVAL, en + ": (1 + npeaks) N must fit an int32");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool timing = c->timing;
-    // all scratch before anything is enqueued (a buffer that grows is freed first, and hipFree waits for the device): the backward rows,
-    // and the class bytes of the matrix-core search at the backward pass's size, which the forward pass would otherwise size for N
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->fb_xy.reserve(sizeof(double) * 6 * rows));
-    HIP_TRY(c->fb_sh.reserve(sizeof(int32_t) * 2 * rows));
-    HIP_TRY(c->fb_rec.reserve(sizeof(float) * 8 * rows));
-    HIP_TRY(c->fb_why.reserve(rows));
-    if (c->u8_ok && mode == 0) HIP_TRY(c->mxl[0].reserve(rows));
-    if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    c->timing = false;                  // (the events bracket the whole call, not its last search)
-    // the forward pass: mimc3_match_ncc_full_any_dev (wide: mimc3_match_ncc_wide_dev) itself, with its refusals
-    int rc = wide ? wide_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, 0, d_out, d_cand, nullptr, stream, en.c_str())
-                  : full_any_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, 0, mode, d_out, d_cand, nullptr, stream);
-    if (rc) { c->timing = timing; return rc; }
-    const int forward_path = c->last_path;
-    double *xy2 = static_cast<double *>(c->fb_xy.p);
-    int32_t *sh2 = static_cast<int32_t *>(c->fb_sh.p);
-    float *back = static_cast<float *>(c->fb_rec.p);
-    uint8_t *why = static_cast<uint8_t *>(c->fb_why.p);
-    hipError_t e = mimc3::launch_fb_seed(d_xyuvav, N, off_u, off_v, d_out, d_cand, npeaks, ocw, c->H, c->W, xy2, sh2, why, s);
-    if (e != hipSuccess) { c->timing = timing; return mimc3::hip_fail(e, "fb seed kernel launch"); }
-    // the backward pass: the chip from i1 at m, the search in i0 around m - offset - r = uv0 (inside the 256-px zero border: the box is
-    // centred on uv0, which lies in the image, and R + ocw <= 15 + 40; wide: R + ocw <= 47 + 32 = 79)
-    rc = wide ? wide_dev(c, xy2, (int32_t)rows, -off_u, -off_v, sh2, ocw, R, 0, 1, back, nullptr, nullptr, stream, en.c_str())
-              : full_any_dev(c, xy2, (int32_t)rows, -off_u, -off_v, sh2, ocw, R, 0, 1, mode, back, nullptr, nullptr, stream);
-    c->timing = timing;
-    c->last_path = forward_path;
-    if (rc) return rc;
-    e = mimc3::launch_fb_compose(d_out, d_cand, N, npeaks, back, why, d_fb, s);
-    if (e != hipSuccess) return mimc3::hip_fail(e, "fb compose kernel launch");
-    if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_full_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                           const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t mode, float *d_out,
-                                           float *d_cand, float *d_fb, void *stream)
-{
-    return full_fb_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, mode, d_out, d_cand, d_fb, stream);
-}
-
-extern "C" int mimc3_match_ncc_full_fb(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                       int32_t ocw, int32_t R, int32_t npeaks, int32_t mode, float *out, float *cand, float *fb)
-{
-    const char *en = "mimc3_match_ncc_full_fb";
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, 0, out, cand, npeaks > 0, en, 4, mode, nullptr, fb);
-}
-
-extern "C" int mimc3_match_ncc_wide_fb_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                           const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, float *d_out, float *d_cand,
-                                           float *d_fb, void *stream)
-{
-    return full_fb_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, 1, d_out, d_cand, d_fb, stream, true);
-}
-
-extern "C" int mimc3_match_ncc_wide_fb(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                       int32_t ocw, int32_t R, int32_t npeaks, float *out, float *cand, float *fb)
-{
-    const char *en = "mimc3_match_ncc_wide_fb";
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": cand goes with npeaks > 0");
-    return full_host(c, xyuvav, N, offset, shift, ocw, R, npeaks, 0, out, cand, npeaks > 0, en, 6, 1, nullptr, fb);
-}
-
-// ---------------------------------------------------------------------------------------------
-// NCC stacking (mimc3_stack_*, stack_kernel.hip): the surfaces of several pairs -- each a mimc3_match_ncc_full_any(mode 1) layer on the
-// pair that is resident, or a caller's array -- accumulated per cell in f64, and the tail of the exhaustive search over their mean.
-// The stack is state of the context that the image setters do not touch.  Every entry validates everything before its first launch.
-// ---------------------------------------------------------------------------------------------
-static void stack_release(mimc3_ctx *c)
-{
-    auto &k = c->stk;
-    for (DevBuf *b : {&k.sum, &k.cnt, &k.lay, &k.shift, &k.wsum, &k.lsh, &k.layer, &k.rec, &k.ref, &k.out, &k.cand, &k.surf, &k.count})
-        b->release();
-    std::vector<int32_t>().swap(k.h_shift);
-    k.N = 0; k.R = 0; k.layers = 0; k.weighted = false;
-}
-
-static inline size_t stack_cells(const mimc3_ctx *c) { return (size_t)((2 * c->stk.R + 1) * (2 * c->stk.R + 1)); }
-// the weights' sums from cell `cell0` on; null on a stack that is not weighted
-static inline double *stack_wsum(const mimc3_ctx *c, size_t cell0)
-{
-    return c->stk.weighted ? static_cast<double *>(c->stk.wsum.p) + cell0 : nullptr;
-}
-
-// (max_R 15: mimc3_stack_begin; 47: mimc3_stack_begin_wide -- one text, so a stack of R <= 15 is the same state through either)
-static int stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift, int max_R, const char *entry)
-{
-    const std::string en(entry);
-    if (!c || N < 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    HIP_TRY(hipSetDevice(c->device));
-    if (N == 0) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        stack_release(c);
-        return 0;
-    }
-    if (R < 1 || R > max_R) return mimc3::fail(MIMC3_EINVAL, en + ": R must be in 1.." + std::to_string(max_R));
-    auto &k = c->stk;
-    k.N = 0; k.R = 0; k.layers = 0;                             // (no stack while this one is being sized)
-    if (k.weighted || k.wsum.p) {                               // the new stack is not weighted: 10 bytes per cell again
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        k.wsum.release();
-        k.weighted = false;
-    }
-    const size_t NC = (size_t)((2 * R + 1) * (2 * R + 1)), cells = (size_t)N * NC;
-    HIP_TRY(k.sum.reserve(sizeof(double) * cells));
-    HIP_TRY(k.cnt.reserve(sizeof(uint16_t) * cells));
-    HIP_TRY(k.lay.reserve(sizeof(uint16_t) * (size_t)N));
-    HIP_TRY(k.shift.reserve(sizeof(int32_t) * 2 * (size_t)N));
-    HIP_TRY(hipMemsetAsync(k.sum.p, 0, sizeof(double) * cells, c->stream));
-    HIP_TRY(hipMemsetAsync(k.cnt.p, 0, sizeof(uint16_t) * cells, c->stream));
-    HIP_TRY(hipMemsetAsync(k.lay.p, 0, sizeof(uint16_t) * (size_t)N, c->stream));
-    k.h_shift.assign(2 * (size_t)N, 0);
-    if (shift) {
-        std::memcpy(k.h_shift.data(), shift, sizeof(int32_t) * 2 * (size_t)N);
-        RC_TRY(h2d_copy(c, k.shift.p, shift, sizeof(int32_t) * 2 * (size_t)N));
-    } else {
-        HIP_TRY(hipMemsetAsync(k.shift.p, 0, sizeof(int32_t) * 2 * (size_t)N, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));                   // (the adds may come in on another stream)
-    k.N = N; k.R = R;
-    return 0;
-}
-
-extern "C" int mimc3_stack_begin(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift)
-{
-    return stack_begin(c, N, R, shift, 15, "mimc3_stack_begin");
-}
-
-extern "C" int mimc3_stack_begin_wide(mimc3_ctx *c, int32_t N, int32_t R, const int32_t *shift)
-{
-    return stack_begin(c, N, R, shift, mimc3::kStackMaxRadius, "mimc3_stack_begin_wide");
-}
-
-extern "C" int32_t mimc3_stack_chunk(int32_t R) { return mimc3::stack_chunk(R); }
-
-extern "C" int mimc3_stack_info(mimc3_ctx *c, int32_t *N, int32_t *R, int32_t *layers)
-{
-    if (!c) return mimc3::fail(MIMC3_EINVAL, "mimc3_stack_info: bad argument");
-    if (N) *N = c->stk.N;
-    if (R) *R = c->stk.R;
-    if (layers) *layers = c->stk.layers;
-    return 0;
-}
-
-// what every add checks about the stack itself
-static int stack_add_state(mimc3_ctx *c, int32_t N, const std::string &en)
-{
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    if (c->stk.N == 0) return mimc3::fail(MIMC3_ESTATE, en + ": no stack (mimc3_stack_begin)");
-    if (N != c->stk.N) return mimc3::fail(MIMC3_EINVAL, en + ": N differs from the stack's");
-    if (c->stk.layers >= 65535) return mimc3::fail(MIMC3_ESTATE, en + ": the stack holds 65,535 layers");
-    return 0;
-}
-
-// a layer of a stack beyond R 15 is mimc3_match_ncc_wide's: the chip size must take the stack's radius (ocw is one of the six)
-static int stack_add_radius(mimc3_ctx *c, int32_t ocw, const std::string &en)
-{
-    if (c->stk.R > 15 && c->stk.R > mimc3::wide_max_radius(ocw))
-        return mimc3::fail(MIMC3_EINVAL, en + ": the stack's R exceeds mimc3_wide_max_radius(ocw)");
-    return 0;
-}
-
-static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
-                         void *stream, const char *entry)
-{
-    const std::string en(entry);
-    // mimc3_match_ncc_full_any_dev's refusals and the stack's own, before anything is allocated or enqueued
-    if (!c || !d_xyuvav || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    RC_TRY(stack_add_state(c, N, en));
-    RC_TRY(stack_add_radius(c, ocw, en));
-    auto &k = c->stk;
-    const size_t NC = stack_cells(c);
-    const size_t chunk = (size_t)(N < mimc3::stack_chunk(k.R) ? N : mimc3::stack_chunk(k.R));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NC));
-    HIP_TRY(k.rec.reserve(sizeof(float) * 8 * chunk));
-    if (!c->fplanes_ok) RC_TRY(build_f32(c));                   // (the float kernel's planes: built on the context's stream, which it drains)
-    const bool timing = c->timing;
-    if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    c->timing = false;                  // (the events bracket the whole call)
-    float *layer = static_cast<float *>(k.layer.p), *rec = static_cast<float *>(k.rec.p);
-    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
-        const int32_t n = (int32_t)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
-        // (beyond R 15 the layer is mimc3_match_ncc_wide's, through the path that entry takes)
-        const int32_t *sh = static_cast<const int32_t *>(k.shift.p) + 2 * g0;
-        const int rc = k.R > 15 ? wide_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, sh, ocw, k.R, 0, swap, rec, nullptr, layer, stream, entry)
-                                : full_any_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, sh, ocw, k.R, 0, swap, 1, rec, nullptr, layer, stream);
-        if (rc) { c->timing = timing; return rc; }
-        const hipError_t e = mimc3::launch_stack_add(layer, rec, nullptr, n, (int)NC, static_cast<double *>(k.sum.p) + g0 * NC,
-                                                     static_cast<uint16_t *>(k.cnt.p) + g0 * NC, static_cast<uint16_t *>(k.lay.p) + g0,
-                                                     stack_wsum(c, g0 * NC), s);
-        if (e != hipSuccess) { c->timing = timing; return mimc3::hip_fail(e, "stack add kernel launch"); }
-    }
-    c->timing = timing;
-    k.layers++;
-    if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
-                                   void *stream)
-{
-    return stack_add_dev(c, d_xyuvav, N, off_u, off_v, ocw, swap, stream, "mimc3_stack_add_dev");
-}
-
-extern "C" int mimc3_stack_add(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap)
-{
-    const char *entry = "mimc3_stack_add";
-    const std::string en(entry);
-    if (!c || !xyuvav || !offset || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    RC_TRY(stack_add_state(c, N, en));
-    RC_TRY(stack_add_radius(c, ocw, en));
-    // the chip inside the image, the search box inside the planes' zero border (as mimc3_match_ncc_full_any's host entry)
-    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
-    const int64_t pad = mimc3::kU8Pad, h = c->stk.R + ocw;
-    const int32_t *shift = c->stk.h_shift.data();
-    for (int32_t g = 0; g < N; ++g) {
-        const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
-        const int64_t cu = (int64_t)u0 + offset[0] + shift[2 * (size_t)g], cv = (int64_t)v0 + offset[1] + shift[2 * (size_t)g + 1];
-        if (cu - h < -pad || cu + h >= c->W + pad || cv - h < -pad || cv + h >= c->H + pad)
-            return mimc3::fail(MIMC3_EBOUNDS, en + ": grid point " + std::to_string(g) + " search box leaves the zero border");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
-    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
-    RC_TRY(stack_add_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, swap, c->stream, entry));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int mimc3_stack_add_surfaces_dev(mimc3_ctx *c, const float *d_surf, const uint8_t *d_refused, int32_t N, void *stream)
-{
-    const std::string en("mimc3_stack_add_surfaces_dev");
-    if (!c || !d_surf || N <= 0 || (reinterpret_cast<uintptr_t>(d_surf) & 3u)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    RC_TRY(stack_add_state(c, N, en));
-    auto &k = c->stk;
-    const size_t NC = stack_cells(c), chunk = (size_t)mimc3::stack_chunk(k.R);
-    HIP_TRY(hipSetDevice(c->device));
-    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
-        const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
-        const hipError_t e = mimc3::launch_stack_add(d_surf + g0 * NC, nullptr, d_refused ? d_refused + g0 : nullptr, n, (int)NC,
-                                                     static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
-                                                     static_cast<uint16_t *>(k.lay.p) + g0, stack_wsum(c, g0 * NC),
-                                                     static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return mimc3::hip_fail(e, "stack add kernel launch");
-    }
-    k.layers++;
-    return 0;
-}
-
-extern "C" int mimc3_stack_add_surfaces(mimc3_ctx *c, const float *surf, const uint8_t *refused, int32_t N)
-{
-    const std::string en("mimc3_stack_add_surfaces");
-    if (!c || !surf || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    RC_TRY(stack_add_state(c, N, en));
-    auto &k = c->stk;
-    const size_t NC = stack_cells(c);
-    const size_t chunk = (size_t)(N < mimc3::stack_chunk(k.R) ? N : mimc3::stack_chunk(k.R));
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NC));
-    if (refused) {
-        HIP_TRY(k.ref.reserve((size_t)N));
-        RC_TRY(h2d_copy(c, k.ref.p, refused, (size_t)N));
-    }
-    // one chunk of surfaces at a time through the layer scratch; copies and launches are ordered on the context's stream
-    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
-        const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
-        RC_TRY(h2d_copy(c, k.layer.p, surf + g0 * NC, sizeof(float) * (size_t)n * NC));
-        const hipError_t e = mimc3::launch_stack_add(static_cast<const float *>(k.layer.p), nullptr,
-                                                     refused ? static_cast<const uint8_t *>(k.ref.p) + g0 : nullptr, n, (int)NC,
-                                                     static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
-                                                     static_cast<uint16_t *>(k.lay.p) + g0, stack_wsum(c, g0 * NC), c->stream);
-        if (e != hipSuccess) return mimc3::hip_fail(e, "stack add kernel launch");
-    }
-    k.layers++;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// ---- layers of another time baseline: scaled and weighted (the definition is in include/mimc3_hip.h) ----
-static inline bool stack_scale_ok(double s) { return s >= 1.0 / 64 && s <= 64.0; }                // (false for NaN)
-static inline bool stack_weight_ok(double w) { return w > 0.0 && std::isfinite(w); }
-
-extern "C" int32_t mimc3_stack_layer_radius(int32_t R, double scale)
-{
-    if (R < 1 || R > mimc3::kStackMaxRadius || !stack_scale_ok(scale)) return 0;
-    return scale == 1.0 ? R : (int32_t)std::floor(scale * (double)R + 0.5) + 1;
-}
-
-// the layer shift of every point from the stack's host shift; MIMC3_EINVAL where |scale shift| >= 2^30.  out may be null (the check alone)
-static int stack_layer_shift(const mimc3_ctx *c, double scale, int32_t *out, const std::string &en)
-{
-    const std::vector<int32_t> &sh = c->stk.h_shift;
-    for (size_t i = 0; i < sh.size(); ++i) {
-        const double p = scale * (double)sh[i];
-        if (!(std::fabs(p) < 1073741824.0)) return mimc3::fail(MIMC3_EINVAL, en + ": |scale x shift| must be below 2^30");
-        if (out) out[i] = (int32_t)std::nearbyint(p);           // (half to even: the default rounding mode, which nothing here changes)
-    }
-    return 0;
-}
-
-// what every scaled add checks beyond its pointers, before anything is allocated or enqueued
-static int stack_scaled_check(mimc3_ctx *c, int32_t N, int32_t layer_R, int32_t max_R, double scale, double weight, const std::string &en)
-{
-    RC_TRY(stack_add_state(c, N, en));
-    if (!stack_scale_ok(scale)) return mimc3::fail(MIMC3_EINVAL, en + ": scale must be in 1/64..64");
-    if (!stack_weight_ok(weight)) return mimc3::fail(MIMC3_EINVAL, en + ": weight must be finite and > 0");
-    if (layer_R < 1 || layer_R > max_R)
-        return mimc3::fail(MIMC3_EINVAL, en + ": layer_R must be in 1.." + std::to_string(max_R));
-    return stack_layer_shift(c, scale, nullptr, en);
-}
-
-extern "C" int mimc3_stack_layer_shift(mimc3_ctx *c, double scale, int32_t *out)
-{
-    const std::string en("mimc3_stack_layer_shift");
-    if (!c || !out) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (c->stk.N == 0) return mimc3::fail(MIMC3_ESTATE, en + ": no stack (mimc3_stack_begin)");
-    if (!stack_scale_ok(scale)) return mimc3::fail(MIMC3_EINVAL, en + ": scale must be in 1/64..64");
-    return stack_layer_shift(c, scale, out, en);
-}
-
-extern "C" int mimc3_stack_weighted(mimc3_ctx *c) { return c && c->stk.N != 0 && c->stk.weighted ? 1 : 0; }
-
-// the points of one launch of a scaled add: neither the layer's slice nor the stack's exceeds kStackChunkCells
-static inline size_t stack_scaled_chunk(const mimc3_ctx *c, int32_t N, int32_t layer_R)
-{
-    const int a = mimc3::stack_chunk(c->stk.R), b = mimc3::stack_chunk(layer_R);
-    const int m = a < b ? a : b;
-    return (size_t)(N < m ? N : m);
-}
-
-// What a scaled add enqueues on `s` before its first chunk: the wsum plane of a stack that this add makes weighted, and the layer shift.
-// Called after every check has passed.
-static int stack_scaled_prepare(mimc3_ctx *c, double scale, double weight, hipStream_t s)
-{
-    auto &k = c->stk;
-    const size_t cells = (size_t)k.N * stack_cells(c);
-    HIP_TRY(k.lsh.reserve(sizeof(int32_t) * 2 * (size_t)k.N));
-    if (weight != 1.0 && !k.weighted) {
-        HIP_TRY(k.wsum.reserve(sizeof(double) * cells));
-        const hipError_t e = mimc3::launch_stack_wsum_init(static_cast<const uint16_t *>(k.cnt.p), cells, static_cast<double *>(k.wsum.p), s);
-        if (e != hipSuccess) return mimc3::hip_fail(e, "stack wsum kernel launch");
-        k.weighted = true;
-    }
-    const hipError_t e = mimc3::launch_stack_layer_shift(static_cast<const int32_t *>(k.shift.p), k.N, scale, static_cast<int32_t *>(k.lsh.p), s);
-    if (e != hipSuccess) return mimc3::hip_fail(e, "stack layer-shift kernel launch");
-    return 0;
-}
-
-static int stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t layer_R,
-                                int32_t swap, double scale, double weight, void *stream, const char *entry)
-{
-    const std::string en(entry);
-    if (!c || !d_xyuvav || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::wide_max_radius(ocw), scale, weight, en));
-    auto &k = c->stk;
-    const size_t NC = stack_cells(c), NCl = (size_t)((2 * layer_R + 1) * (2 * layer_R + 1));
-    const size_t chunk = stack_scaled_chunk(c, N, layer_R);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NCl));
-    HIP_TRY(k.rec.reserve(sizeof(float) * 8 * chunk));
-    if (!c->fplanes_ok) RC_TRY(build_f32(c));                   // (as mimc3_stack_add_dev)
-    const bool timing = c->timing;
-    if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    c->timing = false;                  // (the events bracket the whole call)
-    const int rp = stack_scaled_prepare(c, scale, weight, s);
-    if (rp) { c->timing = timing; return rp; }
-    float *layer = static_cast<float *>(k.layer.p), *rec = static_cast<float *>(k.rec.p);
-    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
-        const int32_t n = (int32_t)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
-        const int32_t *lsh = static_cast<const int32_t *>(k.lsh.p) + 2 * g0;
-        // mimc3_match_ncc_wide(npeaks 0, shift = the layer shift, R = layer_R, surf): the float kernel up to 15, the wide kernel beyond
-        const int rc = wide_dev(c, d_xyuvav + 6 * g0, n, off_u, off_v, lsh, ocw, layer_R, 0, swap, rec, nullptr, layer, stream, entry);
-        if (rc) { c->timing = timing; return rc; }
-        const hipError_t e = mimc3::launch_stack_add_scaled(layer, rec, nullptr, static_cast<const int32_t *>(k.shift.p) + 2 * g0, lsh, n, k.R,
-                                                            layer_R, scale, weight, static_cast<double *>(k.sum.p) + g0 * NC,
-                                                            static_cast<uint16_t *>(k.cnt.p) + g0 * NC, stack_wsum(c, g0 * NC),
-                                                            static_cast<uint16_t *>(k.lay.p) + g0, s);
-        if (e != hipSuccess) { c->timing = timing; return mimc3::hip_fail(e, "scaled stack add kernel launch"); }
-    }
-    c->timing = timing;
-    k.layers++;
-    if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
-                                          int32_t layer_R, int32_t swap, double scale, double weight, void *stream)
-{
-    return stack_add_scaled_dev(c, d_xyuvav, N, off_u, off_v, ocw, layer_R, swap, scale, weight, stream, "mimc3_stack_add_scaled_dev");
-}
-
-extern "C" int mimc3_stack_add_scaled(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t layer_R,
-                                      int32_t swap, double scale, double weight)
-{
-    const char *entry = "mimc3_stack_add_scaled";
-    const std::string en(entry);
-    if (!c || !xyuvav || !offset || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, en + ": images not set");
-    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::wide_max_radius(ocw), scale, weight, en));
-    // the chip inside the image, the layer's search box inside the planes' zero border (as mimc3_stack_add, around the layer shift)
-    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
-    const int64_t pad = mimc3::kU8Pad, h = layer_R + ocw;
-    const int32_t *shift = c->stk.h_shift.data();
-    for (int32_t g = 0; g < N; ++g) {
-        const int32_t u0 = (int32_t)xyuvav[6 * (size_t)g + 2], v0 = (int32_t)xyuvav[6 * (size_t)g + 3];
-        const int64_t lu = (int64_t)std::nearbyint(scale * (double)shift[2 * (size_t)g]);
-        const int64_t lv = (int64_t)std::nearbyint(scale * (double)shift[2 * (size_t)g + 1]);
-        const int64_t cu = (int64_t)u0 + offset[0] + lu, cv = (int64_t)v0 + offset[1] + lv;
-        if (cu - h < -pad || cu + h >= c->W + pad || cv - h < -pad || cv + h >= c->H + pad)
-            return mimc3::fail(MIMC3_EBOUNDS, en + ": grid point " + std::to_string(g) + " search box leaves the zero border");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
-    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
-    RC_TRY(stack_add_scaled_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, layer_R, swap, scale, weight,
-                                c->stream, entry));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int mimc3_stack_add_surfaces_scaled_dev(mimc3_ctx *c, const float *d_surf, const uint8_t *d_refused, int32_t N, int32_t layer_R,
-                                                   double scale, double weight, void *stream)
-{
-    const std::string en("mimc3_stack_add_surfaces_scaled_dev");
-    if (!c || !d_surf || N <= 0 || (reinterpret_cast<uintptr_t>(d_surf) & 3u)) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::kStackMaxRadius, scale, weight, en));
-    auto &k = c->stk;
-    const size_t NC = stack_cells(c), NCl = (size_t)((2 * layer_R + 1) * (2 * layer_R + 1)), chunk = stack_scaled_chunk(c, N, layer_R);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    RC_TRY(stack_scaled_prepare(c, scale, weight, s));
-    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
-        const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
-        const hipError_t e = mimc3::launch_stack_add_scaled(d_surf + g0 * NCl, nullptr, d_refused ? d_refused + g0 : nullptr,
-                                                            static_cast<const int32_t *>(k.shift.p) + 2 * g0,
-                                                            static_cast<const int32_t *>(k.lsh.p) + 2 * g0, n, k.R, layer_R, scale, weight,
-                                                            static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
-                                                            stack_wsum(c, g0 * NC), static_cast<uint16_t *>(k.lay.p) + g0, s);
-        if (e != hipSuccess) return mimc3::hip_fail(e, "scaled stack add kernel launch");
-    }
-    k.layers++;
-    return 0;
-}
-
-extern "C" int mimc3_stack_add_surfaces_scaled(mimc3_ctx *c, const float *surf, const uint8_t *refused, int32_t N, int32_t layer_R,
-                                               double scale, double weight)
-{
-    const std::string en("mimc3_stack_add_surfaces_scaled");
-    if (!c || !surf || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::kStackMaxRadius, scale, weight, en));
-    auto &k = c->stk;
-    const size_t NC = stack_cells(c), NCl = (size_t)((2 * layer_R + 1) * (2 * layer_R + 1)), chunk = stack_scaled_chunk(c, N, layer_R);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NCl));
-    if (refused) {
-        HIP_TRY(k.ref.reserve((size_t)N));
-        RC_TRY(h2d_copy(c, k.ref.p, refused, (size_t)N));
-    }
-    RC_TRY(stack_scaled_prepare(c, scale, weight, c->stream));
-    // one chunk of surfaces at a time through the layer scratch; copies and launches are ordered on the context's stream
-    for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
-        const int n = (int)((size_t)N - g0 < chunk ? (size_t)N - g0 : chunk);
-        RC_TRY(h2d_copy(c, k.layer.p, surf + g0 * NCl, sizeof(float) * (size_t)n * NCl));
-        const hipError_t e = mimc3::launch_stack_add_scaled(static_cast<const float *>(k.layer.p), nullptr,
-                                                            refused ? static_cast<const uint8_t *>(k.ref.p) + g0 : nullptr,
-                                                            static_cast<const int32_t *>(k.shift.p) + 2 * g0,
-                                                            static_cast<const int32_t *>(k.lsh.p) + 2 * g0, n, k.R, layer_R, scale, weight,
-                                                            static_cast<double *>(k.sum.p) + g0 * NC, static_cast<uint16_t *>(k.cnt.p) + g0 * NC,
-                                                            stack_wsum(c, g0 * NC), static_cast<uint16_t *>(k.lay.p) + g0, c->stream);
-        if (e != hipSuccess) return mimc3::hip_fail(e, "scaled stack add kernel launch");
-    }
-    k.layers++;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-static int stack_finish_check(mimc3_ctx *c, int32_t npeaks, int32_t min_count, const float *out, const float *cand, const std::string &en)
-{
-    if (!c || !out) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
-    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": cand goes with npeaks > 0");
-    if (min_count < 1 || min_count > 65535) return mimc3::fail(MIMC3_EINVAL, en + ": min_count must be in 1..65535");
-    if (c->stk.N == 0) return mimc3::fail(MIMC3_ESTATE, en + ": no stack (mimc3_stack_begin)");
-    return 0;
-}
-
-extern "C" int mimc3_stack_finish_dev(mimc3_ctx *c, int32_t npeaks, int32_t min_count, float *d_out, float *d_cand, float *d_surf,
-                                      uint16_t *d_count, void *stream)
-{
-    RC_TRY(stack_finish_check(c, npeaks, min_count, d_out, d_cand, "mimc3_stack_finish_dev"));
-    auto &k = c->stk;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    const hipError_t e = mimc3::launch_stack_tail(static_cast<const double *>(k.sum.p), static_cast<const uint16_t *>(k.cnt.p),
-                                                  static_cast<const uint16_t *>(k.lay.p), stack_wsum(c, 0),
-                                                  static_cast<const int32_t *>(k.shift.p), k.N, k.R, npeaks, min_count, d_out, d_cand,
-                                                  d_surf, d_count, s);
-    if (e != hipSuccess) return mimc3::hip_fail(e, "stack tail kernel launch");
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_stack_finish(mimc3_ctx *c, int32_t npeaks, int32_t min_count, float *out, float *cand, float *surf, uint16_t *count)
-{
-    RC_TRY(stack_finish_check(c, npeaks, min_count, out, cand, "mimc3_stack_finish"));
-    auto &k = c->stk;
-    const size_t N = (size_t)k.N, NC = stack_cells(c);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(k.out.reserve(sizeof(float) * 8 * N));
-    if (npeaks) HIP_TRY(k.cand.reserve(sizeof(float) * 3 * (size_t)npeaks * N));
-    if (surf) HIP_TRY(k.surf.reserve(sizeof(float) * N * NC));
-    if (count) HIP_TRY(k.count.reserve(sizeof(uint16_t) * N));
-    RC_TRY(mimc3_stack_finish_dev(c, npeaks, min_count, static_cast<float *>(k.out.p), npeaks ? static_cast<float *>(k.cand.p) : nullptr,
-                                  surf ? static_cast<float *>(k.surf.p) : nullptr, count ? static_cast<uint16_t *>(k.count.p) : nullptr,
-                                  c->stream));
-    RC_TRY(d2h_copy(c, out, k.out.p, sizeof(float) * 8 * N));
-    if (npeaks) RC_TRY(d2h_copy(c, cand, k.cand.p, sizeof(float) * 3 * (size_t)npeaks * N));
-    if (surf) RC_TRY(d2h_copy(c, surf, k.surf.p, sizeof(float) * N * NC));
-    if (count) RC_TRY(d2h_copy(c, count, k.count.p, sizeof(uint16_t) * N));
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// coarse-to-fine exhaustive search over an image pyramid (pyramid_kernel.hip; every level's search is the exhaustive search of the
-// pair's class: match_mx_kernel.hip, match_full_u16_kernel.hip or match_full_f32_kernel.hip): the levels of the pair, the per-level
-// searches and the chaining between them on one stream
-// ---------------------------------------------------------------------------------------------
-// Pyramid levels pyr_levels + 1 .. L - 1 of the u8 pair, each from the level above by the 2 x 2 null-aware reduction, with their
-// tables.  Like every plane-set builder: enqueued on the context's stream and drained before the levels count as built.
-static int build_levels(mimc3_ctx *c, int L)
-{
-    const int pad = mimc3::kU8Pad;
-    for (int l = c->pyr_levels + 1; l < L; ++l) {
-        mimc3_ctx::PyrLevel &d = c->pyr[l - 1];
-        const bool top = l == 1;
-        const void *s0 = top ? c->pl0.p : c->pyr[l - 2].pl0.p, *s1 = top ? c->pl1.p : c->pyr[l - 2].pl1.p;
-        const int Hs = top ? c->H : c->pyr[l - 2].H, Ws = top ? c->W : c->pyr[l - 2].W, Wps = top ? c->Wp : c->pyr[l - 2].Wp;
-        d.H = Hs >> 1; d.W = Ws >> 1; d.Wp = (d.W + 2 * pad + 3) & ~3;
-        const int Hp = d.H + 2 * pad;
-        const size_t bytes = (size_t)Hp * d.Wp;
-        HIP_TRY(d.pl0.reserve(bytes));
-        HIP_TRY(d.pl1.reserve(bytes));
-        HIP_TRY(d.sat0.reserve(mimc3::sat_bytes(Hp, d.Wp)));
-        HIP_TRY(d.sat1.reserve(mimc3::sat_bytes(Hp, d.Wp)));
-        HIP_TRY(c->sat_tmp.reserve(mimc3::sat_scratch_bytes(Hp, d.Wp)));
-        HIP_TRY(hipMemsetAsync(d.pl0.p, 0, bytes, c->stream));
-        HIP_TRY(hipMemsetAsync(d.pl1.p, 0, bytes, c->stream));
-        HIP_TRY(mimc3::launch_pyr_reduce(static_cast<const unsigned char *>(s0), Hs, Ws, Wps, static_cast<unsigned char *>(d.pl0.p), d.H, d.W, d.Wp, pad, c->stream));
-        HIP_TRY(mimc3::launch_pyr_reduce(static_cast<const unsigned char *>(s1), Hs, Ws, Wps, static_cast<unsigned char *>(d.pl1.p), d.H, d.W, d.Wp, pad, c->stream));
-        const mimc3::SatRegion rg{0, 0, d.Wp, Hp};
-        HIP_TRY(mimc3::launch_sat_u8(static_cast<const unsigned char *>(d.pl0.p), d.Wp, rg, static_cast<unsigned long long *>(d.sat0.p), c->sat_tmp.p, c->stream));
-        HIP_TRY(mimc3::launch_sat_u8(static_cast<const unsigned char *>(d.pl1.p), d.Wp, rg, static_cast<unsigned long long *>(d.sat1.p), c->sat_tmp.p, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (L - 1 > c->pyr_levels) c->pyr_levels = L - 1;
-    return 0;
-}
-
-// The same for a scaled-integer pair (mimc3_match_ncc_pyramid_dn): the levels of the u16 planes q = pixel * 2^shift, which keep the
-// image's shift, with their packed and null tables.
-static int build_levels16(mimc3_ctx *c, int L)
-{
-    const int pad = mimc3::kU8Pad;
-    for (int l = c->pyr_levels + 1; l < L; ++l) {
-        mimc3_ctx::PyrLevel16 &d = c->pyr16[l - 1];
-        const bool top = l == 1;
-        const void *s0 = top ? c->hpl0.p : c->pyr16[l - 2].pl0.p, *s1 = top ? c->hpl1.p : c->pyr16[l - 2].pl1.p;
-        const int Hs = top ? c->H : c->pyr16[l - 2].H, Ws = top ? c->W : c->pyr16[l - 2].W, Wps = top ? c->Wp : c->pyr16[l - 2].Wp;
-        d.H = Hs >> 1; d.W = Ws >> 1; d.Wp = (d.W + 2 * pad + 3) & ~3;
-        const int Hp = d.H + 2 * pad;
-        const size_t bytes = sizeof(unsigned short) * (size_t)Hp * d.Wp;
-        HIP_TRY(d.pl0.reserve(bytes));
-        HIP_TRY(d.pl1.reserve(bytes));
-        HIP_TRY(d.sat0.reserve(mimc3::sat_bytes(Hp, d.Wp)));
-        HIP_TRY(d.sat1.reserve(mimc3::sat_bytes(Hp, d.Wp)));
-        HIP_TRY(d.sz0.reserve(mimc3::sat_null_bytes(Hp, d.Wp)));
-        HIP_TRY(d.sz1.reserve(mimc3::sat_null_bytes(Hp, d.Wp)));
-        HIP_TRY(c->sat_tmp.reserve(mimc3::sat_scratch_bytes(Hp, d.Wp)));
-        HIP_TRY(hipMemsetAsync(d.pl0.p, 0, bytes, c->stream));
-        HIP_TRY(hipMemsetAsync(d.pl1.p, 0, bytes, c->stream));
-        HIP_TRY(mimc3::launch_pyr_reduce_u16(static_cast<const unsigned short *>(s0), Hs, Ws, Wps, static_cast<unsigned short *>(d.pl0.p), d.H, d.W, d.Wp, pad, c->stream));
-        HIP_TRY(mimc3::launch_pyr_reduce_u16(static_cast<const unsigned short *>(s1), Hs, Ws, Wps, static_cast<unsigned short *>(d.pl1.p), d.H, d.W, d.Wp, pad, c->stream));
-        const mimc3::SatRegion rg{0, 0, d.Wp, Hp};
-        HIP_TRY(mimc3::launch_sat_u16(static_cast<const unsigned short *>(d.pl0.p), d.Wp, rg, static_cast<unsigned long long *>(d.sat0.p),
-                                      static_cast<unsigned int *>(d.sz0.p), c->sat_tmp.p, c->stream));
-        HIP_TRY(mimc3::launch_sat_u16(static_cast<const unsigned short *>(d.pl1.p), d.Wp, rg, static_cast<unsigned long long *>(d.sat1.p),
-                                      static_cast<unsigned int *>(d.sz1.p), c->sat_tmp.p, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (L - 1 > c->pyr_levels) c->pyr_levels = L - 1;
-    return 0;
-}
-
-// ... and for an integral-f32 pair: the levels of the f32 planes (reduced on the integers w = pixel * 2^fshift) with their 16-byte tables.
-static int build_levelsf(mimc3_ctx *c, int L)
-{
-    const int pad = mimc3::kU8Pad;
-    for (int l = c->pyr_levels + 1; l < L; ++l) {
-        mimc3_ctx::PyrLevelF &d = c->pyrf[l - 1];
-        const bool top = l == 1;
-        const void *s0 = top ? c->fpl0.p : c->pyrf[l - 2].pl0.p, *s1 = top ? c->fpl1.p : c->pyrf[l - 2].pl1.p;
-        const int Hs = top ? c->H : c->pyrf[l - 2].H, Ws = top ? c->W : c->pyrf[l - 2].W, Wps = top ? c->Wp : c->pyrf[l - 2].Wp;
-        d.H = Hs >> 1; d.W = Ws >> 1; d.Wp = (d.W + 2 * pad + 3) & ~3;
-        const int Hp = d.H + 2 * pad;
-        const size_t bytes = sizeof(float) * (size_t)Hp * d.Wp;
-        HIP_TRY(d.pl0.reserve(bytes));
-        HIP_TRY(d.pl1.reserve(bytes));
-        HIP_TRY(d.sat0.reserve(mimc3::sat2_bytes(Hp, d.Wp)));
-        HIP_TRY(d.sat1.reserve(mimc3::sat2_bytes(Hp, d.Wp)));
-        HIP_TRY(c->sat_tmp.reserve(mimc3::sat2_scratch_bytes(Hp, d.Wp)));
-        HIP_TRY(hipMemsetAsync(d.pl0.p, 0, bytes, c->stream));
-        HIP_TRY(hipMemsetAsync(d.pl1.p, 0, bytes, c->stream));
-        HIP_TRY(mimc3::launch_pyr_reduce_f32(static_cast<const float *>(s0), Hs, Ws, Wps, static_cast<float *>(d.pl0.p), d.H, d.W, d.Wp, pad, c->fshift0, c->stream));
-        HIP_TRY(mimc3::launch_pyr_reduce_f32(static_cast<const float *>(s1), Hs, Ws, Wps, static_cast<float *>(d.pl1.p), d.H, d.W, d.Wp, pad, c->fshift1, c->stream));
-        const mimc3::SatRegion rg{0, 0, d.Wp, Hp};
-        HIP_TRY(mimc3::launch_sat_f32i(static_cast<const float *>(d.pl0.p), d.Wp, rg, c->fshift0, static_cast<mimc3::Sat2 *>(d.sat0.p), c->sat_tmp.p, c->stream));
-        HIP_TRY(mimc3::launch_sat_f32i(static_cast<const float *>(d.pl1.p), d.Wp, rg, c->fshift1, static_cast<mimc3::Sat2 *>(d.sat1.p), c->sat_tmp.p, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (L - 1 > c->pyr_levels) c->pyr_levels = L - 1;
-    return 0;
-}
-
-// ... and for any pair (mimc3_match_ncc_pyramid_any): float levels pyrg_levels + 1 .. L - 1 of the f32 planes, each the f64 mean of the
-// block's included pixels (pyr_reduce_f32g_kernel); no tables.
-static int build_levelsg(mimc3_ctx *c, int L)
-{
-    const int pad = mimc3::kU8Pad;
-    if (!c->fplanes_ok) RC_TRY(build_f32(c));
-    for (int l = c->pyrg_levels + 1; l < L; ++l) {
-        mimc3_ctx::PyrLevelG &d = c->pyrg[l - 1];
-        const bool top = l == 1;
-        const void *s0 = top ? c->fpl0.p : c->pyrg[l - 2].pl0.p, *s1 = top ? c->fpl1.p : c->pyrg[l - 2].pl1.p;
-        const int Hs = top ? c->H : c->pyrg[l - 2].H, Ws = top ? c->W : c->pyrg[l - 2].W, Wps = top ? c->Wp : c->pyrg[l - 2].Wp;
-        d.H = Hs >> 1; d.W = Ws >> 1; d.Wp = (d.W + 2 * pad + 3) & ~3;
-        const size_t bytes = sizeof(float) * (size_t)(d.H + 2 * pad) * d.Wp;
-        HIP_TRY(d.pl0.reserve(bytes));
-        HIP_TRY(d.pl1.reserve(bytes));
-        HIP_TRY(hipMemsetAsync(d.pl0.p, 0, bytes, c->stream));
-        HIP_TRY(hipMemsetAsync(d.pl1.p, 0, bytes, c->stream));
-        HIP_TRY(mimc3::launch_pyr_reduce_f32g(static_cast<const float *>(s0), Hs, Ws, Wps, static_cast<float *>(d.pl0.p), d.H, d.W, d.Wp, pad, c->stream));
-        HIP_TRY(mimc3::launch_pyr_reduce_f32g(static_cast<const float *>(s1), Hs, Ws, Wps, static_cast<float *>(d.pl1.p), d.H, d.W, d.Wp, pad, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (L - 1 > c->pyrg_levels) c->pyrg_levels = L - 1;
-    return 0;
-}
-
-// levels 1 .. L - 1 of the current pair, whatever its class (which full_dn_class has settled), and the level-0 set they start from
-static int build_levels_of_class(mimc3_ctx *c, int L)
-{
-    if (c->u8_ok) {
-        if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
-        return c->pyr_levels < L - 1 ? build_levels(c, L) : 0;
-    }
-    if (c->u16_ok) {
-        if (!c->hpl_valid || !c->sat_u16_ok) RC_TRY(build_u16(c, true));
-        return c->pyr_levels < L - 1 ? build_levels16(c, L) : 0;
-    }
-    return c->pyr_levels < L - 1 ? build_levelsf(c, L) : 0;
-}
-
-// the refusals the pyramid entries make before anything runs (those of the exhaustive search, levels, the coarsest level's size); kind 0:
-// 8-bit alone; 1: the classes of mimc3_match_ncc_full_dn (an integral-f32 pair's planes are built here); 2: any pair
-// (mimc3_match_ncc_pyramid_any: class is no reason to refuse)
-static int pyramid_check(mimc3_ctx *c, int32_t ocw, int32_t R, int32_t levels, const char *entry, int kind)
-{
-    const std::string e(entry);
-    if (!full_ocw_ok(ocw)) return mimc3::fail(MIMC3_EINVAL, e + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (R < 1 || R > 15) return mimc3::fail(MIMC3_EINVAL, e + ": R must be in 1..15");
-    if (levels < 1 || levels > 5) return mimc3::fail(MIMC3_EINVAL, e + ": levels must be in 1..5");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, e + ": images not set");
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, e + ": not on a chip-atlas context");
-    if (kind == 1) RC_TRY(full_dn_class(c, e));
-    else if (kind == 0 && !c->u8_ok) return mimc3::fail(MIMC3_EUNSUPPORTED, e + ": the pair is not 8-bit (u8 planes only)");
-    if (std::min(c->H >> (levels - 1), c->W >> (levels - 1)) < 2 * ocw + 1)
-        return mimc3::fail(MIMC3_EINVAL, e + ": level " + std::to_string(levels - 1) + " is smaller than a chip");
-    return 0;
-}
-
-// The device entry of both pyramid searches, behind their checks: the levels of the pair's class, then per level the step and the class's
-// exhaustive search with the arg-max cells; level 0 is mimc3_match_ncc_full_dn_dev's launch at shift = sh (record and candidates).
-// fmode >= 0 (mimc3_match_ncc_pyramid_any on the float levels): the float levels and the float kernel on every level, and level 0 is
-// mimc3_match_ncc_full_any_dev's launch with mode = fmode
-static int pyramid_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift, int32_t ocw,
-                       int32_t R, int32_t levels, int32_t npeaks, int32_t swap, float *d_out, float *d_cand, int32_t *d_shift_out, void *stream,
-                       int32_t fmode = -1)
-{
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool general = fmode >= 0;
-    if (!general) RC_TRY(build_levels_of_class(c, levels));
-    else if (!c->fplanes_ok || c->pyrg_levels < levels - 1) RC_TRY(build_levelsg(c, levels));
-    DevBuf &ml = c->mxl[0];
-    if (c->u8_ok && !general) HIP_TRY(ml.reserve((size_t)N));
-    HIP_TRY(c->pyr_pos.reserve(sizeof(double) * 2 * (size_t)N));
-    HIP_TRY(c->pyr_peak.reserve(sizeof(int32_t) * (size_t)N));
-    if (!d_shift_out) HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
-    int32_t *sh = d_shift_out ? d_shift_out : static_cast<int32_t *>(c->pyr_sh.p);
-    double *pos = static_cast<double *>(c->pyr_pos.p);
-    int32_t *peak = static_cast<int32_t *>(c->pyr_peak.p);
-    const bool timing = c->timing;
-    if (timing) HIP_TRY(hipEventRecord(c->ev0, s));
-    // the coarsest level's displacement d_{L-1} and positions p_{L-1} (for L = 1: shift_out = shift)
-    HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, d_shift, nullptr, R, levels - 1, true, sh, pos, s));
-    for (int l = levels - 1; l >= 1; --l) {     // level l: its planes, tables and geometry, and the arg-max cells for the step to level l - 1
-        mimc3::MatchU8Args u = u8_args(c, pos, 2, 0, N, 0, 0, ocw, swap, d_out);
-        u.full_shift = sh; u.full_R = R; u.full_peak = peak;
-        hipError_t e;
-        if (general) {
-            const mimc3_ctx::PyrLevelG &d = c->pyrg[l - 1];
-            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
-            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
-            e = mimc3::launch_match_full_f32g(u, nullptr, s);
-        } else if (c->u8_ok) {
-            const mimc3_ctx::PyrLevel &d = c->pyr[l - 1];
-            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
-            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
-            u.sat0 = d.sat0.p; u.sat1 = d.sat1.p; u.sat_ws = mimc3::sat_pitch(d.Wp);
-            HIP_TRY(hipMemsetAsync(ml.p, 0, (size_t)N, s));
-            u.mx_flags = static_cast<uint8_t *>(ml.p);
-            e = mimc3::launch_match_full_mx(u, s);
-        } else if (c->u16_ok) {
-            const mimc3_ctx::PyrLevel16 &d = c->pyr16[l - 1];
-            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
-            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
-            u.sat0 = d.sat0.p; u.sat1 = d.sat1.p; u.satz0 = d.sz0.p; u.satz1 = d.sz1.p; u.sat_ws = mimc3::sat_pitch(d.Wp);
-            e = mimc3::launch_match_full_u16(u, s);
-        } else {
-            const mimc3_ctx::PyrLevelF &d = c->pyrf[l - 1];
-            u.Wp = d.Wp; u.H = d.H; u.W = d.W;
-            u.p0 = static_cast<const unsigned char *>(d.pl0.p); u.p1 = static_cast<const unsigned char *>(d.pl1.p);
-            u.sat0 = d.sat0.p; u.sat1 = d.sat1.p; u.sat_ws = mimc3::sat_pitch(d.Wp);
-            u.scale0 = 1.0 / (double)(1 << c->fshift0); u.scale1 = 1.0 / (double)(1 << c->fshift1);
-            e = mimc3::launch_match_full_f32(u, s);
-        }
-        if (e != hipSuccess) return mimc3::hip_fail(e, "pyramid-level search launch");
-        HIP_TRY(mimc3::launch_pyr_step(d_xyuvav, N, off_u, off_v, nullptr, peak, R, l - 1, false, sh, pos, s));
-    }
-    c->timing = false;                  // (the events bracket the whole pass, not the level-0 launch)
-    const int rc = general ? full_any_dev(c, d_xyuvav, N, off_u, off_v, sh, ocw, R, npeaks, swap, fmode, d_out, d_cand, nullptr, stream)
-                           : full_dn_dev(c, d_xyuvav, N, off_u, off_v, sh, ocw, R, npeaks, swap, d_out, d_cand, stream);      // sets last_path
-    c->timing = timing;
-    if (rc) return rc;
-    if (timing) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_pyramid_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                           const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t swap, float *d_out,
-                                           int32_t *d_shift_out, void *stream)
-{
-    if (!c || !d_xyuvav || !d_out || N <= 0) return mimc3::fail(MIMC3_EINVAL, "mimc3_match_ncc_pyramid_dev: bad argument");
-    RC_TRY(pyramid_check(c, ocw, R, levels, "mimc3_match_ncc_pyramid_dev", 0));
-    return pyramid_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, levels, 0, swap, d_out, nullptr, d_shift_out, stream);
-}
-
-extern "C" int mimc3_match_ncc_pyramid_dn_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                              const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
-                                              float *d_out, float *d_cand, int32_t *d_shift_out, void *stream)
-{
-    const char *en = "mimc3_match_ncc_pyramid_dn_dev";
-    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    RC_TRY(pyramid_check(c, ocw, R, levels, en, 1));
-    return pyramid_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, levels, npeaks, swap, d_out, d_cand, d_shift_out, stream);
-}
-
-// mimc3_match_ncc_pyramid_any behind pyramid_check: which levels and kernels the call runs.  fmode -1: those of the pair's integer class
-// (mode 0 on an 8-bit, scaled-integer or integral-f32 pair: mimc3_match_ncc_pyramid_dn unchanged); else the float ones, level 0 in `mode`.
-// (The class of an f32 pair needs its planes: built here on first use, which drains the stream.)
-static int pyramid_any_fmode(mimc3_ctx *c, int32_t mode, const char *entry, int32_t &fmode)
-{
-    if (mode != 0 && mode != 1) return mimc3::fail(MIMC3_EINVAL, std::string(entry) + ": mode must be 0 or 1");
-    fmode = mode;
-    if (mode == 1) return 0;
-    if (!c->u8_ok && !c->u16_ok) {
-        HIP_TRY(hipSetDevice(c->device));
-        if (!c->fplanes_ok) RC_TRY(build_f32(c));
-        if (!c->f32i_ok) return 0;
-    }
-    fmode = -1;
-    return 0;
-}
-
-extern "C" int mimc3_match_ncc_pyramid_any_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
-                                               const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
-                                               int32_t mode, float *d_out, float *d_cand, int32_t *d_shift_out, void *stream)
-{
-    const char *en = "mimc3_match_ncc_pyramid_any_dev";
-    if (!c || !d_xyuvav || !d_out || N <= 0 || (npeaks == 0) != (d_cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": npeaks must be in 0..8");
-    RC_TRY(pyramid_check(c, ocw, R, levels, en, 2));
-    int32_t fmode;
-    RC_TRY(pyramid_any_fmode(c, mode, en, fmode));
-    return pyramid_dev(c, d_xyuvav, N, off_u, off_v, d_shift, ocw, R, levels, npeaks, swap, d_out, d_cand, d_shift_out, stream, fmode);
-}
-
-// the host entry of the pyramid searches: the checks, the uploads, the device entry and the copies back (kind: pyramid_check's -- 0
-// mimc3_match_ncc_pyramid, 1 mimc3_match_ncc_pyramid_dn, 2 mimc3_match_ncc_pyramid_any with its `mode`)
-static int pyramid_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift, int32_t ocw, int32_t R,
-                        int32_t levels, int32_t npeaks, int32_t swap, float *out, float *cand, int32_t *shift_out, int kind, const char *entry,
-                        int32_t mode = 0)
-{
-    const std::string en(entry);
-    if (!c || !xyuvav || !offset || !out || N <= 0) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    if (npeaks < 0 || npeaks > mimc3::kFullMaxPeaks) return mimc3::fail(MIMC3_EINVAL, en + ": npeaks must be in 0..8");
-    if ((npeaks == 0) != (cand == nullptr)) return mimc3::fail(MIMC3_EINVAL, en + ": cand goes with npeaks > 0");
-    RC_TRY(pyramid_check(c, ocw, R, levels, entry, kind));
-    int32_t fmode = -1;
-    if (kind == 2) RC_TRY(pyramid_any_fmode(c, mode, entry, fmode));
-    // the chip inside the level-0 image (a point whose derived search box leaves the zero border gets the all-NaN record); the starting
-    // displacement within +-2^24 per axis, so that every level's shifts stay exact int32
-    RC_TRY(check_chips(c, xyuvav, 0, N, ocw, entry));
-    const int64_t lim = (int64_t)1 << 24;
-    for (int32_t g = 0; g < N; ++g) {
-        const int64_t du = (int64_t)offset[0] + (shift ? shift[2 * (size_t)g] : 0), dv = (int64_t)offset[1] + (shift ? shift[2 * (size_t)g + 1] : 0);
-        if (offset[0] < -lim || offset[0] > lim || offset[1] < -lim || offset[1] > lim || du < -lim || du > lim || dv < -lim || dv > lim)
-            return mimc3::fail(MIMC3_EINVAL, en + ": grid point " + std::to_string(g) + " starting displacement beyond +-2^24");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
-    HIP_TRY(c->out.reserve(sizeof(float) * 8 * (size_t)N));
-    HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
-    if (npeaks) HIP_TRY(c->full_cand.reserve(sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
-    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
-    const int32_t *d_shift = nullptr;
-    if (shift) {
-        HIP_TRY(c->puv.reserve(sizeof(int32_t) * 2 * (size_t)N));
-        RC_TRY(h2d_copy(c, c->puv.p, shift, sizeof(int32_t) * 2 * (size_t)N));
-        d_shift = static_cast<const int32_t *>(c->puv.p);
-    }
-    RC_TRY(pyramid_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], d_shift, ocw, R, levels, npeaks, swap,
-                       static_cast<float *>(c->out.p), npeaks ? static_cast<float *>(c->full_cand.p) : nullptr,
-                       static_cast<int32_t *>(c->pyr_sh.p), c->stream, fmode));
-    if (shift_out) RC_TRY(d2h_copy(c, shift_out, c->pyr_sh.p, sizeof(int32_t) * 2 * (size_t)N));
-    if (npeaks) RC_TRY(d2h_copy(c, cand, c->full_cand.p, sizeof(float) * 3 * (size_t)npeaks * (size_t)N));
-    return d2h_copy(c, out, c->out.p, sizeof(float) * 8 * (size_t)N);
-}
-
-extern "C" int mimc3_match_ncc_pyramid(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                       int32_t ocw, int32_t R, int32_t levels, int32_t swap, float *out, int32_t *shift_out)
-{
-    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, 0, swap, out, nullptr, shift_out, 0, "mimc3_match_ncc_pyramid");
-}
-
-extern "C" int mimc3_match_ncc_pyramid_dn(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                          int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap, float *out, float *cand,
-                                          int32_t *shift_out)
-{
-    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, npeaks, swap, out, cand, shift_out, 1, "mimc3_match_ncc_pyramid_dn");
-}
-
-extern "C" int mimc3_match_ncc_pyramid_any(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
-                                           int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap, int32_t mode, float *out,
-                                           float *cand, int32_t *shift_out)
-{
-    return pyramid_host(c, xyuvav, N, offset, shift, ocw, R, levels, npeaks, swap, out, cand, shift_out, 2, "mimc3_match_ncc_pyramid_any", mode);
-}
-
-// one level of the current pair as pixel values (the planes' interior; u16 planes divided by 2^shift), for tests of the reduction
-extern "C" int mimc3_ctx_get_pyramid_level(mimc3_ctx *c, int32_t level, float *out0, float *out1)
-{
-    const char *en = "mimc3_ctx_get_pyramid_level";
-    if (!c || !out0 || !out1 || level < 1 || level > 4) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, std::string(en) + ": images not set");
-    RC_TRY(full_dn_class(c, en));
-    if ((c->H >> level) < 1 || (c->W >> level) < 1) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": level " + std::to_string(level) + " is empty");
-    HIP_TRY(hipSetDevice(c->device));
-    RC_TRY(build_levels_of_class(c, level + 1));
-    const int pad = mimc3::kU8Pad;
-    const int cls = c->u8_ok ? 0 : c->u16_ok ? 1 : 2;
-    const size_t es = cls == 0 ? 1 : cls == 1 ? 2 : 4;
-    const int H = c->H >> level, W = c->W >> level;
-    std::vector<unsigned char> tmp(es * (size_t)H * W);
-    for (int k = 0; k < 2; k++) {
-        const void *pl;
-        int Wp;
-        if (cls == 0) { const mimc3_ctx::PyrLevel &d = c->pyr[level - 1]; pl = k ? d.pl1.p : d.pl0.p; Wp = d.Wp; }
-        else if (cls == 1) { const mimc3_ctx::PyrLevel16 &d = c->pyr16[level - 1]; pl = k ? d.pl1.p : d.pl0.p; Wp = d.Wp; }
-        else { const mimc3_ctx::PyrLevelF &d = c->pyrf[level - 1]; pl = k ? d.pl1.p : d.pl0.p; Wp = d.Wp; }
-        float *out = k ? out1 : out0;
-        void *dst = cls == 2 ? static_cast<void *>(out) : static_cast<void *>(tmp.data());
-        HIP_TRY(hipMemcpy2DAsync(dst, es * W, static_cast<const unsigned char *>(pl) + es * ((size_t)pad * Wp + pad), es * Wp, es * W, H,
-                                 hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        const float sc = 1.0f / (float)(1 << (k ? c->shift1 : c->shift0));
-        if (cls == 0) for (size_t i = 0; i < (size_t)H * W; i++) out[i] = (float)tmp[i];
-        if (cls == 1) for (size_t i = 0; i < (size_t)H * W; i++) out[i] = (float)reinterpret_cast<const unsigned short *>(tmp.data())[i] * sc;
-    }
-    return 0;
-}
-
-// one FLOAT level of the current pair, whatever its class (mimc3_match_ncc_pyramid_any's levels), for tests of the reduction
-extern "C" int mimc3_ctx_get_pyramid_level_any(mimc3_ctx *c, int32_t level, float *out0, float *out1)
-{
-    const char *en = "mimc3_ctx_get_pyramid_level_any";
-    if (!c || !out0 || !out1 || level < 1 || level > 4) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": bad argument");
-    if (!c->d_i0 || !c->d_i1) return mimc3::fail(MIMC3_ESTATE, std::string(en) + ": images not set");
-    if (c->child) return mimc3::fail(MIMC3_ESTATE, std::string(en) + ": not on a chip-atlas context");
-    if ((c->H >> level) < 1 || (c->W >> level) < 1) return mimc3::fail(MIMC3_EINVAL, std::string(en) + ": level " + std::to_string(level) + " is empty");
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->fplanes_ok || c->pyrg_levels < level) RC_TRY(build_levelsg(c, level + 1));
-    const int pad = mimc3::kU8Pad;
-    const mimc3_ctx::PyrLevelG &d = c->pyrg[level - 1];
-    for (int k = 0; k < 2; k++) {
-        const float *pl = static_cast<const float *>(k ? d.pl1.p : d.pl0.p);
-        HIP_TRY(hipMemcpy2DAsync(k ? out1 : out0, sizeof(float) * d.W, pl + (size_t)pad * d.Wp + pad, sizeof(float) * d.Wp, sizeof(float) * d.W, d.H,
-                                 hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
+// (the exhaustive-search family -- mimc3_match_ncc_full*, _wide*, _pyramid* -- is in search.cpp, NCC stacking in stack.cpp)
 
 // the a-priori displacement in pixels (get_uv_pivot's sign convention, :559-598), rounded to the nearest integer
 extern "C" int mimc3_prior_shift(const double *xyuvav, int32_t N, float dt, float mpp, int32_t *shift)
