@@ -52,6 +52,8 @@ __device__ __forceinline__ T sat_box(const T *__restrict__ S, int Ws, int x, int
 // 8,224 pixels (sum b < 2^21; beyond that the field above takes a carry and the null count comes back off by it -- a window of
 // 16,384 - carry nulls would read as null-free).  Larger boxes are cut into sub-boxes of at most 64 x 64 pixels, one per lane, and the
 // counts are summed over the wave.  Wave-uniform arguments; every lane gets the result.
+// Only near-saturated data makes the single query fail (on mid-range pixels a 111 x 111 box sums to about 1.6 M < 2^21 and one query is
+// right everywhere), so tests on such fixtures are no evidence that the split can go: tests/test_value_limits_cpu.py has the data that tells.
 __device__ __forceinline__ int sat_nulls_u8(const unsigned long long *__restrict__ S, int Ws, int x, int y, int w, int h, int lane)
 {
     if (w * h <= 8224) return (int)(sat_box(S, Ws, x, y, w, h) >> kSatNullShift8);

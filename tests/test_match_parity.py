@@ -5,6 +5,7 @@ import pytest
 
 from conftest import assert_bits_equal, golden_files, load_match_golden
 from mimc3_amd import synth
+from value_limit_common import expected_path
 
 pytestmark = pytest.mark.gpu
 
@@ -13,24 +14,6 @@ pytestmark = pytest.mark.gpu
 def api():
     from mimc3_amd import api as a
     return a
-
-
-U8_OCW = (7, 15, 16, 30, 32, 40)   # chip sizes the exact u8 kernel is instantiated for
-
-
-F32T_OCW = (7, 15, 16, 30, 32, 40)     # chip sizes of the register-tiled f32 kernel
-
-
-def expected_path(mode, i0, ocw, i1=None):
-    imgs = [i0] if i1 is None else [i0, i1]
-    is_u8 = all(float(i.max()) <= 255.0 and float(i.min()) >= 0 and np.array_equal(i, np.rint(i)) for i in imgs)
-    is_si = all(float(i.min()) >= 0 and ((float(i.max()) <= 4095.0 and np.array_equal(i, np.rint(i))) or
-                (float(i.max()) * 8 <= 4095.0 and np.array_equal(i * 8, np.rint(i * 8)))) for i in imgs)
-    if mode in ("auto", "u8px") and ocw in U8_OCW and is_u8:
-        return "u8_mfma" if mode == "auto" else "u8_exact"     # the matrix-core kernel first ("auto"), or the register-tiled kernel alone
-    if ocw in U8_OCW and ((mode in ("auto", "u8px") and is_si and not is_u8) or (mode == "u16" and is_u8)):
-        return "u16_scaled"
-    return "f32_tiled" if (mode != "general" and ocw in F32T_OCW) else "general_f32"
 
 
 @pytest.mark.parametrize("mode", ["auto", "u8px", "general", "f32", "u16"])

@@ -4,17 +4,12 @@ against the register-tiled kernel alone ("u8px") bit for bit, and against the po
 the program and in both directions, on the inputs that aim at the lists: one of them empty, list lengths around a wave and not a
 multiple of 8 (the XCD order of list positions), static and dynamic hand-ons, long climbs on a stripe image, the two matcher lanes, a pair
 change and a path change between calls.  CPU: the point classes of BASELINE C2 from a numpy summed-area table."""
-import os
-import re
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, assert_bits_equal
+from conftest import assert_bits_equal
 from mimc3_amd import synth
+from u8_stats_common import stats_run
 
 OCWS = (7, 15, 16, 30, 40)
 C2_CLASSES = (96939, 67608, 20928, 14525)          # clean, window nulls only, chip nulls only, both (DESIGN 4.1a)
@@ -162,33 +157,6 @@ def test_long_climbs_on_a_stripe_image(api, oracle, ocw):
         got = ctx.matching_ncc_dlc_2(xy, offset, off, uv, ocw)
     n = 70
     assert_bits_equal(got[:n], oracle.match(i0, i1, np.ascontiguousarray(xy[:n]), offset, off[:n + 1], uv[:off[n]], ocw), "stripes vs oracle")
-
-
-STATS_RE = (r"u8_classify: classes clean (\d+) rest (\d+) nulls (\d+) window-nulls (\d+); lists clean (\d+) rest (\d+)\n"
-            r".*?clean: (\d+) points staged[^\n]*rest (\d+)")
-
-
-def stats_run(body):
-    """one forward call on path auto in a subprocess with the kernels' diagnostics on (the switch is read once per process):
-    (classes clean, rest, nulls, window-nulls; list lengths clean, rest) as u8_classify left them, then the points the
-    matrix-core launch finished and the points classed kMxRest after it"""
-    code = textwrap.dedent("""
-        import sys
-        sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
-        import numpy as np
-        from mimc3_amd import api, synth
-        import test_u8_step_lists as t
-        %s
-        with api.Context(0) as ctx:
-            ctx.set_images(i0, i1)
-            ctx.matching_ncc_dlc_2(xy, offset, off, uv, ocw)
-            assert ctx.last_path() == "u8_mfma"
-    """) % (ROOT, ROOT, body)
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MIMC3_MX_STATS="1"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    m = re.search(STATS_RE, r.stderr, re.S)
-    assert m, r.stderr[-2000:]
-    return tuple(int(v) for v in m.groups())
 
 
 @pytest.mark.gpu
