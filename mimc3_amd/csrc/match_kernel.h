@@ -122,9 +122,9 @@ struct alignas(64) U8PointRec {
     int32_t g;                      // the point
     int32_t u0, v0;                 // its chip centre (image pixels)
     int32_t lu, lv;                 // its last pivot
-    int32_t npiv;
+    int32_t npiv;                   // bits 0-7 (behind u8_classify no call has more than 64 pivots per point) | the climb area << 8 (mx_area_pack)
     int64_t pbeg;                   // piv_off[g]
-    uint32_t tile;                  // tx0 | ty0 << 10 | fits << 20 (mx_tile_fit of the DLC tile, origin 1) | the chip's corner pixel << 24 (clean points)
+    uint32_t tile;                  // tx0 | ty0 << 10 | fits << 20 (mx_tile_fit of the DLC tile, origin 1) | done << 21 (kRecDone) | the chip's corner pixel << 24 (clean and advance points)
     int32_t win_nulls;              // nulls of the window's written area
     unsigned long long chipQ;       // the chip's packed table query (sum, sum of squares, nulls)
     unsigned long long colQ, rowQ;  // clean points only: the queries of the chip's last column and last row (the matrix-core kernel's closed-form T4 terms)
@@ -143,6 +143,40 @@ __device__ __forceinline__ bool mx_tile_fit(int lu, int lv, int ocw, int dx2, in
     if (csx - 2 > 32) { tx0 = min(max((lox + hix) / 2 - 15, 1), csx - 2 - 31); fits = fits && lox - 1 >= tx0 && hix + 1 <= tx0 + 31; }
     if (csy - 2 > 32) { ty0 = min(max((loy + hiy) / 2 - 15, 1), csy - 2 - 31); fits = fits && loy - 1 >= ty0 && hiy + 1 <= ty0 + 31; }
     return fits;
+}
+// The climb area of a point: the rectangle of cells spanned by pivot 0's cell and the last pivot's, grown by kMxAreaGrow cells on every
+// side, clipped to the reachable cells [1, cs - 2] and to the tile (tx0, ty0 of mx_tile_fit).  DLC pivots run from (0, 0) to the last
+// pivot, so their climbs rarely leave it.  a[] = its bounds as tile-relative cells (x0, x1, y0, y1, inclusive, each 0..31); (px, py, pw, ph)
+// = the union of those cells' boxes in window pixels, clipped to the window's written area (2 dx2 x 2 dy2: the never-written last row and
+// column are not window pixels, the clean form's closed-form T4 terms stand for them).  If that rectangle holds no null, n, sx and sxx of
+// every cell of the area are what they are for a null-free window, and the matrix-core kernel's clean form computes those cells exactly
+// -- whatever nulls the rest of the window holds: a climb whose every scan stays inside the area never reads another cell.
+constexpr int kMxAreaGrow = 2;
+__device__ __forceinline__ void mx_climb_area(int lu, int lv, int ocw, int dx2, int dy2, int csx, int csy, int tx0, int ty0, int (&a)[4], int &px,
+                                              int &py, int &pw, int &ph)
+{
+    const int c0x = dx2 - ocw, c1x = c0x + lu, c0y = dy2 - ocw, c1y = c0y + lv;
+    const int lox = max(max(min(c0x, c1x) - kMxAreaGrow, 1), tx0), hix = min(min(max(c0x, c1x) + kMxAreaGrow, csx - 2), tx0 + 31);
+    const int loy = max(max(min(c0y, c1y) - kMxAreaGrow, 1), ty0), hiy = min(min(max(c0y, c1y) + kMxAreaGrow, csy - 2), ty0 + 31);
+    a[0] = lox - tx0; a[1] = hix - tx0; a[2] = loy - ty0; a[3] = hiy - ty0;
+    px = lox; py = loy;                                         // (the box of cell c: window pixels c .. c + 2 ocw)
+    pw = min(hix + 2 * ocw + 1, 2 * dx2) - lox; ph = min(hiy + 2 * ocw + 1, 2 * dy2) - loy;
+}
+// the area's bounds in a record (U8PointRec::npiv, bits 8-27), and the whole tile: what a point without window nulls carries
+__device__ __forceinline__ uint32_t mx_area_pack(const int (&a)[4]) { return ((uint32_t)a[0] | (uint32_t)a[1] << 5 | (uint32_t)a[2] << 10 | (uint32_t)a[3] << 15) << 8; }
+constexpr uint32_t kMxAreaTile = (0u | 31u << 5 | 0u << 10 | 31u << 15) << 8;
+constexpr uint32_t kRecNpivMask = 0xffu;
+constexpr uint32_t kRecDone = 1u << 21;     // U8PointRec::tile of a rest-list record: the matrix-core launch has finished the point (advance list)
+// A scan centred on tile-relative cell (rx, ry) reads nine cells.  It is allowed when all nine lie inside the area, i.e. when
+// (unsigned)(rx - xlo) <= wx && (unsigned)(ry - ylo) <= wy with the four numbers below (an area too narrow for any scan: none passes).
+// The whole tile gives 1, 29, 1, 29
+__device__ __forceinline__ void mx_area_scan_bounds(uint32_t rec_npiv, int &xlo, uint32_t &wx, int &ylo, uint32_t &wy)
+{
+    const uint32_t area = rec_npiv >> 8;
+    const int x0 = (int)(area & 31u), x1 = (int)((area >> 5) & 31u), y0 = (int)((area >> 10) & 31u), y1 = (int)((area >> 15) & 31u);
+    const bool some = x1 - x0 >= 2 && y1 - y0 >= 2;
+    xlo = some ? x0 + 1 : 64; wx = some ? (uint32_t)(x1 - x0 - 2) : 0u;
+    ylo = some ? y0 + 1 : 64; wy = some ? (uint32_t)(y1 - y0 - 2) : 0u;
 }
 // no form of the kernel takes a point with more pivots than a wave has lanes (or none) or a pivot set wider than the tile
 __device__ __forceinline__ bool mx_takes(int npiv, bool fits) { return npiv >= 1 && npiv <= 64 && fits; }
@@ -179,9 +213,11 @@ hipError_t launch_match_f32x(MatchU8Args a, int max_abs_u, int max_abs_v, int ma
 hipError_t launch_match_u8(MatchU8Args a, int max_abs_u, int max_abs_v, int max_npiv, hipStream_t stream);
 // dense correlation surfaces on the matrix cores (8-bit planes with tables; match_mx_kernel.hip): takes the points whose cell grid
 // fits its tile and whose chip and window have no null.  u8_classify runs first (one thread per point, once per call): it writes every
-// point's class byte and the two index lists in ascending point order -- `lists`: [0] clean count, [1] rest count, [kU8ListHead, + N) the
-// clean list, then N words of rest list and u8_classify_scratch_ints(N) of scratch -- and zeroes a.ovf_count.  The clean form then runs
-// over the clean list and appends what it hands on to the rest list, which is launch_match_u8's in list mode right behind.
+// point's class byte and the two index lists in ascending point order -- `lists`: [0] clean count, [1] rest count, [2] advance count,
+// [kU8ListHead, + N) the clean list, then N words of rest list, N words of advance list (rest-list POSITIONS of the window-null points whose
+// climb area is null-free, mx_climb_area above: the clean form tries them in the same launch and marks those it finishes in their rest
+// records) and u8_classify_scratch_ints(N) of scratch -- and zeroes a.ovf_count.  The clean form then runs over the clean list and
+// appends what it hands on to the rest list, which is launch_match_u8's in list mode right behind.
 bool match_mx_supported(int ocw, int max_npiv, int win_half, int max_abs_u, int max_abs_v);
 constexpr int kU8ListHead = 4;
 size_t u8_classify_scratch_ints(int N);
@@ -191,9 +227,11 @@ size_t u8_classify_scratch_ints(int N);
 size_t u8_lists_bytes(int N);
 U8PointRec *u8_list_recs(int32_t *lists, int N);
 bool u8_point_records_on();        // (tuning / A-B: MIMC3_U8_RECS=0 keeps the memory headers)
+bool u8_advance_on();              // (tuning / A-B: MIMC3_U8_ADVANCE=0, or no records, leaves the advance list empty)
 hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream);
 // (u8_classify_kernel.hip; wn_on / gen_on: which forms for null-ridden points run behind the clean form)
-hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, hipStream_t stream);
+// advance: also write the advance list (needs the records) -- else its length is 0
+hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, bool advance, hipStream_t stream);
 // exhaustive-search NCC offsets on the same surfaces (mimc3_match_ncc_full): every point on the matrix cores -- the clean form, then
 // the window-null and general forms over the points it flags (a.mx_flags: N bytes, zero before the call); a.full_R in 1..15,
 // a.ocw one of 7, 15, 16, 30, 32, 40; a.out [N][8]; a.full_peak (optional, int32 [N]) gets every point's arg-max cell k = (su + R)(2R + 1)

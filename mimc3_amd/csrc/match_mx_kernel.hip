@@ -34,6 +34,8 @@
 // here: such a point is appended to the rest list with one atomicAdd, and the register-tiled kernel runs over that list right behind.
 // With point records (U8PointRec, match_kernel.h; RecCfg below) the classifier also leaves, at every list position, the header it has read
 // and derived of that point: the clean form starts from that one record, and a point it appends takes its record along.
+// Behind its clean list the same launch tries the advance list: window-null points whose climb area holds no null, for which the clean
+// form's cells inside that area are exact (mx_climb_area, match_kernel.h) -- finished only if every scan stays inside it.
 // (The exhaustive search classifies in the clean form's header and hands on through the class byte alone: every one of its points
 // stays on this kernel's forms, which run behind in flag mode.)
 #include <hip/hip_runtime.h>
@@ -267,16 +269,26 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     [[maybe_unused]] uint32_t recw = 0u;                     // REC: lane k < 16 holds dword k of the record
     auto rec = [&](int k) __attribute__((always_inline)) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)recw, k); };
     auto rec64 = [&](int k) __attribute__((always_inline)) -> unsigned long long { return ((unsigned long long)rec(k + 1) << 32) | rec(k); };
+    // REC: the launch goes on into the advance list of u8_classify -- rest points whose window holds nulls, but none in the climb area
+    // (mx_climb_area, match_kernel.h).  Workgroup cnt + i takes the point at rest position advance[i], from its rest record; it finishes
+    // the point only if every scan stays inside the area, and then marks the record done for the register-tiled launch (kRecDone)
+    [[maybe_unused]] bool adv = false;
     if (C::REC || p.point_list) {                            // list mode: the clean list of u8_classify (the launch is sized for all N points)
-        const int cnt = *p.point_count;
+        int cnt = *p.point_count;
+        if constexpr (C::REC) {
+            if (gidx >= cnt) {                               // (clean and advance points are disjoint: the N-sized grid holds both)
+                gidx -= cnt; cnt = p.point_count[2]; adv = true;
+            }
+        }
         if (gidx >= cnt) return;
         const int per = cnt >> 3;
         if (gidx < per * 8) gidx = (gidx & 7) * per + (gidx >> 3);              // XCD-contiguous order of the list positions
         if constexpr (C::REC) {
             static_assert(sizeof(U8PointRec) == 64 && offsetof(U8PointRec, rowQ) == 56, "the dword numbers below");
-            rpos = gidx;
-            recw = reinterpret_cast<const uint32_t *>(p.point_recs + rpos)[lane & 15];
+            rpos = adv ? (p.rest_list + p.N)[gidx] : gidx;
+            recw = reinterpret_cast<const uint32_t *>((adv ? p.rest_recs : p.point_recs) + rpos)[lane & 15];
             gidx = (int)rec(0);
+            if (adv && p.stats && tid == 0) p.stats[kStatW * (size_t)blockIdx.x + 7] = 1ull;      // diagnostics: tried
         } else gidx = p.point_list[gidx];
     } else {
         const int nb = gridDim.x, per = nb >> 3;
@@ -286,6 +298,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     if (!C::REC && p.point_flags && p.point_flags[gidx] != (uint8_t)p.flag_value) return;      // flag mode: the points another kernel handed over
     auto hand_on = [&](uint8_t to) __attribute__((always_inline)) {
         if constexpr (C::REC) {
+            if (adv) return;                                 // an advance point that cannot finish is on the rest list already, class and record
             // the point goes to the rest list with its record, which holds all the register-tiled kernel's header reads: fetched again
             // (a few dozen points per launch) rather than carried through the kernel in a register.  Wave 0 calls this, whole
             if (wave == 0) {
@@ -323,7 +336,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     }
     int64_t pbeg;
     int npiv;
-    if constexpr (C::REC) { pbeg = (int64_t)rec64(6); npiv = (int)rec(5); }
+    if constexpr (C::REC) { pbeg = (int64_t)rec64(6); npiv = (int)(rec(5) & kRecNpivMask); }
     else {
         pbeg = C::FULL ? 0 : p.piv_off[gidx];
         npiv = C::FULL ? 1 : (int)(p.piv_off[gidx + 1] - pbeg);
@@ -383,7 +396,12 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     // the tile: all reachable cells if they fit, else centred on the pivots' starts (a scan that leaves it hands the point on)
     int tx0, ty0;
     bool fits;
-    if constexpr (C::REC) { const uint32_t t = rec(8); tx0 = (int)(t & 1023u); ty0 = (int)((t >> 10) & 1023u); fits = ((t >> 20) & 1u) != 0u; }
+    [[maybe_unused]] uint32_t area_w = 0u, tile_w = 0u;      // REC: the record's dwords with the climb area / the done bit, kept in scalar registers
+    if constexpr (C::REC) {
+        const uint32_t t = rec(8);
+        tx0 = (int)(t & 1023u); ty0 = (int)((t >> 10) & 1023u); fits = ((t >> 20) & 1u) != 0u;
+        area_w = rec(5); tile_w = t;
+    }
     else fits = mx_tile_fit(lu, lv, OCW, dx2, dy2, csx, csy, C::FULL ? 0 : 1, tx0, ty0);
     // the null count of the window's written area (:869-886) and the first batch of the tile's pixels: issued now, read below
     int win_nulls_v = 0;
@@ -427,7 +445,8 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     //  of its range, as it always did -- the C ABI refuses empty pivot lists, and the classifier tests npiv before it reads)
     if (!mx_takes(npiv, fits)) { hand_on(kMxRest); return; }
     if (!GEN) {
-        const uint8_t cls = mx_null_class(win_nulls, chip_nulls, p.mx_wn_on, p.mx_gen_on);
+        // (an advance point: its window's nulls lie outside its climb area, the chip's guard stays)
+        const uint8_t cls = mx_null_class((C::REC && adv) ? 0 : win_nulls, chip_nulls, p.mx_wn_on, p.mx_gen_on);
         if (cls != 0) { hand_on(cls); return; }
     }
     // general form: wn = the written area of the window holds nulls (then the never-written last row / column are nulls like any other,
@@ -448,6 +467,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         const float rc = (float)chip_nulls / (float)NPX;
         const float rw = (float)(win_nulls + Dx2 + Dy2 - 1) / (float)(Dx2 * Dy2);
         if (rc > max_ratio || rw > max_ratio) {
+            if (C::REC && adv) return;                        // (left to the register-tiled launch, which counts the nulls it stages)
             if (tid == 0) {
                 const float nanv = __builtin_nanf("");
                 p.out[3 * (size_t)gidx + 0] = nanv; p.out[3 * (size_t)gidx + 1] = nanv; p.out[3 * (size_t)gidx + 2] = -3.0f;
@@ -871,7 +891,10 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     // predicated: one wave-uniform loop, no divergent control flow (the compiler's exec-mask bookkeeping for a per-lane `while` was half
     // the loop's instructions).
     bool alive = lane < npiv && inside(su, sv);
-    bool left = false;                                       // a scan would leave the tile
+    bool left = false;                                       // a scan would leave the tile (REC: the record's area -- the whole tile for a clean point)
+    [[maybe_unused]] int axlo = 1, aylo = 1;
+    [[maybe_unused]] uint32_t awx = 29u, awy = 29u;
+    if constexpr (C::REC) mx_area_scan_bounds(area_w, axlo, awx, aylo, awy);
     uint32_t dlo = 0u, dhi = 0u, updm = 0u;
     int nsc = 0;
     {
@@ -880,7 +903,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         for (int t = 0; t < kSpecRounds; t++) {
             if (!__any(alive)) break;
             const int rx = relx(su), ry = rely(sv);
-            const bool in = (unsigned)(rx - 1) <= 29u && (unsigned)(ry - 1) <= 29u;
+            const bool in = C::REC ? ((unsigned)(rx - axlo) <= awx && (unsigned)(ry - aylo) <= awy) : ((unsigned)(rx - 1) <= 29u && (unsigned)(ry - 1) <= 29u);
             left = left || (alive && !in);
             const bool act = alive && in;
             const float *vp = val + (act ? ry : 1) * VP + (act ? rx : 1);          // (idle lanes read a harmless cell)
@@ -1013,6 +1036,15 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         if (lane < 2) p.out[3 * (size_t)gidx + lane] = o;
         if (lane == 0) p.out[3 * (size_t)gidx + 2] = best;
     }
+    if constexpr (C::REC) {
+        if (adv) {             // finished: the register-tiled launch leaves at this bit of the record's `tile` dword, right behind its header load
+            if (lane == 0) {
+                reinterpret_cast<uint32_t *>(p.rest_recs + rpos)[8] = tile_w | kRecDone;
+                if (p.stats) p.stats[kStatW * (size_t)blockIdx.x + 7] = 2ull;
+            }
+            return;            // ("clean: N points staged" counts the clean list's workgroups alone)
+        }
+    }
     MIMC3_MX_STAMP(6)
     MIMC3_MX_STATS_OUT
 }
@@ -1043,7 +1075,12 @@ static hipError_t launch_one(MatchU8Args a, hipStream_t stream)
         (void)hipMemcpy(hh, d_stats, kStatW * sizeof(unsigned long long) * (size_t)nb, hipMemcpyDeviceToHost);
         unsigned long long hsum[kStatW] = {0};
         size_t live = 0;
-        for (size_t b = 0; b < (size_t)nb; b++) { if (hh[kStatW * b]) live++; for (int i = 0; i < kStatW; i++) hsum[i] += hh[kStatW * b + i]; }
+        size_t adv_tried = 0, adv_done = 0;              // (slot 7: an advance-list workgroup's 1 = tried, 2 = finished; it writes no phase clocks)
+        for (size_t b = 0; b < (size_t)nb; b++) {
+            if (hh[kStatW * b]) live++;
+            for (int i = 0; i < 7; i++) hsum[i] += hh[kStatW * b + i];
+            adv_tried += hh[kStatW * b + 7] != 0; adv_done += hh[kStatW * b + 7] == 2;
+        }
         free(hh);
         const double d = live ? (double)live : 1.0;
         int32_t nn = 0, nr = 0;
@@ -1055,6 +1092,11 @@ static hipError_t launch_one(MatchU8Args a, hipStream_t stream)
         }
         fprintf(stderr, "[mimc3 mx stats] ocw %d %s: %zu points staged; cycles/point: stage %.0f products %.0f box sums %.0f ncc %.0f climb %.0f replay %.0f fit %.0f; lists so far: nulls %d rest %d\n",
                 C::OCW, C::GEN ? (C::CN ? "general" : "window nulls") : "clean", live, hsum[0] / d, hsum[1] / d, hsum[2] / d, hsum[3] / d, hsum[4] / d, hsum[5] / d, hsum[6] / d, nn, nr);
+        if (!C::FULL && !C::GEN && a.mx_classified && a.point_count) {      // (without records the list is empty and no workgroup tries)
+            int32_t nadv = 0;
+            (void)hipMemcpy(&nadv, a.point_count + 2, sizeof(nadv), hipMemcpyDeviceToHost);
+            fprintf(stderr, "[mimc3 mx stats] advance: list %d tried %zu finished %zu\n", nadv, adv_tried, adv_done);
+        }
     }
     return hipGetLastError();
 }
@@ -1122,6 +1164,13 @@ static hipError_t launch_rec_form(const MatchU8Args &a, hipStream_t stream)
     }
 }
 
+bool u8_advance_on()
+{
+    // tuning / A-B: 0 = no advance list (every window-null point waits for the register-tiled launch); needs the point records
+    static const int on = getenv("MIMC3_U8_ADVANCE") ? atoi(getenv("MIMC3_U8_ADVANCE")) : 1;
+    return on != 0 && u8_point_records_on();
+}
+
 bool u8_point_records_on()
 {
     static const int on = getenv("MIMC3_U8_RECS") ? atoi(getenv("MIMC3_U8_RECS")) : 1;      // tuning / A-B: 0 = the headers read memory, as without records
@@ -1152,7 +1201,7 @@ hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
     // there, and a point it hands on takes its record along to the rest list
     a.point_recs = nullptr; a.rest_recs = nullptr;
     if (u8_point_records_on()) { a.point_recs = u8_list_recs(lists, a.N); a.rest_recs = u8_list_recs(lists, a.N) + (size_t)a.N; }
-    hipError_t e = launch_u8_classify(a, lists, stream);
+    hipError_t e = launch_u8_classify(a, lists, u8_advance_on(), stream);
     if (e == hipSuccess) e = mx::classify_stats(a, lists, stream);
     if (e == hipSuccess) e = a.point_recs ? launch_rec_form(a, stream) : launch_form<false, false>(a, stream);
     a.point_list = nullptr; a.point_count = nullptr; a.point_recs = nullptr;

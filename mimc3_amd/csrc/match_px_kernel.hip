@@ -765,6 +765,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
         if constexpr (kRec) {
             static_assert(sizeof(U8PointRec) == 64 && offsetof(U8PointRec, chipQ) == 40, "the dword numbers below");
             recw = reinterpret_cast<const uint32_t *>(p.point_recs + gidx)[lane & 15];
+            if (rec(8) & kRecDone) return;                   // an advance point the matrix-core launch has finished (match_mx_kernel.hip)
             gidx = (int)rec(0);
         } else gidx = p.point_list[gidx];
     } else {
@@ -782,7 +783,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
     int u0, v0, npiv, lu, lv;
     int64_t pbeg;
     if constexpr (kRec) {           // (the record's dwords by number, see U8PointRec)
-        u0 = (int)rec(1); v0 = (int)rec(2); lu = (int)rec(3); lv = (int)rec(4); npiv = (int)rec(5);
+        u0 = (int)rec(1); v0 = (int)rec(2); lu = (int)rec(3); lv = (int)rec(4); npiv = (int)(rec(5) & kRecNpivMask);
         pbeg = (int64_t)(((unsigned long long)rec(7) << 32) | rec(6));
     } else {
         const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;   // (u, v): columns 2, 3 of an xyuvav row, or a packed [N][2] array
