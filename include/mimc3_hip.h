@@ -265,7 +265,8 @@ int mimc3_match_ncc_full_dn_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *   mode 0   dispatch by the class of the pair the context currently matches on: 8-bit, scaled-integer and integral-f32 pairs go where
  *            mimc3_match_ncc_full_dn sends them (mimc3_ctx_last_path 6, 7, 8), bit for bit; every other f32 pair runs the float kernel
  *            (match_full_f32g_kernel.hip) on the zero-bordered f32 planes, without tables.  mimc3_ctx_last_path reports 9.
- *   mode 1   the float kernel on any pair, whatever its class (tests; and the only way to the surfaces of an integer-class pair).
+ *   mode 1   the float kernel on any pair, whatever its class (tests; and this entry's only way to the surfaces of an integer-class
+ *            pair -- mimc3_match_ncc_full_surf below returns them from the class kernels).
  *   Any other mode: MIMC3_EINVAL.
  *   surf     optional (NULL: none), f32 [N][(2R+1)^2]: every point's NCC surface in k order, k = (su + R)(2R + 1) + (sv + R); all NaN at
  *            status -3 (and for a point of the _dev entry that breaks the bounds).  Only the float kernel serves it: surf != NULL on a
@@ -306,6 +307,31 @@ int mimc3_match_ncc_full_any(mimc3_ctx *ctx, const double *xyuvav, int32_t N, co
 int mimc3_match_ncc_full_any_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                  const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
                                  float *d_cand, float *d_surf, void *stream);
+
+/* ---- The surfaces from the kernel of the pair's class: the dispatch of mimc3_match_ncc_full_any(mode 0) with surf MANDATORY and served by
+ *      whichever kernel runs -- the matrix-core kernel on an 8-bit pair, the u16 and integral-f32 kernels on theirs (each in a form that
+ *      also stores the finished surface it holds in LDS), the float kernel on every other pair.  What a stack layer needs
+ *      (mimc3_stack_add_class), at the cost of the class's own search plus the surface writes.
+ *
+ *   Arguments   those of mimc3_match_ncc_full_any without `mode`.  1 <= R <= 15, npeaks 0..8, cand NULL iff npeaks == 0.
+ *   out, cand   exactly the record and the candidates of mimc3_match_ncc_full_dn on an integer-class pair (of mimc3_match_ncc_full_any
+ *               on a float pair), bit for bit.  mimc3_ctx_last_path reports 6 / 7 / 8 / 9 as the dispatch decides.
+ *   surf        f32 [N][(2R+1)^2] in k order, k = (su + R)(2R + 1) + (sv + R); all NaN at status -3 (and for a point of the _dev entry
+ *               that breaks the bounds).  On an integer-class pair every sum is an exact integer in any order and every kernel finishes a
+ *               cell with the reference's operations, so the surface equals that of mimc3_match_ncc_full_any(mode 1, surf) cell for cell
+ *               AS F32 VALUES: finite cells are bit for bit, a non-finite cell is of the same kind (NaN, +Inf or -Inf); NaN payload bits
+ *               are not part of the contract.  On a float pair the call IS mimc3_match_ncc_full_any(mode 0, surf): the same bytes.
+ *   Refusals    surf NULL: MIMC3_EINVAL (with the other arguments); every other refusal is mimc3_match_ncc_full_any's, in its order.
+ *   mimc3_match_ncc_full_any itself is unchanged: surf on a call an integer kernel runs stays MIMC3_EINVAL there.
+ *   Out of scope: the pyramid entries, several GPUs, MIMC3_hip_offsets. */
+int mimc3_match_ncc_full_surf(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                              const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                              int32_t swap, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
+                              float *surf /*[N][(2R+1)^2] host*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_any_dev without `mode`; d_surf is required. */
+int mimc3_match_ncc_full_surf_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                  const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                                  float *d_cand, float *d_surf, void *stream);
 
 /* ---- Exhaustive search beyond +-15 px: ONE exact pass at full resolution over a search range of up to +-47 px, with candidates from the
  *      whole range -- for a displacement the a-priori shift misses by more than 15 px, which the entries above return as status -4 or
@@ -495,6 +521,20 @@ int mimc3_stack_add(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32
  * point that breaks the host entry's bounds has an all-NaN surface and counts as a layer (the contract of the _dev search entries). */
 int mimc3_stack_add_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
                         void *stream);
+/* mimc3_stack_add through the kernel of the pair's class: its arguments and its refusals.  On a stack of R <= 15 the layer is
+ * mimc3_match_ncc_full_surf(npeaks 0, shift = the stack's, surf) -- the same chunks of mimc3_stack_chunk(R) points through the same layer
+ * scratch and the same accumulation -- so an 8-bit, 12-bit or 16-bit DN layer costs its own kernel's search and not the float kernel's.
+ * The accumulation adds only finite cells and takes the refused points from the record's status -3, and the class kernel's finite
+ * cells and records are the float kernel's bit for bit (see mimc3_match_ncc_full_surf): the stack's state after this call -- sum, cnt,
+ * lay, wsum -- is bit for bit the state after mimc3_stack_add, on every pixel class, and the two may be mixed freely.  A weighted
+ * stack's wsum gets 1.0 per finite cell, as from mimc3_stack_add.  On a stack of R >= 16 the call IS mimc3_stack_add (the wide kernel),
+ * byte for byte: a caller does not have to branch.  mimc3_ctx_last_path reports the kernel that ran (6 / 7 / 8 / 9; 10 beyond R 15).
+ * Not covered: scaled layers through the class kernels, an accumulation fused into the search (the layer scratch round trip stays). */
+int mimc3_stack_add_class(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap);
+/* Device-resident variant, under the contract of mimc3_stack_add_dev (a first call on a pair builds the planes and tables its kernel
+ * reads on the context's own stream and waits for them first). */
+int mimc3_stack_add_class_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
+                              void *stream);
 /* One layer from the caller's surfaces -- of another context, of a later kernel, crafted: surf [N][S^2] in k order, refused [N]
  * (not 0 = refused) or NULL (no point is).  Refusals: the stack's, as above. */
 int mimc3_stack_add_surfaces(mimc3_ctx *ctx, const float *surf /*host [N][S^2]*/, const uint8_t *refused /*host [N] or NULL*/, int32_t N);

@@ -61,6 +61,9 @@ _lib.mimc3_match_ncc_full_any.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c
                                           _vp, _vp]
 _lib.mimc3_match_ncc_full_any_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_int32, _vp, _vp, _vp, _vp]
+_lib.mimc3_match_ncc_full_surf.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
+_lib.mimc3_match_ncc_full_surf_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               _vp, _vp, _vp, _vp]
 _lib.mimc3_wide_max_radius.argtypes = [C.c_int32]
 _lib.mimc3_wide_lds_bytes.argtypes = [C.c_int32, C.c_int32]
 _lib.mimc3_match_ncc_wide.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
@@ -80,6 +83,8 @@ _lib.mimc3_stack_chunk.argtypes = [C.c_int32]
 _lib.mimc3_stack_chunk.restype = C.c_int32
 _lib.mimc3_stack_add.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32]
 _lib.mimc3_stack_add_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
+_lib.mimc3_stack_add_class.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32]
+_lib.mimc3_stack_add_class_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
 _lib.mimc3_stack_add_surfaces.argtypes = [_vp, _f32p, _vp, C.c_int32]
 _lib.mimc3_stack_add_surfaces_dev.argtypes = [_vp, _vp, _vp, C.c_int32, _vp]
 _lib.mimc3_stack_finish.argtypes = [_vp, C.c_int32, C.c_int32, _f32p, _vp, _vp, _vp]
@@ -614,6 +619,24 @@ class Context:
                                                  npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
                "match_ncc_full_any_dev")
 
+    def match_ncc_full_surf(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False):
+        """The exhaustive search with every point's NCC surface from the kernel of the pair's class (mimc3_match_ncc_full_surf): the
+        dispatch of match_ncc_full_any(mode=0) -- "u8_mfma_full", "u16_full", "f32i_full" or "f32g_full" -- with the surfaces served by
+        whichever kernel runs -> (float32[N][8] record and float32[npeaks][N][3] candidates or None when npeaks == 0, exactly
+        match_ncc_full_dn's on an integer-class pair, float32[N][(2 radius + 1)^2] surfaces in k order).  The surface equals
+        match_ncc_full_any(mode=1, surface=True)'s cell for cell as f32 values (finite cells bit for bit, a non-finite cell of the same
+        kind; NaN payloads are not part of the contract)."""
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_surf", xyuvav, shift, npeaks=npeaks, radius=radius, surface=True)
+        _check(_lib.mimc3_match_ncc_full_surf(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh), ocw, radius, int(npeaks),
+                                              1 if swap else 0, out, _ptr(cand), _ptr(surf)), "match_ncc_full_surf")
+        return out, cand, surf
+
+    def match_ncc_full_surf_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_surf, d_cand=0, d_shift=0, stream=0, swap=False):
+        """Device-pointer variant (enqueue only): as match_ncc_full_any_dev without mode; d_surf float32[n][(2 radius + 1)^2] is required."""
+        _check(_lib.mimc3_match_ncc_full_surf_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                  npeaks, 1 if swap else 0, d_out, d_cand or None, d_surf or None, stream),
+               "match_ncc_full_surf_dev")
+
     def match_ncc_wide(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False, surface=False):
         """The exhaustive search beyond +-15 px (mimc3_match_ncc_wide): match_ncc_full_any(mode=1) with 1 <= radius <=
         wide_max_radius(ocw) -- up to +-47 px in one exact pass at full resolution, candidates from the whole range.  radius <= 15 is
@@ -699,6 +722,19 @@ class Context:
     def stack_add_dev(self, d_xyuvav, n, offset, ocw, stream=0, swap=False):
         """Device-pointer variant (enqueue only)."""
         _check(_lib.mimc3_stack_add_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), ocw, 1 if swap else 0, stream), "stack_add_dev")
+
+    def stack_add_class(self, xyuvav, offset, ocw, swap=False):
+        """stack_add through the kernel of the pair's class (mimc3_stack_add_class): on a stack of radius <= 15 the layer's surfaces are
+        match_ncc_full_surf's -- the matrix cores on an 8-bit pair, the u16 or f32 planes' kernels on 12- and 16-bit DN -- and the
+        stack's state afterwards is bit for bit stack_add's; on a stack of radius >= 16 it is stack_add."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        _check(_lib.mimc3_stack_add_class(self._h, xy, xy.shape[0], np.ascontiguousarray(offset, np.int32), ocw, 1 if swap else 0),
+               "stack_add_class")
+
+    def stack_add_class_dev(self, d_xyuvav, n, offset, ocw, stream=0, swap=False):
+        """Device-pointer variant (enqueue only)."""
+        _check(_lib.mimc3_stack_add_class_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), ocw, 1 if swap else 0, stream),
+               "stack_add_class_dev")
 
     def stack_add_surfaces(self, surf, refused=None):
         """One layer from the caller's surfaces float32[n][(2 radius + 1)^2] in k order; refused bool[n] (None = no point is)."""

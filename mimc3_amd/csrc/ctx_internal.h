@@ -175,6 +175,8 @@ struct SearchRules {
     bool fb = false;                    // returns forward-backward rows: d_fb is required
     bool pyramid = false;               // takes `levels`
     bool layer = false;                 // a stack's layer add: no record of its own, and a radius that the stack refuses in its own words
+    bool class_surf = false;            // the surfaces come from whichever kernel runs, an integer class's too (mimc3_match_ncc_full_surf,
+                                        // where they are mandatory, and the stack's class layers)
 };
 enum SearchKernel { Mx, U16, F32i, F32g, Wide };                      // last_path 6 .. 10
 struct PlaneSet {
@@ -189,7 +191,7 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
 // -- or, for a pyramid entry, every starting displacement offset + shift within +-2^24, so that every level's shifts stay exact int32
 int search_check_host(const mimc3_ctx *c, const char *entry, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
                       int32_t ocw, int32_t R, bool pyramid = false);
-int pick_kernel(mimc3_ctx *c, const SearchCall &call, SearchKernel &kernel);
+int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel);
 int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &planes);
 int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &planes, const SearchCall &call);
 

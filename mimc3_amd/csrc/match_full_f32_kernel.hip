@@ -44,6 +44,7 @@ struct Cfg {
     static constexpr int OCW = OCW_, CW = 2 * OCW_ + 1, NPX = CW * CW;
     static constexpr bool DIRTY = DIRTY_;
     static constexpr bool PEAK = false, MULTI = MULTI_;         // (what match_full_tail.h asks of a configuration)
+    static constexpr bool SURF = false;                         // also store the finished surface to full_surf (SurfCfg)
     static constexpr int VP = 33;                               // pitch (words) of the NCC surface
     static constexpr int NT = 256;
     static constexpr int RMAX = 15;
@@ -65,6 +66,13 @@ struct Cfg {
 template <int OCW_, bool DIRTY_>
 struct PeakCfg : Cfg<OCW_, DIRTY_, false> {
     static constexpr bool PEAK = true;
+};
+
+// ... and with the surfaces (mimc3_match_ncc_full_surf, the stack's class layers): the same record and candidates, plus every point's
+// finished f32 surface in full_surf, in k order -- all NaN for a point that gets no_record.  A configuration of its own, as PeakCfg
+template <int OCW_, bool DIRTY_, bool MULTI_>
+struct SurfCfg : Cfg<OCW_, DIRTY_, MULTI_> {
+    static constexpr bool SURF = true;
 };
 
 template <class C>
@@ -93,6 +101,11 @@ __global__ __launch_bounds__(C::NT) void match_ncc_full_f32(MatchU8Args p)
     // ---- point header: the refusals, the class and the validity rule of the other fronts ---------------------------------------------
     auto no_record = [&](float status) __attribute__((always_inline)) {
         if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_peak_store<C>(p, gidx, -1); mx::full_cand_fill<C>(p, gidx, status); }
+        if constexpr (C::SURF) {                            // (no surface exists: all NaN, as the float kernel's)
+            const int NC = (2 * p.full_R + 1) * (2 * p.full_R + 1);
+            float *sf = p.full_surf + (size_t)gidx * (size_t)NC;
+            for (int k = tid; k < NC; k += NT) sf[k] = __builtin_nanf("");
+        }
     };
     const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;
     const int u0 = (int)row[0], v0 = (int)row[1];
@@ -210,6 +223,13 @@ __global__ __launch_bounds__(C::NT) void match_ncc_full_f32(MatchU8Args p)
         }
     }
     __syncthreads();
+    if constexpr (C::SURF) {                                // the surface in k order (u outer): coalesced stores, LDS reads at stride VP
+        float *sf = p.full_surf + (size_t)gidx * (size_t)(S * S);
+        for (int k = tid; k < S * S; k += NT) {
+            const int x = k / S, yy = k - S * x;
+            sf[k] = val[yy * VP + x];
+        }
+    }
     if (wave != 0) return;
     mx::full_tail<C>(p, val, gidx, lu, lv, lane);
     if constexpr (C::MULTI) mx::full_tail_multi<C>(p, val, gidx, lu, lv, lane);
@@ -237,10 +257,14 @@ static hipError_t launch_pair(const MatchU8Args &a, hipStream_t stream)
     return launch_one<Dirty>(a, nb, stream);
 }
 
-// the record alone, with the arg-max cells (PEAK) or with the candidates (MULTI)
+// the record alone, with the arg-max cells (PEAK) or with the candidates (MULTI); with full_surf the SURF form of the latter two
 template <int OCW>
 static hipError_t launch_ocw(const MatchU8Args &a, hipStream_t stream)
 {
+    if (a.full_surf) {
+        if (a.full_cand) return launch_pair<SurfCfg<OCW, false, true>, SurfCfg<OCW, true, true>>(a, stream);
+        return launch_pair<SurfCfg<OCW, false, false>, SurfCfg<OCW, true, false>>(a, stream);
+    }
     if (a.full_peak) return launch_pair<PeakCfg<OCW, false>, PeakCfg<OCW, true>>(a, stream);
     if (a.full_cand) return launch_pair<Cfg<OCW, false, true>, Cfg<OCW, true, true>>(a, stream);
     return launch_pair<Cfg<OCW, false, false>, Cfg<OCW, true, false>>(a, stream);
@@ -253,6 +277,7 @@ hipError_t launch_match_full_f32(MatchU8Args a, hipStream_t stream)
     if (a.N <= 0) return hipSuccess;
     if (!a.p0 || !a.p1 || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15 || !(a.scale0 > 0.0) || !(a.scale1 > 0.0)) return hipErrorInvalidValue;
     if (a.full_cand && (a.full_peak || a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks)) return hipErrorInvalidValue;
+    if (a.full_surf && a.full_peak) return hipErrorInvalidValue;
     switch (a.ocw) {
     case 7: return ff32::launch_ocw<7>(a, stream);
     case 15: return ff32::launch_ocw<15>(a, stream);

@@ -70,7 +70,12 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
         int32_t *ovf_list;          // points whose NCC cache overflowed: handed to the general kernel (list mode)
         float *full_cand;           // exhaustive search, optional: f32 [full_npeaks][N][3] (du, dv, ncc); null = the record alone
     };
-    int32_t *ovf_count;
+    // (exhaustive search with surfaces, mimc3_match_ncc_full_surf: the surface-storing forms of the three integer-class kernels; the
+    //  pointer shares the slot of the overflow list's counter, which full mode never reads)
+    union {
+        int32_t *ovf_count;
+        float *full_surf;           // exhaustive search, optional: f32 [N][(2 full_R + 1)^2], every point's surface in k order; null = none
+    };
     const int32_t *point_list, *point_count;   // list mode: workgroup b handles point_list[b], b < *point_count (nullptr = all N points)
     // PxU8o: points whose chip or window does not fit a local 8-bit range.  Matrix-core DLC kernel behind u8_classify: the rest list --
     // a point the kernel meets but does not take (a climb that leaves the tile or outlasts the recorded scans: a few dozen per launch)
@@ -237,12 +242,14 @@ hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, bool advance
 // a.ocw one of 7, 15, 16, 30, 32, 40; a.out [N][8]; a.full_peak (optional, int32 [N]) gets every point's arg-max cell k = (su + R)(2R + 1)
 // + (sv + R), also at status -4, or -1 without one (status -3 / -2, the NaN record of a point outside the image or the zero border);
 // a.full_cand (optional, f32 [a.full_npeaks][N][3], 1 <= full_npeaks <= kFullMaxPeaks; not together with full_peak) gets every point's
-// best local maxima as (du, dv, ncc) candidates (mimc3_match_ncc_full_multi) -- null selects the kernels without that tail
+// best local maxima as (du, dv, ncc) candidates (mimc3_match_ncc_full_multi) -- null selects the kernels without that tail;
+// a.full_surf (optional, f32 [N][(2 full_R + 1)^2]; not together with full_peak) gets every point's surface in k order, k = (su + R)(2R + 1)
+// + (sv + R), from the form that finishes the point -- all NaN where the record is all NaN or has status -3 -- and selects the SURF forms
 constexpr int kFullMaxPeaks = 8;
 hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream);
 // the same search on the zero-bordered u16 planes of a scaled-integer pair (match_full_u16_kernel.hip): a.p0 / a.p1 the u16 planes, a.sat0 /
 // a.sat1 their packed tables, a.satz0 / a.satz1 their null tables; a.full_shift, a.full_R, a.full_peak, a.full_cand / a.full_npeaks and a.out as
-// above.  Two launches, the points without nulls and those with; no flags, lists or scratch
+// above, a.full_surf too.  Two launches, the points without nulls and those with; no flags, lists or scratch
 hipError_t launch_match_full_u16(MatchU8Args a, hipStream_t stream);
 // the same search on the zero-bordered f32 planes of an integral-f32 pair (match_full_f32_kernel.hip; 16-bit DN and its filtered forms):
 // a.p0 / a.p1 the f32 planes, a.sat0 / a.sat1 their 16-byte tables (Sat2), a.scale0 / a.scale1 = 2^-s of each image (pixel * 2^s is the

@@ -110,6 +110,7 @@ struct Cfg {
     static constexpr bool FULL = false;                 // the DLC matcher (true: FullCfg, the exhaustive search)
     static constexpr bool PEAK = false;                 // full mode: also write the arg-max cell to full_peak (FullPeakCfg)
     static constexpr bool MULTI = false;                // full mode: also write the best local maxima as candidates to full_cand (FullMultiCfg)
+    static constexpr bool SURF = false;                 // full mode: also store the finished surface to full_surf (FullSurfCfg, FullMultiSurfCfg)
     static constexpr bool REC = false;                  // the header comes from u8_classify's point record (RecCfg)
 };
 // The clean form behind u8_classify with point records (U8PointRec, match_kernel.h): workgroup b starts from the record at list position b
@@ -138,6 +139,19 @@ struct FullPeakCfg : FullCfg<OCW_, GEN_, CN_> {
 template <int OCW_, bool GEN_, bool CN_>
 struct FullMultiCfg : FullCfg<OCW_, GEN_, CN_> {
     static constexpr bool MULTI = true;
+};
+
+// ... and with the surfaces (mimc3_match_ncc_full_surf, the stack's class layers): the record-only form and the form with candidates,
+// each also storing the point's finished f32 surface to full_surf in k order; all NaN where the point leaves before it has one.  Only
+// the form that finishes a point stores it: the clean form hands null-ridden points on, the flag-mode forms behind it store theirs.
+// (Template forms and not a run-time branch: the kernel is register-tight, and the existing instantiations keep their code.)
+template <int OCW_, bool GEN_, bool CN_>
+struct FullSurfCfg : FullCfg<OCW_, GEN_, CN_> {
+    static constexpr bool SURF = true;
+};
+template <int OCW_, bool GEN_, bool CN_>
+struct FullMultiSurfCfg : FullMultiCfg<OCW_, GEN_, CN_> {
+    static constexpr bool SURF = true;
 };
 
 // The constant band operands, one table per chip size (constant-initialised device data).  v_mfma_i32_16x16x64_i8: lane (n = lane & 15,
@@ -320,6 +334,14 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const unsigned char *chip_pl = p.swap ? p.p1 : p.p0;
     const unsigned char *win_pl = p.swap ? p.p0 : p.p1;
     const int Wp = p.Wp, PAD = p.pad;
+    // SURF: a point that leaves before its surface exists gets an all-NaN one, as the float kernel's (both waves store)
+    auto surf_nan = [&]() __attribute__((always_inline)) {
+        if constexpr (C::SURF) {
+            const int NC = (2 * p.full_R + 1) * (2 * p.full_R + 1);
+            float *sf = p.full_surf + (size_t)gidx * (size_t)NC;
+            for (int k = tid; k < NC; k += NT) sf[k] = __builtin_nanf("");
+        }
+    };
 
     // ---- point header (as match_px_kernel.hip) ---------------------------------------------------------------------
     // (REC: u8_classify has read and derived all of it; the record's dwords by number, see U8PointRec)
@@ -332,6 +354,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     // (full mode, a point that breaks the bounds mimc3_match_ncc_full refuses -- only the _dev entry can pass one: no read, all NaN)
     if (C::FULL && (u0 - OCW < 0 || u0 + OCW >= p.W || v0 - OCW < 0 || v0 + OCW >= p.H)) {
         if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); full_cand_fill<C>(p, gidx, __builtin_nanf("")); }
+        surf_nan();
         return;
     }
     int64_t pbeg;
@@ -390,6 +413,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     const int wu0 = u0 + p.off_u - dx2 + PAD + (C::FULL ? lu : 0), wv0 = v0 + p.off_v - dy2 + PAD + (C::FULL ? lv : 0);   // plane position of window pixel (0, 0)
     if (C::FULL && (wu0 < 0 || wv0 < 0 || wu0 + Dx2 > p.W + 2 * PAD || wv0 + Dy2 > p.H + 2 * PAD)) {
         if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, __builtin_nanf("")); full_peak_store<C>(p, gidx, -1); full_cand_fill<C>(p, gidx, __builtin_nanf("")); }
+        surf_nan();
         return;
     }
     // ---- what this kernel takes -----------------------------------------------------------------------------------
@@ -460,6 +484,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         const float rw = (float)win_nulls / (float)(Dx2 * Dy2);
         if (rc > max_ratio || rw > max_ratio) {
             if (tid == 0) { full_store(p.out + 8 * (size_t)gidx, -3.0f); full_peak_store<C>(p, gidx, -1); full_cand_fill<C>(p, gidx, -3.0f); }
+            surf_nan();
             return;
         }
     } else {
@@ -859,6 +884,14 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     }
     __syncthreads();
     MIMC3_MX_STAMP(3)
+    if constexpr (C::SURF) {                                // the surface in k order (u outer): coalesced stores, LDS reads at stride VP
+        const int S = 2 * p.full_R + 1, NC = S * S;
+        float *sf = p.full_surf + (size_t)gidx * (size_t)NC;
+        for (int k = (int)threadIdx.x; k < NC; k += NT) {
+            const int x = k / S, y = k - S * x;
+            sf[k] = val[y * VP + x];
+        }
+    }
     if (wave != 0) return;                                  // the sequential part needs one wave (lane k = pivot k)
     if constexpr (C::FULL) {
         full_tail<C>(p, val, gidx, lu, lv, lane);
@@ -1213,7 +1246,8 @@ hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
 
 // Exhaustive search: every point on the matrix cores.  The clean form runs over all points and flags the null-ridden ones for the
 // window-null form (nulls in the search box only) or the general form (chip nulls too), which run right behind in flag mode.
-// (FC: FullCfg, FullPeakCfg when the caller wants the arg-max cells, or FullMultiCfg when it wants the candidates)
+// (FC: FullCfg, FullPeakCfg when the caller wants the arg-max cells, or FullMultiCfg when it wants the candidates; FullSurfCfg /
+//  FullMultiSurfCfg when it wants the surfaces as well)
 template <template <int, bool, bool> class FC, bool GEN, bool CN>
 static hipError_t launch_full_form(const MatchU8Args &a, hipStream_t stream)
 {
@@ -1244,10 +1278,12 @@ hipError_t launch_match_full_mx(MatchU8Args a, hipStream_t stream)
     if (!a.mx_flags || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15) return hipErrorInvalidValue;
     a.mx_wn_on = 1; a.mx_gen_on = 1; a.mx_classified = 0;
     a.point_list = nullptr; a.point_count = nullptr; a.point_flags = nullptr; a.point_recs = nullptr; a.rest_recs = nullptr;
+    if (a.full_surf && a.full_peak) return hipErrorInvalidValue;
     if (a.full_cand) {
         if (a.full_peak || a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks) return hipErrorInvalidValue;
-        return launch_full_forms<mx::FullMultiCfg>(a, stream);
+        return a.full_surf ? launch_full_forms<mx::FullMultiSurfCfg>(a, stream) : launch_full_forms<mx::FullMultiCfg>(a, stream);
     }
+    if (a.full_surf) return launch_full_forms<mx::FullSurfCfg>(a, stream);
     return a.full_peak ? launch_full_forms<mx::FullPeakCfg>(a, stream) : launch_full_forms<mx::FullCfg>(a, stream);
 }
 

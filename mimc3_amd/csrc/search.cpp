@@ -1,5 +1,5 @@
 // search.cpp -- the host layer of the exhaustive-search family of the C ABI (include/mimc3_hip.h): mimc3_match_ncc_full, _full_multi,
-// _full_planes, _full_dn, _full_any, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
+// _full_planes, _full_dn, _full_any, _full_surf, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
 // _pyramid_any), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
 // (SearchRules); search_check makes every refusal, pick_kernel selects the kernel, plane_set points at the planes it reads (building
 // them on first use), launch_search is the one place that launches.  The stack's layer adds (stack.cpp) go through the same functions.
@@ -39,15 +39,15 @@ static int check_class(mimc3_ctx *c, PairClass widest, const std::string &en)
 }
 
 // Every refusal the family makes from a call's description, in this order (the first one met decides the code):
-//   1. the arguments, MIMC3_EINVAL: a null context, point array or record, N <= 0, candidates that do not go with npeaks; npeaks out of
-//      range; ocw not one of the six; R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw)); levels outside 1..5
+//   1. the arguments, MIMC3_EINVAL: a null context, point array or record, N <= 0, candidates that do not go with npeaks, no surfaces
+//      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six; R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw)); levels outside 1..5
 //   2. the context's state, MIMC3_ESTATE: no images; a chip-atlas context
 //   3. the pair's class, MIMC3_EUNSUPPORTED
 //   4. MIMC3_EINVAL again: a coarsest pyramid level smaller than a chip; a mode other than 0 or 1; forward-backward rows without d_fb.
 //      The _dev entries of the full searches have always made the last two with the arguments, under 1, and keep doing so: without
 //      images they answer a bad mode with MIMC3_EINVAL where their host entries and the pyramids answer MIMC3_ESTATE.
 // A host entry then makes the checks that need the points (search_check_host); the surfaces asked of an integer kernel are refused
-// once the kernel is known (pick_kernel).
+// once the kernel is known (pick_kernel), unless the entry's rules let every kernel serve them (class_surf).
 int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
 {
     const std::string en(call.entry);
@@ -55,7 +55,7 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
     const bool bad_mode = rules.has_mode && call.mode != 0 && call.mode != 1, no_fb = rules.fb && !call.d_fb;
     const bool mismatch = rules.cand == kCandOptional && (call.npeaks == 0) != (call.d_cand == nullptr);
     if (!c || !call.d_xyuvav || (!call.d_out && !rules.layer) || call.N <= 0 || (rules.cand == kCandMandatory && !call.d_cand) ||
-        (mismatch && !call.host) || (early && no_fb))
+        (rules.class_surf && !rules.layer && !call.d_surf) || (mismatch && !call.host) || (early && no_fb))
         return fail(MIMC3_EINVAL, en + ": bad argument");
     const int32_t least = rules.cand == kCandMandatory ? 1 : 0;
     if (rules.cand != kCandAbsent && (call.npeaks < least || call.npeaks > kFullMaxPeaks))
@@ -97,8 +97,9 @@ int search_check_host(const mimc3_ctx *c, const char *entry, const double *xyuva
 
 // The kernel of a checked call: beyond R 15 the wide float kernel (only the wide entries let such a radius through); in mode 1 the
 // float kernel; else the kernel of the pair's class -- matrix cores on an 8-bit pair, u16 planes on a scaled-integer one, f32 planes
-// with tables on an integral-f32 one, the float kernel on any other.  Only the float kernels serve the surfaces.
-int pick_kernel(mimc3_ctx *c, const SearchCall &call, SearchKernel &kernel)
+// with tables on an integral-f32 one, the float kernel on any other.  Only the float kernels serve the surfaces, unless the rules
+// say class_surf: then the integer kernels run their surface-storing forms.
+int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel)
 {
     if (call.R > 15) kernel = Wide;
     else if (call.mode == 1) kernel = F32g;
@@ -107,7 +108,7 @@ int pick_kernel(mimc3_ctx *c, const SearchCall &call, SearchKernel &kernel)
         RC_TRY(pair_class(c, cls));
         kernel = cls == kU8 ? Mx : cls == kScaledInt ? U16 : cls == kIntegralF32 ? F32i : F32g;
     }
-    if (kernel < F32g && call.d_surf)
+    if (kernel < F32g && call.d_surf && !rules.class_surf)
         return fail(MIMC3_EINVAL, std::string(call.entry) + ": only the float kernel serves the surfaces (mode 1, or a pair of no integer class)");
     return 0;
 }
@@ -227,6 +228,7 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
     u.H = pl.H; u.W = pl.W; u.Wp = pl.Wp;
     u.full_shift = call.d_shift; u.full_R = call.R; u.full_peak = call.d_peak;
     if (call.d_cand) { u.full_cand = call.d_cand; u.full_npeaks = call.npeaks; }
+    if (kernel < F32g) u.full_surf = call.d_surf;           // (the float kernels take it as an argument of its own)
     u.p0 = static_cast<const unsigned char *>(pl.p0); u.p1 = static_cast<const unsigned char *>(pl.p1);
     if (pl.sat0) { u.sat0 = pl.sat0; u.sat1 = pl.sat1; u.satz0 = pl.satz0; u.satz1 = pl.satz1; u.sat_ws = sat_pitch(pl.Wp); }
     u.scale0 = pl.scale0; u.scale1 = pl.scale1;
@@ -247,12 +249,13 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
     return 0;
 }
 
-// ---- what each public entry accepts ----                widest        mode   wide   candidates      fb     pyramid
+// ---- what each public entry accepts ----                widest        mode   wide   candidates      fb     pyramid  layer  class_surf
 static const SearchRules kFull = {kU8, false, false, kCandAbsent};
 static const SearchRules kFullMulti = {kU8, false, false, kCandMandatory};
 static const SearchRules kFullPlanes = {kScaledInt, false, false, kCandOptional};
 static const SearchRules kFullDn = {kIntegralF32, false, false, kCandOptional};
 static const SearchRules kFullAny = {kFloat, true, false, kCandOptional};
+static const SearchRules kFullSurf = {kFloat, false, false, kCandOptional, false, false, false, true};     // (class_surf: surf is mandatory)
 static const SearchRules kWide = {kFloat, false, true, kCandOptional};
 static const SearchRules kFullFb = {kFloat, true, false, kCandOptional, true};
 static const SearchRules kWideFb = {kFloat, false, true, kCandOptional, true};
@@ -276,7 +279,7 @@ static int search_dev(mimc3_ctx *c, const SearchCall &call, const SearchRules &r
     HIP_TRY(hipSetDevice(c->device));
     SearchKernel kernel;
     PlaneSet planes;
-    RC_TRY(pick_kernel(c, call, kernel));
+    RC_TRY(pick_kernel(c, call, rules, kernel));
     RC_TRY(plane_set(c, kernel, 0, planes));
     return launch_search(c, kernel, planes, call);
 }
@@ -304,7 +307,7 @@ static int full_fb_dev(mimc3_ctx *c, const SearchCall &call, const SearchRules &
     TimingSuspended whole(c);           // (the events bracket the whole call, not its last search)
     SearchKernel kernel;
     PlaneSet planes;
-    RC_TRY(pick_kernel(c, call, kernel));
+    RC_TRY(pick_kernel(c, call, rules, kernel));
     RC_TRY(plane_set(c, kernel, 0, planes));
     RC_TRY(launch_search(c, kernel, planes, call));
     double *xy2 = static_cast<double *>(c->fb_xy.p);
@@ -337,7 +340,7 @@ static int pyramid_dev(mimc3_ctx *c, const SearchCall &call, const SearchRules &
     const int32_t N = call.N, levels = call.levels;
     SearchKernel kernel;
     PlaneSet planes;
-    RC_TRY(pick_kernel(c, call, kernel));
+    RC_TRY(pick_kernel(c, call, rules, kernel));
     RC_TRY(plane_set(c, kernel, levels - 1, planes));       // (every level the call reads exists before its first launch)
     if (kernel == Mx) HIP_TRY(c->mxl[0].reserve((size_t)N));
     HIP_TRY(c->pyr_pos.reserve(sizeof(double) * 2 * (size_t)N));
@@ -490,6 +493,22 @@ extern "C" int mimc3_match_ncc_full_any(mimc3_ctx *c, const double *xyuvav, int3
                                         float *surf)
 {
     return search_host(c, kFullAny, "mimc3_match_ncc_full_any", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
+}
+
+// ... with the surfaces from whichever kernel runs: the class dispatch of mimc3_match_ncc_full_any(mode 0), surf mandatory -- the integer
+// kernels in their surface-storing forms, the float kernel as ever
+extern "C" int mimc3_match_ncc_full_surf_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                             const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                                             float *d_cand, float *d_surf, void *stream)
+{
+    return search_dev(c, dev_call("mimc3_match_ncc_full_surf_dev", d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, 0, d_out, d_cand, d_surf, stream),
+                      kFullSurf);
+}
+
+extern "C" int mimc3_match_ncc_full_surf(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                         int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand, float *surf)
+{
+    return search_host(c, kFullSurf, "mimc3_match_ncc_full_surf", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, 0, out, cand, surf, nullptr, nullptr);
 }
 
 // ... beyond +-15 px: mimc3_match_ncc_full_any in mode 1 with R up to mimc3_wide_max_radius(ocw).  R <= 15 IS that entry (the float

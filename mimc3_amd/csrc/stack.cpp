@@ -1,5 +1,6 @@
 // stack.cpp -- NCC stacking of the C ABI (mimc3_stack_*, include/mimc3_hip.h; stack_kernel.hip): the surfaces of several pairs -- each a
-// mimc3_match_ncc_full_any(mode 1) layer on the pair that is resident, or a caller's array -- accumulated per cell in f64, and the tail
+// mimc3_match_ncc_full_any(mode 1) layer on the pair that is resident (mimc3_stack_add_class: the same cells from the kernel of the
+// pair's class), or a caller's array -- accumulated per cell in f64, and the tail
 // of the exhaustive search over their mean.  The stack is state of the context that the image setters do not touch.  Every entry
 // validates everything before its first launch.  A layer from the resident pair is a search of the exhaustive-search family: checked,
 // selected and launched through that layer's functions (search.cpp).
@@ -106,27 +107,30 @@ static int stack_add_radius(mimc3_ctx *c, int32_t ocw, const std::string &en)
 }
 
 // A layer from the resident pair is a search in mode 1 -- the float kernel, the wide one beyond R 15 -- that returns its surfaces: what
-// an add shares with the search (its arguments, the chip size, the images) is the search's to refuse; the radius is the stack's
+// an add shares with the search (its arguments, the chip size, the images) is the search's to refuse; the radius is the stack's.
+// A class layer (mimc3_stack_add_class) is the same search in mode 0 with the surfaces from whichever kernel runs: the kernel of the
+// pair's class up to R 15 -- the same cells, so the same state -- and the wide kernel beyond, which is mimc3_stack_add itself
 static const SearchRules kLayerRules = {kFloat, false, true, kCandAbsent, false, false, true};
-static int layer_check(mimc3_ctx *c, const char *entry, const double *xyuvav, int32_t N, int32_t ocw, bool host)
+static const SearchRules kClassLayerRules = {kFloat, false, true, kCandAbsent, false, false, true, true};
+static int layer_check(mimc3_ctx *c, const char *entry, const double *xyuvav, int32_t N, int32_t ocw, bool host, bool cls = false)
 {
     SearchCall call{};
-    call.entry = entry; call.host = host; call.d_xyuvav = xyuvav; call.N = N; call.ocw = ocw; call.mode = 1;
-    return search_check(c, call, kLayerRules);
+    call.entry = entry; call.host = host; call.d_xyuvav = xyuvav; call.N = N; call.ocw = ocw; call.mode = cls ? 0 : 1;
+    return search_check(c, call, cls ? kClassLayerRules : kLayerRules);
 }
 // the search of one chunk of a layer at radius R around `d_shift`: records into `rec`, surfaces into `layer`
 static SearchCall layer_call(const char *entry, const double *d_xyuvav, int32_t n, int32_t off_u, int32_t off_v, const int32_t *d_shift,
-                             int32_t ocw, int32_t R, int32_t swap, float *rec, float *layer, hipStream_t s)
+                             int32_t ocw, int32_t R, int32_t swap, float *rec, float *layer, hipStream_t s, bool cls = false)
 {
-    return SearchCall{entry, false, d_xyuvav, 6, 2, n, off_u, off_v, d_shift, ocw, R, 0, swap ? 1 : 0, 1, 0, rec, nullptr, layer, nullptr, nullptr, s};
+    return SearchCall{entry, false, d_xyuvav, 6, 2, n, off_u, off_v, d_shift, ocw, R, 0, swap ? 1 : 0, cls ? 0 : 1, 0, rec, nullptr, layer, nullptr, nullptr, s};
 }
 
 static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
-                         void *stream, const char *entry)
+                         void *stream, const char *entry, bool cls)
 {
     const std::string en(entry);
     // the search's refusals and the stack's own, before anything is allocated or enqueued
-    RC_TRY(layer_check(c, entry, d_xyuvav, N, ocw, false));
+    RC_TRY(layer_check(c, entry, d_xyuvav, N, ocw, false, cls));
     RC_TRY(stack_add_state(c, N, en));
     RC_TRY(stack_add_radius(c, ocw, en));
     auto &k = c->stk;
@@ -137,11 +141,11 @@ static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_
     HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NC));
     HIP_TRY(k.rec.reserve(sizeof(float) * 8 * chunk));
     float *layer = static_cast<float *>(k.layer.p), *rec = static_cast<float *>(k.rec.p);
-    SearchCall call = layer_call(entry, d_xyuvav, 0, off_u, off_v, static_cast<const int32_t *>(k.shift.p), ocw, k.R, swap, rec, layer, s);
+    SearchCall call = layer_call(entry, d_xyuvav, 0, off_u, off_v, static_cast<const int32_t *>(k.shift.p), ocw, k.R, swap, rec, layer, s, cls);
     SearchKernel kernel;
     PlaneSet planes;
-    RC_TRY(pick_kernel(c, call, kernel));
-    RC_TRY(plane_set(c, kernel, 0, planes));                    // (the float kernel's planes: built on the context's stream, which it drains)
+    RC_TRY(pick_kernel(c, call, cls ? kClassLayerRules : kLayerRules, kernel));
+    RC_TRY(plane_set(c, kernel, 0, planes));                    // (planes a first call builds: on the context's stream, which it drains)
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     TimingSuspended whole(c);           // (the events bracket the whole call)
     for (size_t g0 = 0; g0 < (size_t)N; g0 += chunk) {
@@ -162,15 +166,21 @@ static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_
 extern "C" int mimc3_stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
                                    void *stream)
 {
-    return stack_add_dev(c, d_xyuvav, N, off_u, off_v, ocw, swap, stream, "mimc3_stack_add_dev");
+    return stack_add_dev(c, d_xyuvav, N, off_u, off_v, ocw, swap, stream, "mimc3_stack_add_dev", false);
 }
 
-extern "C" int mimc3_stack_add(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap)
+extern "C" int mimc3_stack_add_class_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
+                                         int32_t swap, void *stream)
 {
-    const char *entry = "mimc3_stack_add";
+    return stack_add_dev(c, d_xyuvav, N, off_u, off_v, ocw, swap, stream, "mimc3_stack_add_class_dev", true);
+}
+
+static int stack_add_host(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap, const char *entry,
+                          bool cls)
+{
     const std::string en(entry);
     if (!offset) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
-    RC_TRY(layer_check(c, entry, xyuvav, N, ocw, true));
+    RC_TRY(layer_check(c, entry, xyuvav, N, ocw, true, cls));
     RC_TRY(stack_add_state(c, N, en));
     RC_TRY(stack_add_radius(c, ocw, en));
     // the chip inside the image, the search box inside the planes' zero border (as mimc3_match_ncc_full_any's host entry)
@@ -178,9 +188,19 @@ extern "C" int mimc3_stack_add(mimc3_ctx *c, const double *xyuvav, int32_t N, co
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
     RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
-    RC_TRY(stack_add_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, swap, c->stream, entry));
+    RC_TRY(stack_add_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, swap, c->stream, entry, cls));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+extern "C" int mimc3_stack_add(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap)
+{
+    return stack_add_host(c, xyuvav, N, offset, ocw, swap, "mimc3_stack_add", false);
+}
+
+extern "C" int mimc3_stack_add_class(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap)
+{
+    return stack_add_host(c, xyuvav, N, offset, ocw, swap, "mimc3_stack_add_class", true);
 }
 
 extern "C" int mimc3_stack_add_surfaces_dev(mimc3_ctx *c, const float *d_surf, const uint8_t *d_refused, int32_t N, void *stream)
@@ -320,7 +340,7 @@ static int stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N,
     SearchCall call = layer_call(entry, d_xyuvav, 0, off_u, off_v, nullptr, ocw, layer_R, swap, rec, layer, s);
     SearchKernel kernel;
     PlaneSet planes;
-    RC_TRY(pick_kernel(c, call, kernel));
+    RC_TRY(pick_kernel(c, call, kLayerRules, kernel));
     RC_TRY(plane_set(c, kernel, 0, planes));                    // (as mimc3_stack_add_dev)
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     TimingSuspended whole(c);           // (the events bracket the whole call)
