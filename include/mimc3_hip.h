@@ -84,6 +84,8 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *   9 = the exhaustive search of mimc3_match_ncc_full_any on any other f32 pair (non-integral pixels, NaN or negative nulls), or on any
  *       pair with its mode 1: the float search kernel on the f32 planes, without tables;
  *  10 = the exhaustive search beyond +-15 px (mimc3_match_ncc_wide at R >= 16): the wide float search kernel on the same planes.
+ *  11 = the exhaustive search at any chip half-width 1..80 (mimc3_match_ncc_full_chip with its mode 1, or with an ocw that is not one of
+ *       the six): the run-time-ocw float search kernel on the same planes, the chip walked in bands of chip rows.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -331,6 +333,51 @@ int mimc3_match_ncc_full_surf(mimc3_ctx *ctx, const double *xyuvav, int32_t N, c
 /* Device-resident variant: the contract of mimc3_match_ncc_full_any_dev without `mode`; d_surf is required. */
 int mimc3_match_ncc_full_surf_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                   const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
+                                  float *d_cand, float *d_surf, void *stream);
+
+/* ---- Exhaustive search at ANY chip half-width: 1 <= ocw <= mimc3_full_chip_max_ocw() = 80 -- the reference's other chip sets (7, 10, 15, 11
+ *      and 14, 30, 60, 80; MIMC3_DLC.c:140-149) and everything between.  The arguments of mimc3_match_ncc_full_any, `mode` and `surf`
+ *      included; 1 <= R <= 15, npeaks 0..8, cand NULL iff npeaks == 0.
+ *
+ *   mode 0, ocw one of 7, 15, 16, 30, 32, 40   the call IS mimc3_match_ncc_full_any(mode 0): the same bytes, the same mimc3_ctx_last_path
+ *            (6 / 7 / 8 / 9), and the same refusal of surf where an integer kernel runs.
+ *   mode 0, any other ocw                      the run-time-ocw kernel (match_full_chip_kernel.hip), whatever the pair's class.
+ *   mode 1   that kernel at any ocw in range, the six included (tests and timing).  mimc3_ctx_last_path reports 11 when it ran.
+ *   Any other mode: MIMC3_EINVAL.
+ *   When that kernel runs the definition is that of mimc3_match_ncc_full_any in mode 1, word for word (see there): the zero-bordered f32
+ *   planes whatever the pair's class; both null rules (validity over the chip and over the whole (2R + 2 ocw + 1)^2 box, status -3 above a
+ *   ratio of 0.8, a NaN not counted; inclusion a >= 1e-10 && b >= 1e-10, a NaN excluded); the terms (f32 products widened to f64) and
+ *   sums formed by additions only; the reference's f64 finish, correctly rounded; the first-wins arg-max in k = (su + R)(2R + 1) +
+ *   (sv + R); statuses -2 / -3 / -4, the 3 x 3 fit, ncc_fit, SNR and the Hessian; the local-maximum rule and its rank; surf [N][(2R+1)^2]
+ *   in k order, all NaN at status -3 and for a point of the _dev entry that breaks the bounds (chip outside the image, box outside the
+ *   256-px zero border): that point's record is all NaN and each of its candidate slots is (NaN, NaN, NaN), as in
+ *   mimc3_match_ncc_full_any_dev.
+ *   Term bound.  A sum has m <= 25,921 (161^2) positive terms, so an additions-only f64 sum is within (m - 1) 2^-53 < 2.9e-12
+ *   (relative) of the exact sum in ANY order -- against the 6e-8 of an f32 ulp.
+ *   Order of the additions.  The chip is walked in bands of mimc3_full_chip_band_rows(ocw, R) chip rows (the whole chip where it fits 79 KB
+ *   of LDS with its box; ocw <= 41 at R 15).  A band without an excluded pixel in its chip rows and the box rows they meet runs the clean
+ *   body, any other the masked body; the order is fixed for given (ocw, R, npeaks == 0) and for which body runs in which band.  It never
+ *   depends on N, on the point's place in the grid, or on timing.  No float atomics.
+ *   Exactness.  Every partial sum is an exact integer (times a power of two) while m * (largest f32 product) < 2^53.  That holds for
+ *   8-bit, 12-bit and 16-bit DN (and their x 1/8 filtered forms) at every ocw up to 80: 2^32 * 25,921 < 2^47.  There the surface is the
+ *   reference-order sums' bit for bit, and at one of the six ocw the bytes of mimc3_match_ncc_full_any(mode 1).  For integral-f32 pixels
+ *   near 2^20 at the largest chips (2^40 * 25,921 > 2^53) it no longer holds and the float bound above applies: the bytes of
+ *   mimc3_match_ncc_full_dn are NOT promised there.
+ *   Refusals    those of mimc3_match_ncc_full_any, in its order, with "ocw must be in 1..80" in place of the six-ocw text.  Every older
+ *   entry keeps its six-ocw refusal.
+ *   mimc3_full_chip_band_rows(ocw, R)   the band height the launch uses (chip rows; 2 ocw + 1 = one band); 0 outside ocw 1..80, R 1..15.
+ *   Out of scope: the class kernels (matrix cores, u16, integral f32) at other chip sizes -- an 8-bit pair at ocw 10 pays the float
+ *   kernel; mimc3_match_ncc_wide, the pyramids, forward-backward and mimc3_stack_add / _add_class / _add_scaled at other chip sizes
+ *   (mimc3_stack_add_surfaces takes this entry's surfaces as they are); several GPUs; MIMC3_hip_offsets on float TIFFs; ocw above 80. */
+int mimc3_full_chip_max_ocw(void);
+int mimc3_full_chip_band_rows(int32_t ocw, int32_t R);
+int mimc3_match_ncc_full_chip(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                              const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                              int32_t swap, int32_t mode, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
+                              float *surf /*[N][(2R+1)^2] host, or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_any_dev. */
+int mimc3_match_ncc_full_chip_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                  const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
                                   float *d_cand, float *d_surf, void *stream);
 
 /* ---- Exhaustive search beyond +-15 px: ONE exact pass at full resolution over a search range of up to +-47 px, with candidates from the

@@ -61,6 +61,12 @@ _lib.mimc3_match_ncc_full_any.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c
                                           _vp, _vp]
 _lib.mimc3_match_ncc_full_any_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_int32, _vp, _vp, _vp, _vp]
+_lib.mimc3_match_ncc_full_chip.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p,
+                                           _vp, _vp]
+_lib.mimc3_match_ncc_full_chip_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, _vp, _vp, _vp, _vp]
+_lib.mimc3_full_chip_max_ocw.argtypes = []
+_lib.mimc3_full_chip_band_rows.argtypes = [C.c_int32, C.c_int32]
 _lib.mimc3_match_ncc_full_surf.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
 _lib.mimc3_match_ncc_full_surf_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                _vp, _vp, _vp, _vp]
@@ -254,6 +260,17 @@ def _search_arrays(what, xyuvav, shift, npeaks=0, radius=0, surface=False, fb=Fa
 def wide_max_radius(ocw):
     """The largest radius match_ncc_wide takes at this chip size (mimc3_wide_max_radius); 0 for an ocw it does not take."""
     return int(_lib.mimc3_wide_max_radius(int(ocw)))
+
+
+def full_chip_max_ocw():
+    """The largest chip half-width match_ncc_full_chip takes (mimc3_full_chip_max_ocw): 80."""
+    return int(_lib.mimc3_full_chip_max_ocw())
+
+
+def full_chip_band_rows(ocw, radius):
+    """The chip rows of one band of match_ncc_full_chip's kernel (mimc3_full_chip_band_rows): 2 ocw + 1 where the whole chip is one
+    band; 0 outside 1 <= ocw <= full_chip_max_ocw(), 1 <= radius <= 15."""
+    return int(_lib.mimc3_full_chip_band_rows(int(ocw), int(radius)))
 
 
 def wide_lds_bytes(ocw, radius):
@@ -619,6 +636,22 @@ class Context:
                                                  npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
                "match_ncc_full_any_dev")
 
+    def match_ncc_full_chip(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False, mode=0, surface=False):
+        """The exhaustive search at any chip half-width 1 <= ocw <= full_chip_max_ocw() (mimc3_match_ncc_full_chip): mode 0 at one of the
+        six built chip sizes IS match_ncc_full_any(mode=0); any other ocw, and all of mode 1, runs the run-time-ocw float kernel
+        ("f32g_chip") under match_ncc_full_any's mode-1 definition -> (record, candidates or None[, surfaces]) as there."""
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_chip", xyuvav, shift, npeaks=npeaks, radius=radius, surface=surface)
+        _check(_lib.mimc3_match_ncc_full_chip(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh), ocw, radius, int(npeaks),
+                                              1 if swap else 0, int(mode), out, _ptr(cand), _ptr(surf)), "match_ncc_full_chip")
+        return (out, cand, surf) if surface else (out, cand)
+
+    def match_ncc_full_chip_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, mode=0,
+                                d_surf=0):
+        """Device-pointer variant (enqueue only): as match_ncc_full_any_dev."""
+        _check(_lib.mimc3_match_ncc_full_chip_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                  npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
+               "match_ncc_full_chip_dev")
+
     def match_ncc_full_surf(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False):
         """The exhaustive search with every point's NCC surface from the kernel of the pair's class (mimc3_match_ncc_full_surf): the
         dispatch of match_ncc_full_any(mode=0) -- "u8_mfma_full", "u16_full", "f32i_full" or "f32g_full" -- with the surfaces served by
@@ -837,13 +870,16 @@ class Context:
         _check(_lib.mimc3_stack_info(self._h, C.byref(n), C.byref(r), C.byref(k)), "stack_info")
         return n.value, r.value, k.value
 
-    def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None, any_pair=False):
+    def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None, any_pair=False,
+                        any_ocw=False):
         """The candidates of the exhaustive search over image variants and chip sizes -> dp float32[ndp][N][3], ndp = len(kernels) *
         len(vec_ocw) * npeaks <= 64: for each variant in order (None = the raw pair, else filter_images(kernel)) and each ocw one
         forward match_ncc_full_dn call, its candidates stacked variant-major, then ocw, then peak rank -- what
         calc_mean_var_num_dp_cluster and mimc2_postprocess read.  Every variant is filtered from fresh planes (see filter_images).
-        The pair is left unfiltered.  any_pair: the calls are match_ncc_full_any's (mode 0), so a float pair goes through every variant."""
-        match = self.match_ncc_full_any if any_pair else self.match_ncc_full_dn
+        The pair is left unfiltered.  any_pair: the calls are match_ncc_full_any's (mode 0), so a float pair goes through every variant.
+        any_ocw: the calls are match_ncc_full_chip's (mode 0), so vec_ocw may hold any chip half-width 1 .. full_chip_max_ocw() -- the
+        reference's (7, 10, 15, 11) and (14, 30, 60, 80) -- and any pair."""
+        match = self.match_ncc_full_chip if any_ocw else self.match_ncc_full_any if any_pair else self.match_ncc_full_dn
         kernels = tuple(kernels); vec_ocw = tuple(int(o) for o in vec_ocw); npeaks = int(npeaks)
         ndp = len(kernels) * len(vec_ocw) * npeaks
         if npeaks < 1 or ndp < 1:
@@ -1167,7 +1203,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

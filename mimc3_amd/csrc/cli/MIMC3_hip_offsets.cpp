@@ -31,6 +31,9 @@
 // R = 16 .. mimc3_wide_max_radius(ocw) (47; 39 at ocw 40; with levels = 1 only): one exact pass over the whole range
 //   (mimc3_match_ncc_wide, with fb = 1 mimc3_match_ncc_wide_fb) on 8-bit and 16-bit pairs, raw or filtered; the same files, peaks and
 //   filter as above.  R <= 15 takes exactly the calls of a build without this range and writes the same bytes
+// ocw = 1 .. mimc3_full_chip_max_ocw() (80) other than 7, 15, 16, 30, 32, 40 (with levels = 1, fb = 0 and R <= 15 only): the search through
+//   mimc3_match_ncc_full_chip (mode 0) on 8-bit and 16-bit pairs, raw or filtered; the same files, peaks and filter as above.  One of the
+//   six takes exactly the calls of a build without this range and writes the same bytes
 // Environment: MIMC3_HIP_DEVICE (default 0), MIMC3_CP_SEED (as for MIMC3_hip).
 #include <cstdint>
 #include <cstdio>
@@ -66,6 +69,23 @@ int main(int argc, char *argv[])
     if (peaks != 1 && levels != 1) {
         fprintf(stderr, "peaks > 1 needs levels = 1: candidates on a pyramid's level 0 are not supported\n");
         return 2;
+    }
+    const bool any_chip = mimc3_wide_max_radius(ocw) == 0;     // not one of the six built chip sizes: the run-time-ocw entry
+    if (any_chip) {
+        const int32_t max_ocw = mimc3_full_chip_max_ocw();
+        if (ocw < 1 || ocw > max_ocw) { fprintf(stderr, "ocw must be in 1..%d (mimc3_full_chip_max_ocw)\n", max_ocw); return 2; }
+        if (levels != 1) {
+            fprintf(stderr, "ocw %d needs levels = 1: the coarse-to-fine search takes ocw 7, 15, 16, 30, 32 or 40 only\n", ocw);
+            return 2;
+        }
+        if (fbk != 0) {
+            fprintf(stderr, "ocw %d needs fb = 0: the forward-backward check takes ocw 7, 15, 16, 30, 32 or 40 only\n", ocw);
+            return 2;
+        }
+        if (R > 15) {
+            fprintf(stderr, "ocw %d needs R <= 15: the search beyond +-15 px takes ocw 7, 15, 16, 30, 32 or 40 only\n", ocw);
+            return 2;
+        }
     }
     const bool wide = R > 15;               // beyond +-15 px: the wide entries, whatever the pixel class
     if (wide) {
@@ -138,11 +158,14 @@ int main(int argc, char *argv[])
     std::vector<float> fb(fbk ? 4 * (size_t)(1 + K) * (size_t)N : 0);
     if (fbk) printf("forward-backward consistency of every result\n");
     if (wide) printf("one exact pass over +-%d px\n", R);
+    if (any_chip) printf("chip half-width %d: the run-time-ocw search kernel\n", ocw);
     if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
         (wide ? (fbk ? mimc3_match_ncc_wide_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, rec.data(),
                                                K > 0 ? cand.data() : nullptr, fb.data())
                      : mimc3_match_ncc_wide(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
                                             K > 0 ? cand.data() : nullptr, nullptr))
+         : any_chip ? mimc3_match_ncc_full_chip(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, 0, rec.data(),
+                                                K > 0 ? cand.data() : nullptr, nullptr)
          : fbk ? mimc3_match_ncc_full_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
                                        K > 0 ? cand.data() : nullptr, fb.data())
          : dn16 ? mimc3_match_ncc_full_dn(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),

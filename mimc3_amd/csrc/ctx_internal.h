@@ -177,8 +177,10 @@ struct SearchRules {
     bool layer = false;                 // a stack's layer add: no record of its own, and a radius that the stack refuses in its own words
     bool class_surf = false;            // the surfaces come from whichever kernel runs, an integer class's too (mimc3_match_ncc_full_surf,
                                         // where they are mandatory, and the stack's class layers)
+    bool any_ocw = false;               // every chip half-width 1 .. kFullChipMaxOcw, not the six alone (mimc3_match_ncc_full_chip): what
+                                        // the other kernels are not built for, and all of mode 1, runs the run-time-ocw kernel
 };
-enum SearchKernel { Mx, U16, F32i, F32g, Wide };                      // last_path 6 .. 10
+enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip };                // last_path 6 .. 11
 struct PlaneSet {
     const void *p0, *p1, *sat0, *sat1, *satz0, *satz1;
     int32_t H, W, Wp;

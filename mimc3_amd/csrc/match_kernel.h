@@ -265,6 +265,13 @@ hipError_t launch_match_full_f32g(MatchU8Args a, float *surf, hipStream_t stream
 int wide_max_radius(int ocw);
 int wide_lds_bytes(int ocw, int R);     // the dynamic LDS of a launch at radius R (0 outside 1 .. wide_max_radius(ocw))
 hipError_t launch_match_wide(MatchU8Args a, float *surf, hipStream_t stream);
+// the same search at ANY chip half-width 1 <= a.ocw <= kFullChipMaxOcw (match_full_chip_kernel.hip; mimc3_match_ncc_full_chip): the arguments
+// of launch_match_full_f32g without a.full_peak; a.ocw is a run-time value, the chip is walked in bands of full_chip_band_rows(ocw, R) chip
+// rows (the whole chip where it fits), each band within kChipLdsBudget bytes of dynamic LDS.  One launch
+constexpr int kFullChipMaxOcw = 80;
+constexpr int kChipLdsBudget = 79 * 1024;       // two workgroups per CU (160 KB), their static slots included
+int full_chip_band_rows(int ocw, int R);        // 0 outside 1 <= ocw <= kFullChipMaxOcw, 1 <= R <= 15
+hipError_t launch_match_full_chip(MatchU8Args a, float *surf, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all

@@ -1,5 +1,5 @@
 // search.cpp -- the host layer of the exhaustive-search family of the C ABI (include/mimc3_hip.h): mimc3_match_ncc_full, _full_multi,
-// _full_planes, _full_dn, _full_any, _full_surf, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
+// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
 // _pyramid_any), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
 // (SearchRules); search_check makes every refusal, pick_kernel selects the kernel, plane_set points at the planes it reads (building
 // them on first use), launch_search is the one place that launches.  The stack's layer adds (stack.cpp) go through the same functions.
@@ -40,7 +40,7 @@ static int check_class(mimc3_ctx *c, PairClass widest, const std::string &en)
 
 // Every refusal the family makes from a call's description, in this order (the first one met decides the code):
 //   1. the arguments, MIMC3_EINVAL: a null context, point array or record, N <= 0, candidates that do not go with npeaks, no surfaces
-//      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six; R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw)); levels outside 1..5
+//      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six (any_ocw: outside 1..80); R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw)); levels outside 1..5
 //   2. the context's state, MIMC3_ESTATE: no images; a chip-atlas context
 //   3. the pair's class, MIMC3_EUNSUPPORTED
 //   4. MIMC3_EINVAL again: a coarsest pyramid level smaller than a chip; a mode other than 0 or 1; forward-backward rows without d_fb.
@@ -62,7 +62,9 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
         return fail(MIMC3_EINVAL, en + ": npeaks must be in " + std::to_string(least) + "..8");
     if (mismatch) return fail(MIMC3_EINVAL, en + ": cand goes with npeaks > 0");
     if (early && bad_mode) return fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
-    if (!full_ocw_ok(call.ocw)) return fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
+    if (rules.any_ocw) {
+        if (call.ocw < 1 || call.ocw > kFullChipMaxOcw) return fail(MIMC3_EINVAL, en + ": ocw must be in 1.." + std::to_string(kFullChipMaxOcw));
+    } else if (!full_ocw_ok(call.ocw)) return fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
     if (!rules.layer && (call.R < 1 || call.R > (rules.wide ? wide_max_radius(call.ocw) : 15)))
         return fail(MIMC3_EINVAL, en + (rules.wide ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
     if (rules.pyramid && (call.levels < 1 || call.levels > 5)) return fail(MIMC3_EINVAL, en + ": levels must be in 1..5");
@@ -98,10 +100,12 @@ int search_check_host(const mimc3_ctx *c, const char *entry, const double *xyuva
 // The kernel of a checked call: beyond R 15 the wide float kernel (only the wide entries let such a radius through); in mode 1 the
 // float kernel; else the kernel of the pair's class -- matrix cores on an 8-bit pair, u16 planes on a scaled-integer one, f32 planes
 // with tables on an integral-f32 one, the float kernel on any other.  Only the float kernels serve the surfaces, unless the rules
-// say class_surf: then the integer kernels run their surface-storing forms.
+// say class_surf: then the integer kernels run their surface-storing forms.  Under any_ocw the run-time-ocw float kernel takes mode 1 and
+// every chip size the others are not built for; mode 0 at one of the six takes the class dispatch as before.
 int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel)
 {
     if (call.R > 15) kernel = Wide;
+    else if (rules.any_ocw && (call.mode == 1 || !full_ocw_ok(call.ocw))) kernel = Chip;
     else if (call.mode == 1) kernel = F32g;
     else {
         PairClass cls;
@@ -222,7 +226,7 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl)
 int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const SearchCall &call)
 {
     static const char *const what[] = {"full-search kernel launch", "full-search u16 kernel launch", "full-search f32 kernel launch",
-                                       "full-search general f32 kernel launch", "wide-search kernel launch"};
+                                       "full-search general f32 kernel launch", "wide-search kernel launch", "full-search any-chip kernel launch"};
     hipStream_t s = call.stream;
     MatchU8Args u = u8_args(c, call.d_xyuvav, call.xy_stride, call.xy_col, call.N, call.off_u, call.off_v, call.ocw, call.swap, call.d_out);
     u.H = pl.H; u.W = pl.W; u.Wp = pl.Wp;
@@ -242,6 +246,7 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
     } else if (kernel == U16) e = launch_match_full_u16(u, s);
     else if (kernel == F32i) e = launch_match_full_f32(u, s);
     else if (kernel == F32g) e = launch_match_full_f32g(u, call.d_surf, s);
+    else if (kernel == Chip) e = launch_match_full_chip(u, call.d_surf, s);
     else e = launch_match_wide(u, call.d_surf, s);
     if (e != hipSuccess) return hip_fail(e, what[kernel]);
     c->last_path = 6 + (int)kernel;
@@ -249,12 +254,13 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
     return 0;
 }
 
-// ---- what each public entry accepts ----                widest        mode   wide   candidates      fb     pyramid  layer  class_surf
+// ---- what each public entry accepts ----                widest        mode   wide   candidates      fb     pyramid  layer  class_surf  any_ocw
 static const SearchRules kFull = {kU8, false, false, kCandAbsent};
 static const SearchRules kFullMulti = {kU8, false, false, kCandMandatory};
 static const SearchRules kFullPlanes = {kScaledInt, false, false, kCandOptional};
 static const SearchRules kFullDn = {kIntegralF32, false, false, kCandOptional};
 static const SearchRules kFullAny = {kFloat, true, false, kCandOptional};
+static const SearchRules kFullChip = {kFloat, true, false, kCandOptional, false, false, false, false, true};    // (any_ocw)
 static const SearchRules kFullSurf = {kFloat, false, false, kCandOptional, false, false, false, true};     // (class_surf: surf is mandatory)
 static const SearchRules kWide = {kFloat, false, true, kCandOptional};
 static const SearchRules kFullFb = {kFloat, true, false, kCandOptional, true};
@@ -509,6 +515,26 @@ extern "C" int mimc3_match_ncc_full_surf(mimc3_ctx *c, const double *xyuvav, int
                                          int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand, float *surf)
 {
     return search_host(c, kFullSurf, "mimc3_match_ncc_full_surf", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, 0, out, cand, surf, nullptr, nullptr);
+}
+
+// ... at any chip half-width 1 .. 80: mode 0 at one of the six IS mimc3_match_ncc_full_any(mode 0); every other ocw, and all of mode 1,
+// runs match_full_chip_kernel.hip (run-time ocw, the chip walked in bands) under mimc3_match_ncc_full_any's mode-1 definition
+extern "C" int mimc3_full_chip_max_ocw(void) { return kFullChipMaxOcw; }
+extern "C" int mimc3_full_chip_band_rows(int32_t ocw, int32_t R) { return full_chip_band_rows(ocw, R); }
+
+extern "C" int mimc3_match_ncc_full_chip_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                             const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                             float *d_out, float *d_cand, float *d_surf, void *stream)
+{
+    return search_dev(c, dev_call("mimc3_match_ncc_full_chip_dev", d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, d_surf, stream),
+                      kFullChip);
+}
+
+extern "C" int mimc3_match_ncc_full_chip(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                         int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *out, float *cand,
+                                         float *surf)
+{
+    return search_host(c, kFullChip, "mimc3_match_ncc_full_chip", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
 }
 
 // ... beyond +-15 px: mimc3_match_ncc_full_any in mode 1 with R up to mimc3_wide_max_radius(ocw).  R <= 15 IS that entry (the float
