@@ -86,6 +86,8 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *  10 = the exhaustive search beyond +-15 px (mimc3_match_ncc_wide at R >= 16): the wide float search kernel on the same planes.
  *  11 = the exhaustive search at any chip half-width 1..80 (mimc3_match_ncc_full_chip with its mode 1, or with an ocw that is not one of
  *       the six): the run-time-ocw float search kernel on the same planes, the chip walked in bands of chip rows.
+ *  12 = the exhaustive search of mimc3_match_ncc_full_chip_class on an 8-bit pair, with its mode 1 or with an ocw that is not one of the
+ *       six: the run-time-ocw matrix-core search kernel on the u8 planes and their tables.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -366,8 +368,8 @@ int mimc3_match_ncc_full_surf_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_
  *   Refusals    those of mimc3_match_ncc_full_any, in its order, with "ocw must be in 1..80" in place of the six-ocw text.  Every older
  *   entry keeps its six-ocw refusal.
  *   mimc3_full_chip_band_rows(ocw, R)   the band height the launch uses (chip rows; 2 ocw + 1 = one band); 0 outside ocw 1..80, R 1..15.
- *   Out of scope: the class kernels (matrix cores, u16, integral f32) at other chip sizes -- an 8-bit pair at ocw 10 pays the float
- *   kernel; mimc3_match_ncc_wide, the pyramids, forward-backward and mimc3_stack_add / _add_class / _add_scaled at other chip sizes
+ *   Out of scope: the u16 and integral-f32 class kernels at other chip sizes -- a 16-bit pair at ocw 10 pays the float kernel (an
+ *   8-bit pair has mimc3_match_ncc_full_chip_class below); mimc3_match_ncc_wide, the pyramids, forward-backward and mimc3_stack_add / _add_class / _add_scaled at other chip sizes
  *   (mimc3_stack_add_surfaces takes this entry's surfaces as they are); several GPUs; MIMC3_hip_offsets on float TIFFs; ocw above 80. */
 int mimc3_full_chip_max_ocw(void);
 int mimc3_full_chip_band_rows(int32_t ocw, int32_t R);
@@ -379,6 +381,47 @@ int mimc3_match_ncc_full_chip(mimc3_ctx *ctx, const double *xyuvav, int32_t N, c
 int mimc3_match_ncc_full_chip_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                   const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
                                   float *d_cand, float *d_surf, void *stream);
+
+/* ---- Exhaustive search at any chip half-width with the 8-BIT pair on the matrix cores: the arguments of mimc3_match_ncc_full_chip, `mode`,
+ *      `cand` and `surf` (both optional) included; 1 <= ocw <= 80, 1 <= R <= 15, npeaks 0..8, cand NULL iff npeaks == 0.
+ *
+ *   mode 0, ocw one of 7, 15, 16, 30, 32, 40   the class dispatch of mimc3_match_ncc_full_any(mode 0): the same record and candidates, the same
+ *            mimc3_ctx_last_path (6 / 7 / 8 / 9); surf, when given, is served as mimc3_match_ncc_full_surf serves it (by whichever kernel runs).
+ *   mode 0, any other ocw                      an 8-bit pair runs the run-time-ocw matrix-core kernel (match_full_chip_u8_kernel.hip;
+ *            mimc3_ctx_last_path 12); every other class runs the float kernel of mimc3_match_ncc_full_chip (11), with that entry's bytes.
+ *   mode 1   the matrix-core kernel at every ocw in range, the six included (tests and timing).  8-bit pairs only: any other pair is
+ *            MIMC3_EUNSUPPORTED, where the family refuses a class.
+ *   Any other mode: MIMC3_EINVAL.
+ *   The kernel.  The exhaustive-search half of the matrix-core matcher with ocw as a kernel argument: the Toeplitz-band GEMM on
+ *   v_mfma_i32_16x16x64_i8 over the 32 x 32 cell tile with origin c - R, the window-side box sums on the same pipe, the chip's sums from
+ *   the packed table in sub-boxes of at most 64 x 64 pixels (one query is exact only up to 8,224 pixels: ocw >= 45 would carry between
+ *   its fields on near-saturated data), the guarded fast finish with its exact redo and the tails of the family.  Two forms: the clean one
+ *   runs over all points and flags those that hold a null (pixel 0) in the chip or the search box; the masked one runs behind it over the
+ *   flagged points and takes any null pattern -- the five masked sums are the clean ones minus correlations with the two null indicators,
+ *   whose operands it forms in registers, so it needs no further LDS and is not banded.  Every sum is an exact i32 (the largest true sum
+ *   is 161^2 255^2 < 2^31).
+ *   Promise on an 8-bit pair.  Every sum of mimc3_match_ncc_full_chip's float kernel is the same exact integer there, so record, candidates
+ *   and surface are the bytes of mimc3_match_ncc_full_chip(mode 1) at every ocw 1..80, and at the six also those of
+ *   mimc3_match_ncc_full_surf: finite surface cells bit for bit, a non-finite cell of the same kind (NaN, +Inf or -Inf; payload bits are
+ *   not part of the contract); statuses, the all-NaN surface at -3 and the all-NaN results of a _dev point that breaks the bounds included.
+ *   Dispatch.  mode 0 sends an ocw to the matrix-core kernel where every pass of its timing series was faster than every pass of the float
+ *   kernel's (tools/full_chip_u8_time.py, BASELINE C2; profiles/full_search_chip_u8/): every ocw measured, 7 .. 80, those where 97-99.6 %
+ *   of the points run the masked form included.  No range is kept on the float kernel.
+ *   mimc3_full_chip_class_layout(ocw, out)   the kernel's layout at this ocw: out[0] K chunks of 64 window columns per chip row (1..3),
+ *            out[1] 16-row tiles and out[2] K chunks of the box sums, out[3] dynamic LDS bytes; returns 1, or 0 outside ocw 1..80.
+ *   Refusals    those of mimc3_match_ncc_full_chip, in its order; mode 1 on a pair that is not 8-bit: MIMC3_EUNSUPPORTED.
+ *   mimc3_match_ncc_full_chip and every older entry are unchanged.
+ *   Out of scope: u16 and integral-f32 kernels at other chip sizes; the wide search, the pyramids, forward-backward and mimc3_stack_add* at
+ *   other chip sizes (mimc3_stack_add_surfaces takes this entry's surfaces as they are); several GPUs. */
+int mimc3_full_chip_class_layout(int32_t ocw, int32_t out[4]);
+int mimc3_match_ncc_full_chip_class(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                                    const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                                    int32_t swap, int32_t mode, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
+                                    float *surf /*[N][(2R+1)^2] host, or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_chip_dev. */
+int mimc3_match_ncc_full_chip_class_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                        const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
+                                        float *d_cand, float *d_surf, void *stream);
 
 /* ---- Exhaustive search beyond +-15 px: ONE exact pass at full resolution over a search range of up to +-47 px, with candidates from the
  *      whole range -- for a displacement the a-priori shift misses by more than 15 px, which the entries above return as status -4 or

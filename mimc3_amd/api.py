@@ -65,6 +65,9 @@ _lib.mimc3_match_ncc_full_chip.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.
                                            _vp, _vp]
 _lib.mimc3_match_ncc_full_chip_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                C.c_int32, _vp, _vp, _vp, _vp]
+_lib.mimc3_match_ncc_full_chip_class.argtypes = _lib.mimc3_match_ncc_full_chip.argtypes
+_lib.mimc3_match_ncc_full_chip_class_dev.argtypes = _lib.mimc3_match_ncc_full_chip_dev.argtypes
+_lib.mimc3_full_chip_class_layout.argtypes = [C.c_int32, _vp]
 _lib.mimc3_full_chip_max_ocw.argtypes = []
 _lib.mimc3_full_chip_band_rows.argtypes = [C.c_int32, C.c_int32]
 _lib.mimc3_match_ncc_full_surf.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
@@ -265,6 +268,14 @@ def wide_max_radius(ocw):
 def full_chip_max_ocw():
     """The largest chip half-width match_ncc_full_chip takes (mimc3_full_chip_max_ocw): 80."""
     return int(_lib.mimc3_full_chip_max_ocw())
+
+
+def full_chip_class_layout(ocw):
+    """The layout of match_ncc_full_chip_class's matrix-core kernel at this chip half-width (mimc3_full_chip_class_layout) -> (K chunks of
+    64 window columns per chip row, 16-row tiles of the box sums, K chunks of the box sums, dynamic LDS bytes); None outside
+    1 <= ocw <= full_chip_max_ocw()."""
+    out = (C.c_int32 * 4)()
+    return tuple(int(v) for v in out) if _lib.mimc3_full_chip_class_layout(int(ocw), out) else None
 
 
 def full_chip_band_rows(ocw, radius):
@@ -652,6 +663,24 @@ class Context:
                                                   npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
                "match_ncc_full_chip_dev")
 
+    def match_ncc_full_chip_class(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False, mode=0, surface=False):
+        """match_ncc_full_chip with the 8-bit pair on the matrix cores at every chip size (mimc3_match_ncc_full_chip_class): mode 0 at one of
+        the six built chip sizes is the class dispatch ("u8_mfma_full", "u16_full", "f32i_full", "f32g_full"; the surfaces as
+        match_ncc_full_surf serves them); at any other ocw an 8-bit pair runs the run-time-ocw matrix-core kernel ("u8_mfma_chip") and
+        every other class the float kernel ("f32g_chip"); mode 1 runs the matrix-core kernel at every ocw and takes 8-bit pairs only.
+        On an 8-bit pair the bytes are match_ncc_full_chip(mode=1)'s -> (record, candidates or None[, surfaces]) as there."""
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_chip_class", xyuvav, shift, npeaks=npeaks, radius=radius, surface=surface)
+        _check(_lib.mimc3_match_ncc_full_chip_class(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh), ocw, radius, int(npeaks),
+                                                    1 if swap else 0, int(mode), out, _ptr(cand), _ptr(surf)), "match_ncc_full_chip_class")
+        return (out, cand, surf) if surface else (out, cand)
+
+    def match_ncc_full_chip_class_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, mode=0,
+                                      d_surf=0):
+        """Device-pointer variant (enqueue only): as match_ncc_full_chip_dev."""
+        _check(_lib.mimc3_match_ncc_full_chip_class_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                        npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
+               "match_ncc_full_chip_class_dev")
+
     def match_ncc_full_surf(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False):
         """The exhaustive search with every point's NCC surface from the kernel of the pair's class (mimc3_match_ncc_full_surf): the
         dispatch of match_ncc_full_any(mode=0) -- "u8_mfma_full", "u16_full", "f32i_full" or "f32g_full" -- with the surfaces served by
@@ -878,8 +907,10 @@ class Context:
         calc_mean_var_num_dp_cluster and mimc2_postprocess read.  Every variant is filtered from fresh planes (see filter_images).
         The pair is left unfiltered.  any_pair: the calls are match_ncc_full_any's (mode 0), so a float pair goes through every variant.
         any_ocw: the calls are match_ncc_full_chip's (mode 0), so vec_ocw may hold any chip half-width 1 .. full_chip_max_ocw() -- the
-        reference's (7, 10, 15, 11) and (14, 30, 60, 80) -- and any pair."""
+        reference's (7, 10, 15, 11) and (14, 30, 60, 80) -- and any pair; at a chip size in range other than the six built ones they are
+        match_ncc_full_chip_class's (mode 0: an 8-bit pair on the matrix cores, the same bytes)."""
         match = self.match_ncc_full_chip if any_ocw else self.match_ncc_full_any if any_pair else self.match_ncc_full_dn
+        six = (7, 15, 16, 30, 32, 40)
         kernels = tuple(kernels); vec_ocw = tuple(int(o) for o in vec_ocw); npeaks = int(npeaks)
         ndp = len(kernels) * len(vec_ocw) * npeaks
         if npeaks < 1 or ndp < 1:
@@ -893,7 +924,8 @@ class Context:
                 if k is not None:
                     self.filter_images(k)
                 for ocw in vec_ocw:
-                    blocks.append(match(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
+                    call = self.match_ncc_full_chip_class if any_ocw and ocw not in six and 1 <= ocw <= full_chip_max_ocw() else match
+                    blocks.append(call(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
         finally:
             self.filter_images(None)
         return np.concatenate(blocks, axis=0)
@@ -1203,7 +1235,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip", 12: "u8_mfma_chip"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

@@ -179,8 +179,11 @@ struct SearchRules {
                                         // where they are mandatory, and the stack's class layers)
     bool any_ocw = false;               // every chip half-width 1 .. kFullChipMaxOcw, not the six alone (mimc3_match_ncc_full_chip): what
                                         // the other kernels are not built for, and all of mode 1, runs the run-time-ocw kernel
+    bool chip_class = false;            // with any_ocw (mimc3_match_ncc_full_chip_class): an 8-bit pair at a chip size outside the six, and in all
+                                        // of mode 1 (which takes no other class), runs the run-time-ocw matrix-core kernel; mode 0 at one of the
+                                        // six is the class dispatch; whichever kernel runs serves the surfaces, which stay optional
 };
-enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip };                // last_path 6 .. 11
+enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8 };        // last_path 6 .. 12
 struct PlaneSet {
     const void *p0, *p1, *sat0, *sat1, *satz0, *satz1;
     int32_t H, W, Wp;

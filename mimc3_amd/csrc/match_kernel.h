@@ -272,6 +272,14 @@ constexpr int kFullChipMaxOcw = 80;
 constexpr int kChipLdsBudget = 79 * 1024;       // two workgroups per CU (160 KB), their static slots included
 int full_chip_band_rows(int ocw, int R);        // 0 outside 1 <= ocw <= kFullChipMaxOcw, 1 <= R <= 15
 hipError_t launch_match_full_chip(MatchU8Args a, float *surf, hipStream_t stream);
+// the same search at any chip half-width on the u8 planes of an 8-BIT pair, on the matrix cores (match_full_chip_u8_kernel.hip;
+// mimc3_match_ncc_full_chip_class): a.p0 / a.p1 the u8 planes, a.sat0 / a.sat1 their packed tables, a.mx_flags N class bytes, zero before
+// the call; a.full_shift, a.full_R, a.full_cand / a.full_npeaks, a.full_surf and a.out as launch_match_full_mx takes them, no a.full_peak.
+// forms: bit 0 the clean form over all points (it flags the points that hold a null), bit 1 the masked form over the flagged points --
+// 3 is the search, 1 and 2 are for timing the forms apart.  full_chip_u8_layout: K chunks per chip row, 16-row tiles and K chunks of the
+// box sums, dynamic LDS bytes of a launch at this ocw (false outside 1 .. kFullChipMaxOcw)
+bool full_chip_u8_layout(int ocw, int out[4]);
+hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all

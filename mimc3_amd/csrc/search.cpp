@@ -1,10 +1,11 @@
 // search.cpp -- the host layer of the exhaustive-search family of the C ABI (include/mimc3_hip.h): mimc3_match_ncc_full, _full_multi,
-// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
+// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
 // _pyramid_any), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
 // (SearchRules); search_check makes every refusal, pick_kernel selects the kernel, plane_set points at the planes it reads (building
 // them on first use), launch_search is the one place that launches.  The stack's layer adds (stack.cpp) go through the same functions.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include "ctx_internal.h"
 #include "sat_kernel.h"
 #include "fb_kernel.h"
@@ -42,7 +43,7 @@ static int check_class(mimc3_ctx *c, PairClass widest, const std::string &en)
 //   1. the arguments, MIMC3_EINVAL: a null context, point array or record, N <= 0, candidates that do not go with npeaks, no surfaces
 //      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six (any_ocw: outside 1..80); R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw)); levels outside 1..5
 //   2. the context's state, MIMC3_ESTATE: no images; a chip-atlas context
-//   3. the pair's class, MIMC3_EUNSUPPORTED
+//   3. the pair's class, MIMC3_EUNSUPPORTED (chip_class in mode 1: any pair that is not 8-bit)
 //   4. MIMC3_EINVAL again: a coarsest pyramid level smaller than a chip; a mode other than 0 or 1; forward-backward rows without d_fb.
 //      The _dev entries of the full searches have always made the last two with the arguments, under 1, and keep doing so: without
 //      images they answer a bad mode with MIMC3_EINVAL where their host entries and the pyramids answer MIMC3_ESTATE.
@@ -70,7 +71,7 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
     if (rules.pyramid && (call.levels < 1 || call.levels > 5)) return fail(MIMC3_EINVAL, en + ": levels must be in 1..5");
     if (!c->d_i0 || !c->d_i1) return fail(MIMC3_ESTATE, en + ": images not set");
     if (c->child) return fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    RC_TRY(check_class(c, rules.widest, en));
+    RC_TRY(check_class(c, rules.chip_class && call.mode == 1 ? kU8 : rules.widest, en));
     if (rules.pyramid && std::min(c->H >> (call.levels - 1), c->W >> (call.levels - 1)) < 2 * call.ocw + 1)
         return fail(MIMC3_EINVAL, en + ": level " + std::to_string(call.levels - 1) + " is smaller than a chip");
     if (bad_mode) return fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
@@ -101,10 +102,22 @@ int search_check_host(const mimc3_ctx *c, const char *entry, const double *xyuva
 // float kernel; else the kernel of the pair's class -- matrix cores on an 8-bit pair, u16 planes on a scaled-integer one, f32 planes
 // with tables on an integral-f32 one, the float kernel on any other.  Only the float kernels serve the surfaces, unless the rules
 // say class_surf: then the integer kernels run their surface-storing forms.  Under any_ocw the run-time-ocw float kernel takes mode 1 and
-// every chip size the others are not built for; mode 0 at one of the six takes the class dispatch as before.
+// every chip size the others are not built for; mode 0 at one of the six takes the class dispatch as before.  Under chip_class an 8-bit
+// pair takes the run-time-ocw matrix-core kernel instead, in mode 1 (search_check has refused every other class) and at the chip sizes
+// outside the six that chip_u8_mode0 names.
+// The mode-0 rule follows the series of tools/full_chip_u8_time.py (profiles/full_search_chip_u8/): an ocw goes to the matrix-core kernel
+// where every pass of its series was faster than every pass of the float kernel's -- on BASELINE C2 every ocw measured, 7 .. 80, the
+// 97-99.6 % dirty sizes 60 and 80 included.
+static bool chip_u8_mode0(int32_t ocw) { return ocw >= 1 && ocw <= kFullChipMaxOcw; }
+
 int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel)
 {
     if (call.R > 15) kernel = Wide;
+    else if (rules.chip_class && (call.mode == 1 || !full_ocw_ok(call.ocw))) {
+        PairClass cls = kU8;
+        if (call.mode != 1) RC_TRY(pair_class(c, cls));
+        kernel = cls == kU8 && (call.mode == 1 || chip_u8_mode0(call.ocw)) ? ChipU8 : Chip;
+    }
     else if (rules.any_ocw && (call.mode == 1 || !full_ocw_ok(call.ocw))) kernel = Chip;
     else if (call.mode == 1) kernel = F32g;
     else {
@@ -112,7 +125,7 @@ int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, 
         RC_TRY(pair_class(c, cls));
         kernel = cls == kU8 ? Mx : cls == kScaledInt ? U16 : cls == kIntegralF32 ? F32i : F32g;
     }
-    if (kernel < F32g && call.d_surf && !rules.class_surf)
+    if (kernel < F32g && call.d_surf && !rules.class_surf && !rules.chip_class)
         return fail(MIMC3_EINVAL, std::string(call.entry) + ": only the float kernel serves the surfaces (mode 1, or a pair of no integer class)");
     return 0;
 }
@@ -206,7 +219,7 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl)
     }
     HIP_TRY(hipSetDevice(c->device));
     pl.H = c->H; pl.W = c->W; pl.Wp = c->Wp;
-    if (kernel == Mx) {
+    if (kernel == Mx || kernel == ChipU8) {
         if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
         pl.p0 = c->pl0.p; pl.p1 = c->pl1.p; pl.sat0 = c->sat0.p; pl.sat1 = c->sat1.p;
     } else if (kernel == U16) {
@@ -226,23 +239,32 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl)
 int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const SearchCall &call)
 {
     static const char *const what[] = {"full-search kernel launch", "full-search u16 kernel launch", "full-search f32 kernel launch",
-                                       "full-search general f32 kernel launch", "wide-search kernel launch", "full-search any-chip kernel launch"};
+                                       "full-search general f32 kernel launch", "wide-search kernel launch", "full-search any-chip kernel launch",
+                                       "full-search any-chip u8 kernel launch"};
     hipStream_t s = call.stream;
     MatchU8Args u = u8_args(c, call.d_xyuvav, call.xy_stride, call.xy_col, call.N, call.off_u, call.off_v, call.ocw, call.swap, call.d_out);
     u.H = pl.H; u.W = pl.W; u.Wp = pl.Wp;
     u.full_shift = call.d_shift; u.full_R = call.R; u.full_peak = call.d_peak;
     if (call.d_cand) { u.full_cand = call.d_cand; u.full_npeaks = call.npeaks; }
-    if (kernel < F32g) u.full_surf = call.d_surf;           // (the float kernels take it as an argument of its own)
+    if (kernel < F32g || kernel == ChipU8) u.full_surf = call.d_surf;       // (the float kernels take it as an argument of its own)
     u.p0 = static_cast<const unsigned char *>(pl.p0); u.p1 = static_cast<const unsigned char *>(pl.p1);
     if (pl.sat0) { u.sat0 = pl.sat0; u.sat1 = pl.sat1; u.satz0 = pl.satz0; u.satz1 = pl.satz1; u.sat_ws = sat_pitch(pl.Wp); }
     u.scale0 = pl.scale0; u.scale1 = pl.scale1;
-    if (kernel == Mx) HIP_TRY(c->mxl[0].reserve((size_t)call.N));      // one class byte per point, zero before the launch
+    const bool flags = kernel == Mx || kernel == ChipU8;
+    if (flags) HIP_TRY(c->mxl[0].reserve((size_t)call.N));             // one class byte per point, zero before the launch
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     hipError_t e;
-    if (kernel == Mx) {
+    if (flags) {
         HIP_TRY(hipMemsetAsync(c->mxl[0].p, 0, (size_t)call.N, s));
         u.mx_flags = static_cast<uint8_t *>(c->mxl[0].p);
-        e = launch_match_full_mx(u, s);
+    }
+    if (kernel == Mx) e = launch_match_full_mx(u, s);
+    else if (kernel == ChipU8) {
+        // tuning / timing: MIMC3_CHIP_U8_FORMS = 1 runs the clean form alone (the flagged points get no result), 2 the masked form alone
+        // (over no point: nothing has flagged one); read at every call, so that one process can time the forms apart
+        const char *fe = getenv("MIMC3_CHIP_U8_FORMS");
+        const int forms = fe ? atoi(fe) & 3 : 3;
+        e = launch_match_full_chip_u8(u, forms ? forms : 3, s);
     } else if (kernel == U16) e = launch_match_full_u16(u, s);
     else if (kernel == F32i) e = launch_match_full_f32(u, s);
     else if (kernel == F32g) e = launch_match_full_f32g(u, call.d_surf, s);
@@ -261,6 +283,7 @@ static const SearchRules kFullPlanes = {kScaledInt, false, false, kCandOptional}
 static const SearchRules kFullDn = {kIntegralF32, false, false, kCandOptional};
 static const SearchRules kFullAny = {kFloat, true, false, kCandOptional};
 static const SearchRules kFullChip = {kFloat, true, false, kCandOptional, false, false, false, false, true};    // (any_ocw)
+static const SearchRules kFullChipClass = {kFloat, true, false, kCandOptional, false, false, false, false, true, true};     // (any_ocw, chip_class)
 static const SearchRules kFullSurf = {kFloat, false, false, kCandOptional, false, false, false, true};     // (class_surf: surf is mandatory)
 static const SearchRules kWide = {kFloat, false, true, kCandOptional};
 static const SearchRules kFullFb = {kFloat, true, false, kCandOptional, true};
@@ -535,6 +558,32 @@ extern "C" int mimc3_match_ncc_full_chip(mimc3_ctx *c, const double *xyuvav, int
                                          float *surf)
 {
     return search_host(c, kFullChip, "mimc3_match_ncc_full_chip", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
+}
+
+// ... with the 8-bit pair on the matrix cores at every chip size (match_full_chip_u8_kernel.hip): mode 0 at one of the six is the class
+// dispatch (surfaces as mimc3_match_ncc_full_surf serves them), at any other ocw an 8-bit pair runs the run-time-ocw matrix-core kernel and
+// every other class the float kernel as above; mode 1 runs the matrix-core kernel at every ocw and takes 8-bit pairs only
+extern "C" int mimc3_full_chip_class_layout(int32_t ocw, int32_t out[4])
+{
+    int l[4];
+    if (!out || !full_chip_u8_layout(ocw, l)) return 0;
+    for (int i = 0; i < 4; i++) out[i] = l[i];
+    return 1;
+}
+
+extern "C" int mimc3_match_ncc_full_chip_class_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                                   const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                                   float *d_out, float *d_cand, float *d_surf, void *stream)
+{
+    return search_dev(c, dev_call("mimc3_match_ncc_full_chip_class_dev", d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, d_surf, stream),
+                      kFullChipClass);
+}
+
+extern "C" int mimc3_match_ncc_full_chip_class(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                               int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *out, float *cand,
+                                               float *surf)
+{
+    return search_host(c, kFullChipClass, "mimc3_match_ncc_full_chip_class", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
 }
 
 // ... beyond +-15 px: mimc3_match_ncc_full_any in mode 1 with R up to mimc3_wide_max_radius(ocw).  R <= 15 IS that entry (the float
