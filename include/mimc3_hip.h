@@ -88,6 +88,9 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *       the six): the run-time-ocw float search kernel on the same planes, the chip walked in bands of chip rows.
  *  12 = the exhaustive search of mimc3_match_ncc_full_chip_class on an 8-bit pair, with its mode 1 or with an ocw that is not one of the
  *       six: the run-time-ocw matrix-core search kernel on the u8 planes and their tables.
+ *  13 = the exhaustive search of mimc3_match_ncc_full_chip_planes on a scaled-integer pair (12-bit DN, a filtered 8-bit pair) with an ocw that
+ *       is not one of the six, or on an 8-bit or scaled-integer pair with its mode 1: the run-time-ocw matrix-core search kernel on the u16
+ *       planes (two 6-bit planes per pixel) and their tables.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -411,7 +414,7 @@ int mimc3_match_ncc_full_chip_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_
  *            out[1] 16-row tiles and out[2] K chunks of the box sums, out[3] dynamic LDS bytes; returns 1, or 0 outside ocw 1..80.
  *   Refusals    those of mimc3_match_ncc_full_chip, in its order; mode 1 on a pair that is not 8-bit: MIMC3_EUNSUPPORTED.
  *   mimc3_match_ncc_full_chip and every older entry are unchanged.
- *   Out of scope: u16 and integral-f32 kernels at other chip sizes; the wide search, the pyramids, forward-backward and mimc3_stack_add* at
+ *   Out of scope: u16 (mimc3_match_ncc_full_chip_planes below) and integral-f32 kernels at other chip sizes; the wide search, the pyramids, forward-backward and mimc3_stack_add* at
  *   other chip sizes (mimc3_stack_add_surfaces takes this entry's surfaces as they are); several GPUs. */
 int mimc3_full_chip_class_layout(int32_t ocw, int32_t out[4]);
 int mimc3_match_ncc_full_chip_class(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
@@ -422,6 +425,49 @@ int mimc3_match_ncc_full_chip_class(mimc3_ctx *ctx, const double *xyuvav, int32_
 int mimc3_match_ncc_full_chip_class_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                         const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
                                         float *d_cand, float *d_surf, void *stream);
+
+/* ---- Exhaustive search at any chip half-width with the 8-BIT AND THE SCALED-INTEGER pair on the matrix cores: the arguments of
+ *      mimc3_match_ncc_full_chip_class.  A scaled-integer pair is what mimc3_match_ncc_full_planes takes: pixels q / 2^s with q < 4096 on u16
+ *      planes -- 12-bit DN, and the d/dx, d/dy and Laplacian forms of an 8-bit pair (mimc3_ctx_filter_images).
+ *
+ *   mode 0, ocw one of 7, 15, 16, 30, 32, 40   the class dispatch, exactly as mimc3_match_ncc_full_chip_class(mode 0).
+ *   mode 0, any other ocw                      an 8-bit pair runs the u8 matrix-core kernel (mimc3_ctx_last_path 12); a scaled-integer pair runs
+ *            the run-time-ocw matrix-core kernel on the u16 planes (match_full_chip_u16_kernel.hip; 13) at the chip sizes the measured rule
+ *            below names; every other class runs the float kernel of mimc3_match_ncc_full_chip (11).
+ *   mode 1   the u16 matrix-core kernel at every ocw in range, the six included, on any pair that is 8-bit (q < 256 on its u16 planes) or
+ *            scaled-integer; any other pair is MIMC3_EUNSUPPORTED, where the family refuses a class.
+ *   Any other mode: MIMC3_EINVAL.
+ *   The kernel.  mimc3_match_ncc_full_chip_class's, with every pixel as two 6-bit planes q = 64 h + l: both are non-negative i8 values, so the
+ *   Toeplitz-band GEMM on v_mfma_i32_16x16x64_i8 needs no offset terms, and sum ab = 4096 HH + 64 (SS - HH - LL) + LL from three
+ *   correlations per K chunk (SS that of the plane sums h + l <= 126), put together in 64 bits (the true sum reaches 161^2 4095^2 < 2^39).
+ *   The window-side box sums run on the same pipe (row sums of q as three byte planes, of q^2 -- a u32 -- as four), the chip's sums come from
+ *   the packed u16 table in sub-boxes of at most 64 x 64 pixels (one query is exact only while sum q < 2^25: ocw >= 45 would carry on
+ *   near-saturated data), the null counts from the u32 null table.  Two forms as there: the clean one flags the points that hold a null
+ *   (q == 0) in the chip or the search box, the masked one takes any null pattern behind it, its extra operands formed in registers.
+ *   The cell is finished with the float kernel's own f64 operations on the exact integer sums: from ocw 76 on n sum ab and (sum a)^2 can
+ *   pass 2^53 on near-saturated 12-bit data and round -- identically in both kernels.
+ *   Promise on an 8-bit or scaled-integer pair.  Record, candidates and surface are the bytes of mimc3_match_ncc_full_chip(mode 1) at every
+ *   ocw 1..80; at the six also those of mimc3_match_ncc_full_planes / mimc3_match_ncc_full_surf (finite surface cells bit for bit, a
+ *   non-finite cell of the same kind); on an 8-bit pair those of mimc3_match_ncc_full_chip_class(mode 1).  Statuses, the all-NaN surface at
+ *   -3 and the all-NaN results of a _dev point that breaks the bounds included.
+ *   Dispatch.  mode 0 sends an ocw to the u16 matrix-core kernel where every pass of its timing series was faster than every pass of the
+ *   float kernel's in the same session (tools/full_chip_u16_time.py; profiles/full_search_chip_u16/): every ocw measured, 7 .. 80, on C2 as
+ *   12-bit DN and as its d/dx pair, those where 97-99.6 % of the points run the masked form included.  No range is kept on the float kernel.
+ *   mimc3_full_chip_planes_layout(ocw, out)   the kernel's layout at this ocw: out[0] K chunks of 64 window columns per chip row (1..3),
+ *            out[1] 16-row tiles and out[2] K chunks of the box sums, out[3] dynamic LDS bytes; returns 1, or 0 outside ocw 1..80.
+ *   Refusals    those of mimc3_match_ncc_full_chip_class, in its order; mode 1 on a pair that is neither 8-bit nor scaled-integer:
+ *   MIMC3_EUNSUPPORTED.  mimc3_match_ncc_full_chip, mimc3_match_ncc_full_chip_class and every older entry are unchanged.
+ *   Out of scope: the integral-f32 kernel (16-bit pairs) at other chip sizes; the wide search, the pyramids, forward-backward and
+ *   mimc3_stack_add* at other chip sizes (mimc3_stack_add_surfaces takes this entry's surfaces as they are); several GPUs. */
+int mimc3_full_chip_planes_layout(int32_t ocw, int32_t out[4]);
+int mimc3_match_ncc_full_chip_planes(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                                     const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                                     int32_t swap, int32_t mode, float *out /*[N][8] host*/, float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/,
+                                     float *surf /*[N][(2R+1)^2] host, or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_chip_dev. */
+int mimc3_match_ncc_full_chip_planes_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                         const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *d_out,
+                                         float *d_cand, float *d_surf, void *stream);
 
 /* ---- Exhaustive search beyond +-15 px: ONE exact pass at full resolution over a search range of up to +-47 px, with candidates from the
  *      whole range -- for a displacement the a-priori shift misses by more than 15 px, which the entries above return as status -4 or

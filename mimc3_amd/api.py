@@ -68,6 +68,9 @@ _lib.mimc3_match_ncc_full_chip_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C
 _lib.mimc3_match_ncc_full_chip_class.argtypes = _lib.mimc3_match_ncc_full_chip.argtypes
 _lib.mimc3_match_ncc_full_chip_class_dev.argtypes = _lib.mimc3_match_ncc_full_chip_dev.argtypes
 _lib.mimc3_full_chip_class_layout.argtypes = [C.c_int32, _vp]
+_lib.mimc3_match_ncc_full_chip_planes.argtypes = _lib.mimc3_match_ncc_full_chip.argtypes
+_lib.mimc3_match_ncc_full_chip_planes_dev.argtypes = _lib.mimc3_match_ncc_full_chip_dev.argtypes
+_lib.mimc3_full_chip_planes_layout.argtypes = [C.c_int32, _vp]
 _lib.mimc3_full_chip_max_ocw.argtypes = []
 _lib.mimc3_full_chip_band_rows.argtypes = [C.c_int32, C.c_int32]
 _lib.mimc3_match_ncc_full_surf.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
@@ -276,6 +279,14 @@ def full_chip_class_layout(ocw):
     1 <= ocw <= full_chip_max_ocw()."""
     out = (C.c_int32 * 4)()
     return tuple(int(v) for v in out) if _lib.mimc3_full_chip_class_layout(int(ocw), out) else None
+
+
+def full_chip_planes_layout(ocw):
+    """The layout of match_ncc_full_chip_planes's matrix-core kernel on the u16 planes at this chip half-width
+    (mimc3_full_chip_planes_layout) -> (K chunks of 64 window columns per chip row, 16-row tiles of the box sums, K chunks of the box sums,
+    dynamic LDS bytes); None outside 1 <= ocw <= full_chip_max_ocw()."""
+    out = (C.c_int32 * 4)()
+    return tuple(int(v) for v in out) if _lib.mimc3_full_chip_planes_layout(int(ocw), out) else None
 
 
 def full_chip_band_rows(ocw, radius):
@@ -681,6 +692,25 @@ class Context:
                                                         npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
                "match_ncc_full_chip_class_dev")
 
+    def match_ncc_full_chip_planes(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False, mode=0, surface=False):
+        """match_ncc_full_chip with the 8-bit and the scaled-integer pair (12-bit DN, a filtered 8-bit pair) on the matrix cores at every chip
+        size (mimc3_match_ncc_full_chip_planes): mode 0 at one of the six built chip sizes is the class dispatch, as
+        match_ncc_full_chip_class(mode=0); at any other ocw an 8-bit pair runs "u8_mfma_chip", a scaled-integer pair the run-time-ocw
+        matrix-core kernel on the u16 planes ("u16_mfma_chip") and every other class the float kernel ("f32g_chip"); mode 1 runs
+        "u16_mfma_chip" at every ocw and takes 8-bit and scaled-integer pairs only.  On such a pair the bytes are
+        match_ncc_full_chip(mode=1)'s -> (record, candidates or None[, surfaces]) as there."""
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_full_chip_planes", xyuvav, shift, npeaks=npeaks, radius=radius, surface=surface)
+        _check(_lib.mimc3_match_ncc_full_chip_planes(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh), ocw, radius, int(npeaks),
+                                                     1 if swap else 0, int(mode), out, _ptr(cand), _ptr(surf)), "match_ncc_full_chip_planes")
+        return (out, cand, surf) if surface else (out, cand)
+
+    def match_ncc_full_chip_planes_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, mode=0,
+                                       d_surf=0):
+        """Device-pointer variant (enqueue only): as match_ncc_full_chip_dev."""
+        _check(_lib.mimc3_match_ncc_full_chip_planes_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                         npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
+               "match_ncc_full_chip_planes_dev")
+
     def match_ncc_full_surf(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False):
         """The exhaustive search with every point's NCC surface from the kernel of the pair's class (mimc3_match_ncc_full_surf): the
         dispatch of match_ncc_full_any(mode=0) -- "u8_mfma_full", "u16_full", "f32i_full" or "f32g_full" -- with the surfaces served by
@@ -908,7 +938,7 @@ class Context:
         The pair is left unfiltered.  any_pair: the calls are match_ncc_full_any's (mode 0), so a float pair goes through every variant.
         any_ocw: the calls are match_ncc_full_chip's (mode 0), so vec_ocw may hold any chip half-width 1 .. full_chip_max_ocw() -- the
         reference's (7, 10, 15, 11) and (14, 30, 60, 80) -- and any pair; at a chip size in range other than the six built ones they are
-        match_ncc_full_chip_class's (mode 0: an 8-bit pair on the matrix cores, the same bytes)."""
+        match_ncc_full_chip_planes's (mode 0: an 8-bit or scaled-integer pair on the matrix cores, the same bytes)."""
         match = self.match_ncc_full_chip if any_ocw else self.match_ncc_full_any if any_pair else self.match_ncc_full_dn
         six = (7, 15, 16, 30, 32, 40)
         kernels = tuple(kernels); vec_ocw = tuple(int(o) for o in vec_ocw); npeaks = int(npeaks)
@@ -924,7 +954,7 @@ class Context:
                 if k is not None:
                     self.filter_images(k)
                 for ocw in vec_ocw:
-                    call = self.match_ncc_full_chip_class if any_ocw and ocw not in six and 1 <= ocw <= full_chip_max_ocw() else match
+                    call = self.match_ncc_full_chip_planes if any_ocw and ocw not in six and 1 <= ocw <= full_chip_max_ocw() else match
                     blocks.append(call(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
         finally:
             self.filter_images(None)
@@ -1235,7 +1265,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip", 12: "u8_mfma_chip"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip", 12: "u8_mfma_chip", 13: "u16_mfma_chip"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

@@ -32,7 +32,7 @@
 //   (mimc3_match_ncc_wide, with fb = 1 mimc3_match_ncc_wide_fb) on 8-bit and 16-bit pairs, raw or filtered; the same files, peaks and
 //   filter as above.  R <= 15 takes exactly the calls of a build without this range and writes the same bytes
 // ocw = 1 .. mimc3_full_chip_max_ocw() (80) other than 7, 15, 16, 30, 32, 40 (with levels = 1, fb = 0 and R <= 15 only): the search through
-//   mimc3_match_ncc_full_chip_class (mode 0: an 8-bit pair on the matrix cores, every other on the float kernel; the bytes of
+//   mimc3_match_ncc_full_chip_planes (mode 0: an 8-bit or scaled-integer pair on the matrix cores, every other on the float kernel; the bytes of
 //   mimc3_match_ncc_full_chip) on 8-bit and 16-bit pairs, raw or filtered; the same files, peaks and filter as above.  One of the
 //   six takes exactly the calls of a build without this range and writes the same bytes
 // Environment: MIMC3_HIP_DEVICE (default 0), MIMC3_CP_SEED (as for MIMC3_hip).
@@ -165,8 +165,8 @@ int main(int argc, char *argv[])
                                                K > 0 ? cand.data() : nullptr, fb.data())
                      : mimc3_match_ncc_wide(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
                                             K > 0 ? cand.data() : nullptr, nullptr))
-         : any_chip ? mimc3_match_ncc_full_chip_class(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, 0, rec.data(),
-                                                      K > 0 ? cand.data() : nullptr, nullptr)
+         : any_chip ? mimc3_match_ncc_full_chip_planes(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, 0, rec.data(),
+                                                       K > 0 ? cand.data() : nullptr, nullptr)
          : fbk ? mimc3_match_ncc_full_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),
                                        K > 0 ? cand.data() : nullptr, fb.data())
          : dn16 ? mimc3_match_ncc_full_dn(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),

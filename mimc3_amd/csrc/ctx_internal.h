@@ -182,8 +182,11 @@ struct SearchRules {
     bool chip_class = false;            // with any_ocw (mimc3_match_ncc_full_chip_class): an 8-bit pair at a chip size outside the six, and in all
                                         // of mode 1 (which takes no other class), runs the run-time-ocw matrix-core kernel; mode 0 at one of the
                                         // six is the class dispatch; whichever kernel runs serves the surfaces, which stay optional
+    bool chip_planes = false;           // with chip_class (mimc3_match_ncc_full_chip_planes): a scaled-integer pair at a chip size outside the six, and
+                                        // every 8-bit or scaled-integer pair in mode 1 (which takes no other class), runs the run-time-ocw
+                                        // matrix-core kernel on the u16 planes
 };
-enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8 };        // last_path 6 .. 12
+enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8, ChipU16 };       // last_path 6 .. 13
 struct PlaneSet {
     const void *p0, *p1, *sat0, *sat1, *satz0, *satz1;
     int32_t H, W, Wp;

@@ -280,6 +280,10 @@ hipError_t launch_match_full_chip(MatchU8Args a, float *surf, hipStream_t stream
 // box sums, dynamic LDS bytes of a launch at this ocw (false outside 1 .. kFullChipMaxOcw)
 bool full_chip_u8_layout(int ocw, int out[4]);
 hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t stream);
+// ... and on the u16 planes of a SCALED-INTEGER pair (q < 4096; match_full_chip_u16_kernel.hip; mimc3_match_ncc_full_chip_planes): a.p0 / a.p1
+// the u16 planes, a.sat0 / a.sat1 their packed tables, a.satz0 / a.satz1 their null tables, the rest as above (forms included)
+bool full_chip_u16_layout(int ocw, int out[4]);
+hipError_t launch_match_full_chip_u16(MatchU8Args a, int forms, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all

@@ -1,5 +1,5 @@
 // search.cpp -- the host layer of the exhaustive-search family of the C ABI (include/mimc3_hip.h): mimc3_match_ncc_full, _full_multi,
-// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
+// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _full_chip_planes, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
 // _pyramid_any), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
 // (SearchRules); search_check makes every refusal, pick_kernel selects the kernel, plane_set points at the planes it reads (building
 // them on first use), launch_search is the one place that launches.  The stack's layer adds (stack.cpp) go through the same functions.
@@ -43,7 +43,8 @@ static int check_class(mimc3_ctx *c, PairClass widest, const std::string &en)
 //   1. the arguments, MIMC3_EINVAL: a null context, point array or record, N <= 0, candidates that do not go with npeaks, no surfaces
 //      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six (any_ocw: outside 1..80); R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw)); levels outside 1..5
 //   2. the context's state, MIMC3_ESTATE: no images; a chip-atlas context
-//   3. the pair's class, MIMC3_EUNSUPPORTED (chip_class in mode 1: any pair that is not 8-bit)
+//   3. the pair's class, MIMC3_EUNSUPPORTED (chip_class in mode 1: any pair that is not 8-bit; chip_planes in mode 1: any pair that is
+//      neither 8-bit nor scaled-integer)
 //   4. MIMC3_EINVAL again: a coarsest pyramid level smaller than a chip; a mode other than 0 or 1; forward-backward rows without d_fb.
 //      The _dev entries of the full searches have always made the last two with the arguments, under 1, and keep doing so: without
 //      images they answer a bad mode with MIMC3_EINVAL where their host entries and the pyramids answer MIMC3_ESTATE.
@@ -71,7 +72,7 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
     if (rules.pyramid && (call.levels < 1 || call.levels > 5)) return fail(MIMC3_EINVAL, en + ": levels must be in 1..5");
     if (!c->d_i0 || !c->d_i1) return fail(MIMC3_ESTATE, en + ": images not set");
     if (c->child) return fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
-    RC_TRY(check_class(c, rules.chip_class && call.mode == 1 ? kU8 : rules.widest, en));
+    RC_TRY(check_class(c, call.mode == 1 && rules.chip_planes ? kScaledInt : call.mode == 1 && rules.chip_class ? kU8 : rules.widest, en));
     if (rules.pyramid && std::min(c->H >> (call.levels - 1), c->W >> (call.levels - 1)) < 2 * call.ocw + 1)
         return fail(MIMC3_EINVAL, en + ": level " + std::to_string(call.levels - 1) + " is smaller than a chip");
     if (bad_mode) return fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
@@ -104,19 +105,30 @@ int search_check_host(const mimc3_ctx *c, const char *entry, const double *xyuva
 // say class_surf: then the integer kernels run their surface-storing forms.  Under any_ocw the run-time-ocw float kernel takes mode 1 and
 // every chip size the others are not built for; mode 0 at one of the six takes the class dispatch as before.  Under chip_class an 8-bit
 // pair takes the run-time-ocw matrix-core kernel instead, in mode 1 (search_check has refused every other class) and at the chip sizes
-// outside the six that chip_u8_mode0 names.
+// outside the six that chip_mode0 names.
 // The mode-0 rule follows the series of tools/full_chip_u8_time.py (profiles/full_search_chip_u8/): an ocw goes to the matrix-core kernel
 // where every pass of its series was faster than every pass of the float kernel's -- on BASELINE C2 every ocw measured, 7 .. 80, the
 // 97-99.6 % dirty sizes 60 and 80 included.
-static bool chip_u8_mode0(int32_t ocw) { return ocw >= 1 && ocw <= kFullChipMaxOcw; }
+// Under chip_planes (mimc3_match_ncc_full_chip_planes) a scaled-integer pair takes the run-time-ocw matrix-core kernel on the u16 planes as
+// well: in mode 1 at every ocw (an 8-bit pair included: q < 256 on its u16 planes; search_check has refused every wider class) and in
+// mode 0 at the chip sizes outside the six that chip_mode0 names; an 8-bit pair in mode 0 keeps the u8 kernel.
+// The same rule on the series of tools/full_chip_u16_time.py (profiles/full_search_chip_u16/): on BASELINE C2 as 12-bit DN and as its d/dx
+// pair every pass of the matrix-core kernel was faster than every pass of the float kernel at every ocw measured, 7 .. 80 (3.55 ms against
+// 16.9 at ocw 7, 350 ms against 2414 at ocw 80, where 99.6 % of the points run the masked form): no range stays on the float kernel.
+// One predicate for both kernels (ChipU8, ChipU16): the measured ranges happen to be the same, every ocw in range; a range that a later
+// series hands back to the float kernel is cut out here, per kernel.
+static bool chip_mode0(SearchKernel, int32_t ocw) { return ocw >= 1 && ocw <= kFullChipMaxOcw; }
 
 int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel)
 {
     if (call.R > 15) kernel = Wide;
     else if (rules.chip_class && (call.mode == 1 || !full_ocw_ok(call.ocw))) {
-        PairClass cls = kU8;
+        // (mode 1: the entry's own matrix-core kernel on whatever search_check let through; mode 0: the kernel of the pair's class)
+        PairClass cls = rules.chip_planes ? kScaledInt : kU8;
         if (call.mode != 1) RC_TRY(pair_class(c, cls));
-        kernel = cls == kU8 && (call.mode == 1 || chip_u8_mode0(call.ocw)) ? ChipU8 : Chip;
+        const bool u16 = rules.chip_planes && (call.mode == 1 || cls == kScaledInt);
+        kernel = u16 ? (call.mode == 1 || chip_mode0(ChipU16, call.ocw) ? ChipU16 : Chip)
+                     : cls == kU8 && (call.mode == 1 || chip_mode0(ChipU8, call.ocw)) ? ChipU8 : Chip;
     }
     else if (rules.any_ocw && (call.mode == 1 || !full_ocw_ok(call.ocw))) kernel = Chip;
     else if (call.mode == 1) kernel = F32g;
@@ -222,7 +234,7 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl)
     if (kernel == Mx || kernel == ChipU8) {
         if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
         pl.p0 = c->pl0.p; pl.p1 = c->pl1.p; pl.sat0 = c->sat0.p; pl.sat1 = c->sat1.p;
-    } else if (kernel == U16) {
+    } else if (kernel == U16 || kernel == ChipU16) {
         if (!c->hpl_valid || !c->sat_u16_ok) RC_TRY(build_u16(c, true));
         pl.p0 = c->hpl0.p; pl.p1 = c->hpl1.p; pl.sat0 = c->hsat0.p; pl.sat1 = c->hsat1.p; pl.satz0 = c->hsz0.p; pl.satz1 = c->hsz1.p;
     } else {
@@ -240,17 +252,17 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
 {
     static const char *const what[] = {"full-search kernel launch", "full-search u16 kernel launch", "full-search f32 kernel launch",
                                        "full-search general f32 kernel launch", "wide-search kernel launch", "full-search any-chip kernel launch",
-                                       "full-search any-chip u8 kernel launch"};
+                                       "full-search any-chip u8 kernel launch", "full-search any-chip u16 kernel launch"};
     hipStream_t s = call.stream;
     MatchU8Args u = u8_args(c, call.d_xyuvav, call.xy_stride, call.xy_col, call.N, call.off_u, call.off_v, call.ocw, call.swap, call.d_out);
     u.H = pl.H; u.W = pl.W; u.Wp = pl.Wp;
     u.full_shift = call.d_shift; u.full_R = call.R; u.full_peak = call.d_peak;
     if (call.d_cand) { u.full_cand = call.d_cand; u.full_npeaks = call.npeaks; }
-    if (kernel < F32g || kernel == ChipU8) u.full_surf = call.d_surf;       // (the float kernels take it as an argument of its own)
+    if (kernel < F32g || kernel == ChipU8 || kernel == ChipU16) u.full_surf = call.d_surf;       // (the float kernels take it as an argument of its own)
     u.p0 = static_cast<const unsigned char *>(pl.p0); u.p1 = static_cast<const unsigned char *>(pl.p1);
     if (pl.sat0) { u.sat0 = pl.sat0; u.sat1 = pl.sat1; u.satz0 = pl.satz0; u.satz1 = pl.satz1; u.sat_ws = sat_pitch(pl.Wp); }
     u.scale0 = pl.scale0; u.scale1 = pl.scale1;
-    const bool flags = kernel == Mx || kernel == ChipU8;
+    const bool flags = kernel == Mx || kernel == ChipU8 || kernel == ChipU16;
     if (flags) HIP_TRY(c->mxl[0].reserve((size_t)call.N));             // one class byte per point, zero before the launch
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     hipError_t e;
@@ -265,6 +277,12 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
         const char *fe = getenv("MIMC3_CHIP_U8_FORMS");
         const int forms = fe ? atoi(fe) & 3 : 3;
         e = launch_match_full_chip_u8(u, forms ? forms : 3, s);
+    } else if (kernel == ChipU16) {
+        // (MIMC3_CHIP_U16_FORMS: the same measurement-only switch for this kernel's two forms -- tools/full_chip_u16_time.py times the clean
+        //  form with it; DESIGN 4.1r names it.  With 1 the flagged points get no result: never set it around a real search)
+        const char *fe = getenv("MIMC3_CHIP_U16_FORMS");
+        const int forms = fe ? atoi(fe) & 3 : 3;
+        e = launch_match_full_chip_u16(u, forms ? forms : 3, s);
     } else if (kernel == U16) e = launch_match_full_u16(u, s);
     else if (kernel == F32i) e = launch_match_full_f32(u, s);
     else if (kernel == F32g) e = launch_match_full_f32g(u, call.d_surf, s);
@@ -284,6 +302,7 @@ static const SearchRules kFullDn = {kIntegralF32, false, false, kCandOptional};
 static const SearchRules kFullAny = {kFloat, true, false, kCandOptional};
 static const SearchRules kFullChip = {kFloat, true, false, kCandOptional, false, false, false, false, true};    // (any_ocw)
 static const SearchRules kFullChipClass = {kFloat, true, false, kCandOptional, false, false, false, false, true, true};     // (any_ocw, chip_class)
+static const SearchRules kFullChipPlanes = {kFloat, true, false, kCandOptional, false, false, false, false, true, true, true};    // (..., chip_planes)
 static const SearchRules kFullSurf = {kFloat, false, false, kCandOptional, false, false, false, true};     // (class_surf: surf is mandatory)
 static const SearchRules kWide = {kFloat, false, true, kCandOptional};
 static const SearchRules kFullFb = {kFloat, true, false, kCandOptional, true};
@@ -584,6 +603,32 @@ extern "C" int mimc3_match_ncc_full_chip_class(mimc3_ctx *c, const double *xyuva
                                                float *surf)
 {
     return search_host(c, kFullChipClass, "mimc3_match_ncc_full_chip_class", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
+}
+
+// ... and with the scaled-integer pair on the matrix cores too (match_full_chip_u16_kernel.hip: q = 64 h + l, two 6-bit planes): mode 0 at one
+// of the six is the class dispatch; at any other ocw an 8-bit pair runs the u8 matrix-core kernel, a scaled-integer pair the u16 one, every
+// other class the float kernel; mode 1 runs the u16 matrix-core kernel at every ocw and takes 8-bit and scaled-integer pairs only
+extern "C" int mimc3_full_chip_planes_layout(int32_t ocw, int32_t out[4])
+{
+    int l[4];
+    if (!out || !full_chip_u16_layout(ocw, l)) return 0;
+    for (int i = 0; i < 4; i++) out[i] = l[i];
+    return 1;
+}
+
+extern "C" int mimc3_match_ncc_full_chip_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                                    const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                                    float *d_out, float *d_cand, float *d_surf, void *stream)
+{
+    return search_dev(c, dev_call("mimc3_match_ncc_full_chip_planes_dev", d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, d_surf, stream),
+                      kFullChipPlanes);
+}
+
+extern "C" int mimc3_match_ncc_full_chip_planes(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                                int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *out, float *cand,
+                                                float *surf)
+{
+    return search_host(c, kFullChipPlanes, "mimc3_match_ncc_full_chip_planes", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
 }
 
 // ... beyond +-15 px: mimc3_match_ncc_full_any in mode 1 with R up to mimc3_wide_max_radius(ocw).  R <= 15 IS that entry (the float
