@@ -91,6 +91,8 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *  13 = the exhaustive search of mimc3_match_ncc_full_chip_planes on a scaled-integer pair (12-bit DN, a filtered 8-bit pair) with an ocw that
  *       is not one of the six, or on an 8-bit or scaled-integer pair with its mode 1: the run-time-ocw matrix-core search kernel on the u16
  *       planes (two 6-bit planes per pixel) and their tables.
+ *  14 = the exhaustive search beyond +-15 px of mimc3_match_ncc_wide_class on an 8-bit pair (R >= 16): the matrix-core wide search kernel on
+ *       the u8 planes and their tables, at any chip half-width 1..80.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -504,6 +506,51 @@ int mimc3_match_ncc_wide(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const 
 int mimc3_match_ncc_wide_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                              const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *d_out,
                              float *d_cand, float *d_surf, void *stream);
+
+/* ---- The exhaustive search beyond +-15 px with the 8-BIT pair on the matrix cores, at ANY chip half-width 1 <= ocw <= 80
+ *      (match_wide_u8_kernel.hip): mimc3_match_ncc_wide pays 40 to 400 times the R-15 price of an 8-bit pair (a float kernel, f64 adds) and
+ *      takes the six built chip sizes only.
+ *   The arguments are those of mimc3_match_ncc_full_chip_class, with 1 <= R <= mimc3_wide_class_max_radius(ocw) (47 for 1 <= ocw <= 80).
+ *   R <= 15, any mode   mimc3_match_ncc_full_chip_class with the same mode: its kernel, its bytes, its last_path.
+ *   R >= 16, mode 0     an 8-bit pair runs the matrix-core wide kernel, mimc3_ctx_last_path 14 ("u8_mfma_wide"), at every (ocw, R) named by
+ *                       the measured rule below and at every (ocw, R) mimc3_match_ncc_wide does not take; any other (ocw, R), and every
+ *                       pair of another class, runs mimc3_match_ncc_wide's kernel where that entry takes (ocw, R): its bytes, last_path
+ *                       10.  A pair that is not 8-bit at any other (ocw, R): MIMC3_EUNSUPPORTED, at the step where the family refuses a
+ *                       class.
+ *   R >= 16, mode 1     the matrix-core wide kernel at every (ocw, R) in range, 8-bit pairs only; any other pair: MIMC3_EUNSUPPORTED.
+ *   any other mode      MIMC3_EINVAL.  The order of refusals is that of mimc3_match_ncc_full_chip_class.
+ *   The kernel.  mimc3_match_ncc_full_chip_class's, over a grid of ceil(S / 32)^2 tiles of 32 x 32 cells, S = 2R + 1 <= 95: per point the
+ *   header, the chip's sums from the packed table in 64 x 64 sub-boxes, the null count of the whole (2R + 2 ocw + 1)^2 box, status -3 above
+ *   0.8, the chip plane staged once; per tile the window restaged, the Toeplitz-band GEMM on v_mfma_i32_16x16x64_i8, the box sums against
+ *   bands of ones, the masked corrections, sum ab in f64, the guarded finish, into a surface at pitch 96 with LDS bytes of its own; cells
+ *   beyond S are computed and dropped.  Then mimc3_match_ncc_wide's tails, unmodified.  A clean form over all points flags those with a null
+ *   in the chip or the box; a masked form runs behind it over the flagged points.
+ *   Promise on an 8-bit pair: record, candidates and surface are the bytes of the definition mimc3_match_ncc_wide states
+ *   (mimc3_match_ncc_full_any in mode 1, word for word) -- at the six chip sizes within mimc3_wide_max_radius those of mimc3_match_ncc_wide
+ *   itself (finite surface cells bit for bit, a non-finite cell of the same kind); statuses -2 / -3 / -4 and the all-NaN surface at -3 agree.
+ *   mimc3_wide_class_layout(ocw, R, out)   the kernel's layout: out[0] K chunks of 64 window columns per chip row (1..3), out[1] cell tiles
+ *              per axis (2..3), out[2] threads per workgroup (128), out[3] dynamic LDS bytes, from the constexpr layout the launch uses;
+ *              returns 1, or 0 outside 1 <= ocw <= 80, 16 <= R <= 47.
+ *   The mode-0 rule: an (ocw, R) goes to the matrix-core kernel where every pass of its series was faster than every pass of the float
+ *   wide kernel's in the same session (tools/wide_u8_time.py, profiles/full_search_wide_u8/).  Measured on C2 (189,054 points, one MI355X): true in all 18
+ *   configurations the float kernel takes -- ocw 16 at R 16 / 23 / 31 / 32 / 47: 9.73 / 11.01 / 15.76 / 27.28 / 44.61 ms against 103.1 / 196.8 / 387.2 / 464.7 / 1296.8; ocw 7 at R 16 / 47: 5.09 / 29.75 against 19.87 / 276.6;
+ *   ocw 40 at R 16 / 39: 51.25 / 221.2 against 1648.0 / 6065.8 -- and in a second run at ocw 15, 30 and 32 (R 16 and 47: 9.4 to 25.8 times faster), so every (ocw, R) that mimc3_match_ncc_wide
+ *   takes goes to the matrix-core kernel; ocw 80 at
+ *   R 16 / 47, where it is the only kernel: 552.5 / 1411.2 ms.
+ *   MIMC3_hip_offsets calls this entry in mode 0 at levels = 1, fb = 0, 16 <= R <= mimc3_wide_max_radius(ocw): the same files, an 8-bit raw
+ *   pair on the matrix cores.
+ *   Out of scope: 12-bit pairs beyond R 15 on the matrix cores; mimc3_stack_add / _add_class, mimc3_match_ncc_wide_fb and
+ *   Context.full_candidates through this kernel; an ocw outside the six on the command line at R > 15; the pyramids; several GPUs. */
+int mimc3_wide_class_max_radius(int32_t ocw);
+int mimc3_wide_class_layout(int32_t ocw, int32_t R, int32_t out[4]);
+int mimc3_match_ncc_wide_class(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                               const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                               int32_t swap, int32_t mode, float *out /*[N][8] host*/,
+                               float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/, float *surf /*[N][(2R+1)^2] host, or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_chip_class_dev. */
+int mimc3_match_ncc_wide_class_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                   const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                   float *d_out, float *d_cand, float *d_surf, void *stream);
 
 /* ---- Forward-backward consistency of the exhaustive search: is a peak RECIPROCAL -- does matching back from where a point landed return
  *      to where it started?  (The back-matching test AMPCOR and IMCORR users apply after the run; the record's quality columns all

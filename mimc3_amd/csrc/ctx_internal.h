@@ -185,8 +185,11 @@ struct SearchRules {
     bool chip_planes = false;           // with chip_class (mimc3_match_ncc_full_chip_planes): a scaled-integer pair at a chip size outside the six, and
                                         // every 8-bit or scaled-integer pair in mode 1 (which takes no other class), runs the run-time-ocw
                                         // matrix-core kernel on the u16 planes
+    bool wide_class = false;            // with chip_class (mimc3_match_ncc_wide_class): the radius limit is wide_u8_max_radius(ocw); beyond R 15 an
+                                        // 8-bit pair runs the matrix-core wide kernel (mode 1 always, mode 0 where wide_mode0 names it or the
+                                        // float wide kernel does not take the call), any other class the float wide kernel where that takes it
 };
-enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8, ChipU16 };       // last_path 6 .. 13
+enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8, ChipU16, WideU8 };       // last_path 6 .. 14
 struct PlaneSet {
     const void *p0, *p1, *sat0, *sat1, *satz0, *satz1;
     int32_t H, W, Wp;

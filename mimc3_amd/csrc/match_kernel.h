@@ -284,7 +284,15 @@ hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t strea
 // the u16 planes, a.sat0 / a.sat1 their packed tables, a.satz0 / a.satz1 their null tables, the rest as above (forms included)
 bool full_chip_u16_layout(int ocw, int out[4]);
 hipError_t launch_match_full_chip_u16(MatchU8Args a, int forms, hipStream_t stream);
-static_assert(sizeof(MatchU8Args) == 344, "MatchU8Args: the unions over its slots keep the struct's size");
+// the search beyond +-15 px on the u8 planes of an 8-BIT pair at any chip half-width, on the matrix cores (match_wide_u8_kernel.hip;
+// mimc3_match_ncc_wide_class): the arguments and forms of launch_match_full_chip_u8 with 16 <= a.full_R <= 47 -- that kernel over a grid of
+// 32 x 32 cell tiles, the surface at pitch 96 in LDS bytes of its own, the tails of match_full_tail.h and match_wide_tail.h.
+// wide_u8_max_radius: 47 for 1 <= ocw <= kFullChipMaxOcw, else 0.  wide_u8_layout_query: K chunks per chip row, cell tiles per axis, threads
+// per workgroup, dynamic LDS bytes of a launch at (ocw, R) (false outside 1 .. kFullChipMaxOcw x 16 .. 47), from the constexpr layout the launch uses
+int wide_u8_max_radius(int ocw);
+bool wide_u8_layout_query(int ocw, int R, int out[4]);
+hipError_t launch_match_wide_u8(MatchU8Args a, int forms, hipStream_t stream);
+static_assert(sizeof(MatchU8Args) == 344,"MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all
 // zero; Hd = Hs >> 1, Wd = Ws >> 1 (the destination plane pre-zeroed, border pad in both)

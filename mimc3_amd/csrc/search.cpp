@@ -1,5 +1,5 @@
 // search.cpp -- the host layer of the exhaustive-search family of the C ABI (include/mimc3_hip.h): mimc3_match_ncc_full, _full_multi,
-// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _full_chip_planes, _wide, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
+// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _full_chip_planes, _wide, _wide_class, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
 // _pyramid_any), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
 // (SearchRules); search_check makes every refusal, pick_kernel selects the kernel, plane_set points at the planes it reads (building
 // them on first use), launch_search is the one place that launches.  The stack's layer adds (stack.cpp) go through the same functions.
@@ -13,6 +13,8 @@
 namespace mimc3 {
 
 bool full_ocw_ok(int32_t ocw) { return ocw == 7 || ocw == 15 || ocw == 16 || ocw == 30 || ocw == 32 || ocw == 40; }
+// what the float wide kernel (mimc3_match_ncc_wide beyond R 15) takes
+static bool wide_float_takes(int32_t ocw, int32_t R) { return full_ocw_ok(ocw) && R <= wide_max_radius(ocw); }
 
 // the pair's class; that of a pair which is neither 8-bit nor scaled-integer needs its f32 planes: built here on first use (drains the stream)
 static int pair_class(mimc3_ctx *c, PairClass &cls)
@@ -41,10 +43,11 @@ static int check_class(mimc3_ctx *c, PairClass widest, const std::string &en)
 
 // Every refusal the family makes from a call's description, in this order (the first one met decides the code):
 //   1. the arguments, MIMC3_EINVAL: a null context, point array or record, N <= 0, candidates that do not go with npeaks, no surfaces
-//      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six (any_ocw: outside 1..80); R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw)); levels outside 1..5
+//      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six (any_ocw: outside 1..80); R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw); wide_class: 1..mimc3_wide_class_max_radius(ocw)); levels outside 1..5
 //   2. the context's state, MIMC3_ESTATE: no images; a chip-atlas context
 //   3. the pair's class, MIMC3_EUNSUPPORTED (chip_class in mode 1: any pair that is not 8-bit; chip_planes in mode 1: any pair that is
-//      neither 8-bit nor scaled-integer)
+//      neither 8-bit nor scaled-integer; wide_class beyond R 15 in mode 0: a pair that is not 8-bit at an (ocw, R) the float wide kernel does
+//      not take)
 //   4. MIMC3_EINVAL again: a coarsest pyramid level smaller than a chip; a mode other than 0 or 1; forward-backward rows without d_fb.
 //      The _dev entries of the full searches have always made the last two with the arguments, under 1, and keep doing so: without
 //      images they answer a bad mode with MIMC3_EINVAL where their host entries and the pyramids answer MIMC3_ESTATE.
@@ -67,12 +70,16 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
     if (rules.any_ocw) {
         if (call.ocw < 1 || call.ocw > kFullChipMaxOcw) return fail(MIMC3_EINVAL, en + ": ocw must be in 1.." + std::to_string(kFullChipMaxOcw));
     } else if (!full_ocw_ok(call.ocw)) return fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (!rules.layer && (call.R < 1 || call.R > (rules.wide ? wide_max_radius(call.ocw) : 15)))
-        return fail(MIMC3_EINVAL, en + (rules.wide ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
+    if (!rules.layer && (call.R < 1 || call.R > (rules.wide_class ? wide_u8_max_radius(call.ocw) : rules.wide ? wide_max_radius(call.ocw) : 15)))
+        return fail(MIMC3_EINVAL, en + (rules.wide_class ? ": R must be in 1..mimc3_wide_class_max_radius(ocw)"
+                                        : rules.wide     ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
     if (rules.pyramid && (call.levels < 1 || call.levels > 5)) return fail(MIMC3_EINVAL, en + ": levels must be in 1..5");
     if (!c->d_i0 || !c->d_i1) return fail(MIMC3_ESTATE, en + ": images not set");
     if (c->child) return fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
     RC_TRY(check_class(c, call.mode == 1 && rules.chip_planes ? kScaledInt : call.mode == 1 && rules.chip_class ? kU8 : rules.widest, en));
+    // (wide_class beyond R 15, mode 0: a pair that is not 8-bit has the float wide kernel alone, which takes the six chip sizes up to its own radius)
+    if (rules.wide_class && call.R > 15 && call.mode == 0 && !c->u8_ok && !wide_float_takes(call.ocw, call.R))
+        return fail(MIMC3_EUNSUPPORTED, en + ": beyond R 15 a pair that is not 8-bit needs ocw one of 7, 15, 16, 30, 32, 40 and R <= mimc3_wide_max_radius(ocw)");
     if (rules.pyramid && std::min(c->H >> (call.levels - 1), c->W >> (call.levels - 1)) < 2 * call.ocw + 1)
         return fail(MIMC3_EINVAL, en + ": level " + std::to_string(call.levels - 1) + " is smaller than a chip");
     if (bad_mode) return fail(MIMC3_EINVAL, en + ": mode must be 0 or 1");
@@ -118,10 +125,20 @@ int search_check_host(const mimc3_ctx *c, const char *entry, const double *xyuva
 // One predicate for both kernels (ChipU8, ChipU16): the measured ranges happen to be the same, every ocw in range; a range that a later
 // series hands back to the float kernel is cut out here, per kernel.
 static bool chip_mode0(SearchKernel, int32_t ocw) { return ocw >= 1 && ocw <= kFullChipMaxOcw; }
+// The same rule beyond R 15 (mimc3_match_ncc_wide_class, mode 0, an 8-bit pair) on the series of tools/wide_u8_time.py
+// (profiles/full_search_wide_u8/): an (ocw, R) the float wide kernel takes goes to the matrix-core wide kernel where every pass of its
+// series was faster than every pass of the float kernel's in the same session -- on BASELINE C2
+// every configuration measured (ocw 7, 16, 40; R 16 .. 47; npeaks 0 and 4: 3.4 to 32.2 times faster; ocw 15, 30, 32 at R 16 and 47 in a second run: 9.4 to 25.8), so no (ocw, R) stays on the float kernel
+static bool wide_mode0(int32_t ocw, int32_t R) { return ocw >= 1 && ocw <= kFullChipMaxOcw && R >= 16 && R <= wide_u8_max_radius(ocw); }
 
 int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel)
 {
-    if (call.R > 15) kernel = Wide;
+    if (call.R > 15 && rules.wide_class) {
+        // (mode 1: search_check has refused every pair that is not 8-bit; mode 0: every pair the float wide kernel cannot take)
+        const bool u8 = call.mode == 1 || (c->u8_ok && (wide_mode0(call.ocw, call.R) || !wide_float_takes(call.ocw, call.R)));
+        kernel = u8 ? WideU8 : Wide;
+    }
+    else if (call.R > 15) kernel = Wide;
     else if (rules.chip_class && (call.mode == 1 || !full_ocw_ok(call.ocw))) {
         // (mode 1: the entry's own matrix-core kernel on whatever search_check let through; mode 0: the kernel of the pair's class)
         PairClass cls = rules.chip_planes ? kScaledInt : kU8;
@@ -231,7 +248,7 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl)
     }
     HIP_TRY(hipSetDevice(c->device));
     pl.H = c->H; pl.W = c->W; pl.Wp = c->Wp;
-    if (kernel == Mx || kernel == ChipU8) {
+    if (kernel == Mx || kernel == ChipU8 || kernel == WideU8) {
         if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
         pl.p0 = c->pl0.p; pl.p1 = c->pl1.p; pl.sat0 = c->sat0.p; pl.sat1 = c->sat1.p;
     } else if (kernel == U16 || kernel == ChipU16) {
@@ -252,17 +269,17 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
 {
     static const char *const what[] = {"full-search kernel launch", "full-search u16 kernel launch", "full-search f32 kernel launch",
                                        "full-search general f32 kernel launch", "wide-search kernel launch", "full-search any-chip kernel launch",
-                                       "full-search any-chip u8 kernel launch", "full-search any-chip u16 kernel launch"};
+                                       "full-search any-chip u8 kernel launch", "full-search any-chip u16 kernel launch", "wide-search u8 kernel launch"};
     hipStream_t s = call.stream;
     MatchU8Args u = u8_args(c, call.d_xyuvav, call.xy_stride, call.xy_col, call.N, call.off_u, call.off_v, call.ocw, call.swap, call.d_out);
     u.H = pl.H; u.W = pl.W; u.Wp = pl.Wp;
     u.full_shift = call.d_shift; u.full_R = call.R; u.full_peak = call.d_peak;
     if (call.d_cand) { u.full_cand = call.d_cand; u.full_npeaks = call.npeaks; }
-    if (kernel < F32g || kernel == ChipU8 || kernel == ChipU16) u.full_surf = call.d_surf;       // (the float kernels take it as an argument of its own)
+    if (kernel < F32g || kernel == ChipU8 || kernel == ChipU16 || kernel == WideU8) u.full_surf = call.d_surf;       // (the float kernels take it as an argument of its own)
     u.p0 = static_cast<const unsigned char *>(pl.p0); u.p1 = static_cast<const unsigned char *>(pl.p1);
     if (pl.sat0) { u.sat0 = pl.sat0; u.sat1 = pl.sat1; u.satz0 = pl.satz0; u.satz1 = pl.satz1; u.sat_ws = sat_pitch(pl.Wp); }
     u.scale0 = pl.scale0; u.scale1 = pl.scale1;
-    const bool flags = kernel == Mx || kernel == ChipU8 || kernel == ChipU16;
+    const bool flags = kernel == Mx || kernel == ChipU8 || kernel == ChipU16 || kernel == WideU8;
     if (flags) HIP_TRY(c->mxl[0].reserve((size_t)call.N));             // one class byte per point, zero before the launch
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     hipError_t e;
@@ -283,6 +300,12 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
         const char *fe = getenv("MIMC3_CHIP_U16_FORMS");
         const int forms = fe ? atoi(fe) & 3 : 3;
         e = launch_match_full_chip_u16(u, forms ? forms : 3, s);
+    } else if (kernel == WideU8) {
+        // (MIMC3_WIDE_U8_FORMS: the same measurement-only switch for this kernel's two forms -- tools/wide_u8_time.py times the clean form
+        //  with it; DESIGN 4.1s names it.  With 1 the flagged points get no result: never set it around a real search)
+        const char *fe = getenv("MIMC3_WIDE_U8_FORMS");
+        const int forms = fe ? atoi(fe) & 3 : 3;
+        e = launch_match_wide_u8(u, forms ? forms : 3, s);
     } else if (kernel == U16) e = launch_match_full_u16(u, s);
     else if (kernel == F32i) e = launch_match_full_f32(u, s);
     else if (kernel == F32g) e = launch_match_full_f32g(u, call.d_surf, s);
@@ -303,6 +326,7 @@ static const SearchRules kFullAny = {kFloat, true, false, kCandOptional};
 static const SearchRules kFullChip = {kFloat, true, false, kCandOptional, false, false, false, false, true};    // (any_ocw)
 static const SearchRules kFullChipClass = {kFloat, true, false, kCandOptional, false, false, false, false, true, true};     // (any_ocw, chip_class)
 static const SearchRules kFullChipPlanes = {kFloat, true, false, kCandOptional, false, false, false, false, true, true, true};    // (..., chip_planes)
+static const SearchRules kWideClass = {kFloat, true, false, kCandOptional, false, false, false, false, true, true, false, true};    // (any_ocw, chip_class, wide_class)
 static const SearchRules kFullSurf = {kFloat, false, false, kCandOptional, false, false, false, true};     // (class_surf: surf is mandatory)
 static const SearchRules kWide = {kFloat, false, true, kCandOptional};
 static const SearchRules kFullFb = {kFloat, true, false, kCandOptional, true};
@@ -647,6 +671,33 @@ extern "C" int mimc3_match_ncc_wide(mimc3_ctx *c, const double *xyuvav, int32_t 
                                     int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, float *out, float *cand, float *surf)
 {
     return search_host(c, kWide, "mimc3_match_ncc_wide", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, 1, out, cand, surf, nullptr, nullptr);
+}
+
+// ... and beyond +-15 px with the 8-bit pair on the matrix cores at every chip size (match_wide_u8_kernel.hip): R <= 15 IS
+// mimc3_match_ncc_full_chip_class with the same mode; R >= 16 runs the matrix-core wide kernel on an 8-bit pair (mode 1 always; mode 0 where
+// wide_mode0 names it, and wherever the float wide kernel does not take the call) and the float wide kernel on any other pair in mode 0
+extern "C" int mimc3_wide_class_max_radius(int32_t ocw) { return wide_u8_max_radius(ocw); }
+extern "C" int mimc3_wide_class_layout(int32_t ocw, int32_t R, int32_t out[4])
+{
+    int l[4];
+    if (!out || !wide_u8_layout_query(ocw, R, l)) return 0;
+    for (int i = 0; i < 4; i++) out[i] = l[i];
+    return 1;
+}
+
+extern "C" int mimc3_match_ncc_wide_class_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                              const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                              float *d_out, float *d_cand, float *d_surf, void *stream)
+{
+    return search_dev(c, dev_call("mimc3_match_ncc_wide_class_dev", d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, d_surf, stream),
+                      kWideClass);
+}
+
+extern "C" int mimc3_match_ncc_wide_class(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                          int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *out, float *cand,
+                                          float *surf)
+{
+    return search_host(c, kWideClass, "mimc3_match_ncc_wide_class", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
 }
 
 // ... and with forward-backward consistency
