@@ -59,17 +59,22 @@ def phases(xy, offset, off, uv, ocw, shift=None, radius=None):
     return res
 
 
-def geometry(ocw):
+def geometry(ocw, reach=None):
     """-> (H, W, first u, first v, spacing in u, in v): odd spacings larger than the largest DLC window plus 4, so that no two windows
-    overlap; every window inside the image"""
+    overlap; every window inside the image.  reach (a search radius beyond 16, where the search boxes of that spacing overlap): odd
+    spacings larger than the search box of that radius at every offset of OFFSETS and under every a-priori shift, so that no two boxes
+    overlap; every box inside the image (a smaller reach leaves the grid as it is)"""
     dx2, dy2 = LU_MAX + ocw + 2, LV_MAX + ocw + 2
     su, sv = 2 * dx2 + 7, 2 * dy2 + 7
     mu, mv = dx2 + 6, dy2 + 6
+    if reach is not None:
+        hu, hv = reach + ocw + LU_MAX + 3, reach + ocw + LV_MAX + 3              # what a box reaches from its point, either way
+        su, sv, mu, mv = max(su, 2 * hu + 3), max(sv, 2 * hv + 3), max(mu, hu + 2), max(mv, hv + 2)
     return 2 * mv + (DIMY - 1) * sv, 2 * mu + (DIMX - 1) * su, mu, mv, su, sv
 
 
-def grid(ocw):
-    _, _, mu, mv, su, sv = geometry(ocw)
+def grid(ocw, reach=None):
+    _, _, mu, mv, su, sv = geometry(ocw, reach)
     iy, ix = np.divmod(np.arange(DIMX * DIMY), DIMX)
     u, v = (mu + su * ix).astype(np.float64), (mv + sv * iy).astype(np.float64)
     speed, ang = np.asarray(ROW_SPEED)[iy], np.deg2rad(np.asarray(ROW_ANGLE))[iy]
@@ -77,9 +82,9 @@ def grid(ocw):
     return np.ascontiguousarray(xy, np.float64)
 
 
-def planned_classes(ocw):
+def planned_classes(ocw, reach=None):
     """the null class of every point: within each (chip phase, parity of the row's |lu|) group the points cycle through the four"""
-    xy = grid(ocw)
+    xy = grid(ocw, reach)
     iy, ix = np.divmod(np.arange(DIMX * DIMY), DIMX)
     key = ((trunc(xy)[0] - ocw) & 3) * 2 + (iy & 1)
     cls = np.zeros(xy.shape[0], np.int64)
@@ -89,13 +94,13 @@ def planned_classes(ocw):
     return cls
 
 
-def _base(ocw, bits):
-    H, W = geometry(ocw)[:2]
+def _base(ocw, bits, reach=None):
+    H, W = geometry(ocw, reach)[:2]
     return synth.make_pair(H, W, TRUE_SHIFT, 9100 + ocw, noise_dn=2, bits=bits, sigma=1.0)
 
 
 @functools.lru_cache(maxsize=None)
-def fixture(ocw, kind="u8", plan="dlc"):
+def fixture(ocw, kind="u8", plan="dlc", reach=None):
     """One pair and one grid per chip size -> namespace (i0, i1, xy, off, uv: the pivots' CSR arrays, ocw, dt, mpp, cls: the planned null
     class per point, kind, plan); read-only arrays, shared among the tests.
 
@@ -107,20 +112,23 @@ def fixture(ocw, kind="u8", plan="dlc"):
       * plan "search": it sits ocw + 4 columns right of the point, a row down: inside the search box of radius SEARCH_R at every offset, with
         and without the a-priori shift.
     kind: "u8" synth.texture; "9bit" the remap of tests/test_match_parity.py's nine_bit_case (150 + 0.8 p), with a pixel of 500 next to
-    every 16th point, in chip and window; "12bit"; "eighths" (the 12-bit pair / 8); "16bit"."""
+    every 16th point, in chip and window; "12bit"; "eighths" (the 12-bit pair / 8); "16bit".
+    reach: the grid of geometry(ocw, reach), for searches of a radius beyond 16 (plan "search" only); a reach below SEARCH_R puts the
+    window's null 4 columns right of the point, a row down: at ocw >= 18 inside the search box of every radius from 1 on at every offset,
+    with and without the a-priori shift."""
     from oracle.oracle import Oracle
-    assert kind in KINDS and plan in ("dlc", "search")
-    i0, i1 = _base(ocw, {"u8": 8, "9bit": 8, "12bit": 12, "eighths": 12, "16bit": 16}[kind])
+    assert kind in KINDS and plan in ("dlc", "search") and (reach is None or plan == "search")
+    i0, i1 = _base(ocw, {"u8": 8, "9bit": 8, "12bit": 12, "eighths": 12, "16bit": 16}[kind], reach)
     if kind == "9bit":
         i0, i1 = (np.round(150.0 + i * 0.8).astype(np.float32) for i in (i0, i1))
     elif kind == "eighths":
         i0, i1 = (i0 / 8).astype(np.float32), (i1 / 8).astype(np.float32)
     H, W = i0.shape
-    xy = grid(ocw)
+    xy = grid(ocw, reach)
     off, uv = Oracle("port").get_uv_pivot(xy, synth.DT_DAYS, synth.MPP, ocw, H, W)
     last = uv[off[1:] - 1].astype(np.int64)
     u0, v0 = trunc(xy)
-    cls = planned_classes(ocw)
+    cls = planned_classes(ocw, reach)
     cw = 2 * ocw + 1
     for g in range(xy.shape[0]):
         if kind == "9bit" and g in BRIGHT_POINTS:
@@ -134,7 +142,7 @@ def fixture(ocw, kind="u8", plan="dlc"):
                 dx2 = abs(last[g, 0]) + ocw + 2
                 i1[v0[g], u0[g] - dx2 + 4 if last[g, 0] > 0 else u0[g] + dx2 - 1] = 0.0
             else:
-                i1[v0[g] + 1, u0[g] + ocw + 4] = 0.0
+                i1[v0[g] + 1, u0[g] + (4 if reach is not None and reach < SEARCH_R else ocw + 4)] = 0.0
     for a in (i0, i1, xy, off, uv, cls):
         a.setflags(write=False)
     return types.SimpleNamespace(i0=i0, i1=i1, xy=xy, off=off, uv=uv, ocw=ocw, dt=synth.DT_DAYS, mpp=synth.MPP, cls=cls, kind=kind, plan=plan,

@@ -81,7 +81,7 @@ def test_size_cases_are_the_librarys(api):
 
 @pytest.mark.parametrize("ocw,radius", fp.size_cases())
 def test_chip_sizes(api, ocw, radius):
-    c, rec, surf = run_fixture(api, ocw, radius, oracle=ocw in (1, 2, 3, 10, 11, 25, 57, 80))
+    c, rec, surf = run_fixture(api, ocw, radius, oracle=True)           # (12 points: the oracle stays under a second at every size)
     assert (rec[:, 2] >= -1).any() and np.isfinite(surf).all()
     for g in fp.BOX_ONLY + fp.CHIP_ONLY + fp.BOTH:
         assert rec[g, 2] >= -1 or rec[g, 2] == -4
