@@ -93,6 +93,9 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *       planes (two 6-bit planes per pixel) and their tables.
  *  14 = the exhaustive search beyond +-15 px of mimc3_match_ncc_wide_class on an 8-bit pair (R >= 16): the matrix-core wide search kernel on
  *       the u8 planes and their tables, at any chip half-width 1..80.
+ *  15 = the exhaustive search beyond +-15 px of mimc3_match_ncc_wide_planes on a scaled-integer pair (R >= 16), or on an 8-bit or
+ *       scaled-integer pair with its mode 1: the matrix-core wide search kernel on the u16 planes (two 6-bit planes per pixel) and their
+ *       tables, at any chip half-width 1..80.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -539,7 +542,8 @@ int mimc3_match_ncc_wide_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, 
  *   R 16 / 47, where it is the only kernel: 552.5 / 1411.2 ms.
  *   MIMC3_hip_offsets calls this entry in mode 0 at levels = 1, fb = 0, 16 <= R <= mimc3_wide_max_radius(ocw): the same files, an 8-bit raw
  *   pair on the matrix cores.
- *   Out of scope: 12-bit pairs beyond R 15 on the matrix cores; mimc3_stack_add / _add_class, mimc3_match_ncc_wide_fb and
+ *   12-bit and filtered pairs beyond R 15 on the matrix cores: mimc3_match_ncc_wide_planes, below.
+ *   Out of scope: mimc3_stack_add / _add_class, mimc3_match_ncc_wide_fb and
  *   Context.full_candidates through this kernel; an ocw outside the six on the command line at R > 15; the pyramids; several GPUs. */
 int mimc3_wide_class_max_radius(int32_t ocw);
 int mimc3_wide_class_layout(int32_t ocw, int32_t R, int32_t out[4]);
@@ -551,6 +555,55 @@ int mimc3_match_ncc_wide_class(mimc3_ctx *ctx, const double *xyuvav, int32_t N, 
 int mimc3_match_ncc_wide_class_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                    const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
                                    float *d_out, float *d_cand, float *d_surf, void *stream);
+
+/* ---- The exhaustive search beyond +-15 px with the SCALED-INTEGER pair (u16 planes, q < 4096: 12-bit DN, and the d/dx, d/dy and Laplacian
+ *      forms of an 8-bit pair) on the matrix cores as well, at ANY chip half-width 1 <= ocw <= 80 (match_wide_u16_kernel.hip).
+ *   The arguments are those of mimc3_match_ncc_wide_class: 1 <= ocw <= 80, 1 <= R <= mimc3_wide_class_max_radius(ocw), else MIMC3_EINVAL.
+ *   R <= 15, any mode   mimc3_match_ncc_full_chip_planes with the same mode: its kernel, its bytes, its last_path.
+ *   R >= 16, mode 1     the matrix-core wide kernel on the u16 planes, mimc3_ctx_last_path 15 ("u16_mfma_wide"), on an 8-bit pair (q < 256 on
+ *                       its u16 planes) and on a scaled-integer pair; any other pair: MIMC3_EUNSUPPORTED.  R beyond
+ *                       mimc3_wide_planes_max_radius(ocw): MIMC3_EUNSUPPORTED, with the limit in the message.
+ *   R >= 16, mode 0     an 8-bit pair goes where mimc3_match_ncc_wide_class (mode 0) sends it (last_path 14).  A scaled-integer pair runs
+ *                       the u16-plane wide kernel (last_path 15) at every (ocw, R <= mimc3_wide_planes_max_radius(ocw)) named by the measured
+ *                       rule below and at every such (ocw, R) mimc3_match_ncc_wide does not take; elsewhere mimc3_match_ncc_wide's kernel
+ *                       where that takes (ocw, R) (last_path 10); beyond both kernels: MIMC3_EUNSUPPORTED.  Every other class is served
+ *                       or refused as mimc3_match_ncc_wide_class does it.
+ *   any other mode      MIMC3_EINVAL.  Every refusal comes before anything is enqueued or written, in the family's order.
+ *   The kernel.  mimc3_match_ncc_full_chip_planes's (two 6-bit planes per pixel, three correlations per K chunk, sum ab put together in 64-bit
+ *   integers, the row-box sums as three, four and one byte planes, the chip's sums in 64 x 64 sub-boxes of the packed u16 table, the null
+ *   counts from the u32 null table, the f64 finish of the float kernel) over mimc3_match_ncc_wide_class's grid of ceil(S / 32)^2 tiles of
+ *   32 x 32 cells: both chip planes staged once per point, both window tiles restaged per tile, the surface at pitch 96 in LDS bytes of its
+ *   own, then mimc3_match_ncc_wide's tails, unmodified.  A clean form over all points flags those with a null in the chip or the box; a
+ *   masked form runs behind it over the flagged points.
+ *   Promise on an 8-bit or scaled-integer pair: record, candidates and surface are the bytes of the definition mimc3_match_ncc_wide states
+ *   (mimc3_match_ncc_full_any in mode 1, word for word) -- at the six chip sizes within mimc3_wide_max_radius those of mimc3_match_ncc_wide
+ *   itself (finite surface cells bit for bit, a non-finite cell of the same kind).
+ *   mimc3_wide_planes_max_radius(ocw)   the largest R <= 47 whose layout -- two tiles, two chip planes, the surface of (2R + 1) x 96 x 4 bytes --
+ *              fits the 160 KB of a CU: 47 for ocw 1..68; 46 / 45 / 44 / 43 at ocw 69 / 70 / 71 / 72; 34 at ocw 73, one less per ocw down to
+ *              27 at ocw 80 (163,680 bytes); 0 outside 1..80.  The single source of the limit.
+ *   mimc3_wide_planes_layout(ocw, R, out)   out[0] K chunks of 64 window columns per chip row (1..3), out[1] cell tiles per axis (2..3),
+ *              out[2] threads per workgroup (128), out[3] dynamic LDS bytes, from the constexpr layout the launch uses; returns 1, or 0
+ *              outside 1 <= ocw <= 80, 16 <= R <= mimc3_wide_planes_max_radius(ocw).
+ *   The mode-0 rule: an (ocw, R) that mimc3_match_ncc_wide also takes goes to the matrix-core kernel where every pass of its series was
+ *   faster than every pass of the float wide kernel's in the same session (tools/wide_u16_time.py, profiles/full_search_wide_u16/).
+ *   Measured on C2 as 12-bit DN and as its d/dx pair (189,054 points, one MI355X): true in all 32 configurations the float kernel takes -- ocw 16 at
+ *   R 16 / 23 / 31 / 32 / 47: 16.33 / 18.16 / 24.98 / 41.93 / 67.72 ms against 103.0 / 196.7 / 386.6 / 464.9 / 1296.0; ocw 7 at R 16 / 47: 7.78 / 38.58 against 19.9 / 276.3;
+ *   ocw 40 at R 16: 151.7 against 1646.2 at R 16 -- and in a second run at ocw 15, 30 and 32 (R 16 and 47: 5.0 to 16.9 times faster), so every (ocw, R) that
+ *   mimc3_match_ncc_wide takes goes to the matrix-core kernel; ocw 80, where it is the only kernel: 1170.5 / 1407.1 ms at R 16 / 27.
+ *   MIMC3_hip_offsets calls this entry in mode 0 where it called mimc3_match_ncc_wide_class: the same files, a filtered pair and a 12-bit
+ *   pair in a 16-bit TIFF on the matrix cores.
+ *   Out of scope: integral-f32 (16-bit DN) pairs beyond R 15; mimc3_stack_add*, mimc3_match_ncc_wide_fb and Context.full_candidates through
+ *   the class wide kernels; an ocw outside the six on the command line at R > 15; the pyramids; several GPUs. */
+int mimc3_wide_planes_max_radius(int32_t ocw);
+int mimc3_wide_planes_layout(int32_t ocw, int32_t R, int32_t out[4]);
+int mimc3_match_ncc_wide_planes(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                                const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                                int32_t swap, int32_t mode, float *out /*[N][8] host*/,
+                                float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/, float *surf /*[N][(2R+1)^2] host, or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_full_chip_planes_dev. */
+int mimc3_match_ncc_wide_planes_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                    const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                    float *d_out, float *d_cand, float *d_surf, void *stream);
 
 /* ---- Forward-backward consistency of the exhaustive search: is a peak RECIPROCAL -- does matching back from where a point landed return
  *      to where it started?  (The back-matching test AMPCOR and IMCORR users apply after the run; the record's quality columns all

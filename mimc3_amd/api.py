@@ -85,6 +85,10 @@ _lib.mimc3_wide_class_max_radius.argtypes = [C.c_int32]
 _lib.mimc3_wide_class_layout.argtypes = [C.c_int32, C.c_int32, _vp]
 _lib.mimc3_match_ncc_wide_class.argtypes = _lib.mimc3_match_ncc_full_chip.argtypes
 _lib.mimc3_match_ncc_wide_class_dev.argtypes = _lib.mimc3_match_ncc_full_chip_dev.argtypes
+_lib.mimc3_wide_planes_max_radius.argtypes = [C.c_int32]
+_lib.mimc3_wide_planes_layout.argtypes = [C.c_int32, C.c_int32, _vp]
+_lib.mimc3_match_ncc_wide_planes.argtypes = _lib.mimc3_match_ncc_full_chip.argtypes
+_lib.mimc3_match_ncc_wide_planes_dev.argtypes = _lib.mimc3_match_ncc_full_chip_dev.argtypes
 _lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
 _lib.mimc3_match_ncc_full_fb.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
@@ -311,6 +315,21 @@ def wide_class_layout(ocw, radius):
     16 <= radius <= 47."""
     out = (C.c_int32 * 4)()
     return tuple(int(v) for v in out) if _lib.mimc3_wide_class_layout(int(ocw), int(radius), out) else None
+
+
+def wide_planes_max_radius(ocw):
+    """The largest radius match_ncc_wide_planes's matrix-core kernel on the u16 planes takes at this chip half-width
+    (mimc3_wide_planes_max_radius): the largest radius <= 47 whose layout fits the LDS of a CU -- 47 for ocw 1..68, falling to 27 at ocw
+    80; 0 outside 1 <= ocw <= full_chip_max_ocw()."""
+    return int(_lib.mimc3_wide_planes_max_radius(int(ocw)))
+
+
+def wide_planes_layout(ocw, radius):
+    """The layout of match_ncc_wide_planes's matrix-core kernel (mimc3_wide_planes_layout) -> (K chunks of 64 window columns per chip row,
+    32 x 32 cell tiles per axis, threads per workgroup, dynamic LDS bytes); None outside 1 <= ocw <= full_chip_max_ocw(),
+    16 <= radius <= wide_planes_max_radius(ocw)."""
+    out = (C.c_int32 * 4)()
+    return tuple(int(v) for v in out) if _lib.mimc3_wide_planes_layout(int(ocw), int(radius), out) else None
 
 
 def wide_lds_bytes(ocw, radius):
@@ -781,6 +800,26 @@ class Context:
         _check(_lib.mimc3_match_ncc_wide_class_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
                                                    npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
                "match_ncc_wide_class_dev")
+
+    def match_ncc_wide_planes(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False, mode=0, surface=False):
+        """The exhaustive search beyond +-15 px with the 8-bit AND the scaled-integer pair (12-bit DN, a filtered 8-bit pair) on the matrix
+        cores at every chip half-width 1..80 (mimc3_match_ncc_wide_planes), 1 <= radius <= wide_class_max_radius(ocw).  radius <= 15 is
+        match_ncc_full_chip_planes with the same mode, byte for byte.  radius >= 16: mode 1 runs the matrix-core wide kernel on the u16
+        planes ("u16_mfma_wide") up to wide_planes_max_radius(ocw) and takes 8-bit and scaled-integer pairs only; mode 0 sends an 8-bit
+        pair where match_ncc_wide_class does, runs a scaled-integer pair on "u16_mfma_wide" (or on "f32g_wide" beyond its radius, where
+        match_ncc_wide takes (ocw, radius)) and any other pair as match_ncc_wide_class does.  The bytes are match_ncc_wide's
+        -> (record, candidates or None[, surfaces]) as there."""
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_wide_planes", xyuvav, shift, npeaks=npeaks, radius=radius, surface=surface)
+        _check(_lib.mimc3_match_ncc_wide_planes(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh), ocw, radius, int(npeaks),
+                                                1 if swap else 0, int(mode), out, _ptr(cand), _ptr(surf)), "match_ncc_wide_planes")
+        return (out, cand, surf) if surface else (out, cand)
+
+    def match_ncc_wide_planes_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, mode=0,
+                                  d_surf=0):
+        """Device-pointer variant (enqueue only): as match_ncc_full_chip_dev."""
+        _check(_lib.mimc3_match_ncc_wide_planes_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                    npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
+               "match_ncc_wide_planes_dev")
 
     def match_ncc_full_fb(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, mode=0):
         """Forward-backward consistency of the exhaustive search (mimc3_match_ncc_full_fb): the forward pass is match_ncc_full_any(swap
@@ -1301,7 +1340,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip", 12: "u8_mfma_chip", 13: "u16_mfma_chip", 14: "u8_mfma_wide"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip", 12: "u8_mfma_chip", 13: "u16_mfma_chip", 14: "u8_mfma_wide", 15: "u16_mfma_wide"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

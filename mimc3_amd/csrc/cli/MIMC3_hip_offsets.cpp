@@ -29,8 +29,8 @@
 //   [(1 + K) N][4], plane-major, K = 0 for peaks = 1 and peaks otherwise -- row p N + i = (du_b, dv_b, ncc_b or status, err) of grid
 //   point i's record (p = 0) or candidate p - 1.  fb = 0 writes exactly the files of a run without the argument
 // R = 16 .. mimc3_wide_max_radius(ocw) (47; 39 at ocw 40; with levels = 1 only): one exact pass over the whole range
-//   (mimc3_match_ncc_wide_class in mode 0: a raw 8-bit pair on the matrix cores, every other pair on the float wide kernel -- the bytes of
-//   mimc3_match_ncc_wide either way; with fb = 1 mimc3_match_ncc_wide_fb) on 8-bit and 16-bit pairs, raw or filtered; the same files, peaks and
+//   (mimc3_match_ncc_wide_planes in mode 0: a raw 8-bit pair, a filtered pair and a 12-bit pair in a 16-bit TIFF on the matrix cores, every
+//   other pair on the float wide kernel -- the bytes of mimc3_match_ncc_wide either way; with fb = 1 mimc3_match_ncc_wide_fb) on 8-bit and 16-bit pairs, raw or filtered; the same files, peaks and
 //   filter as above.  R <= 15 takes exactly the calls of a build without this range and writes the same bytes
 // ocw = 1 .. mimc3_full_chip_max_ocw() (80) other than 7, 15, 16, 30, 32, 40 (with levels = 1, fb = 0 and R <= 15 only): the search through
 //   mimc3_match_ncc_full_chip_planes (mode 0: an 8-bit or scaled-integer pair on the matrix cores, every other on the float kernel; the bytes of
@@ -164,8 +164,8 @@ int main(int argc, char *argv[])
     if (mimc3_prior_shift(xy.data(), N, dt, r.mpp, shift.data()) ||
         (wide ? (fbk ? mimc3_match_ncc_wide_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, rec.data(),
                                                K > 0 ? cand.data() : nullptr, fb.data())
-                     : mimc3_match_ncc_wide_class(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, 0, rec.data(),
-                                                  K > 0 ? cand.data() : nullptr, nullptr))
+                     : mimc3_match_ncc_wide_planes(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, 0, rec.data(),
+                                                   K > 0 ? cand.data() : nullptr, nullptr))
          : any_chip ? mimc3_match_ncc_full_chip_planes(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, 0, rec.data(),
                                                        K > 0 ? cand.data() : nullptr, nullptr)
          : fbk ? mimc3_match_ncc_full_fb(ctx, xy.data(), N, offset, shift.data(), ocw, R, peaks != 1 ? peaks : 0, 0, rec.data(),

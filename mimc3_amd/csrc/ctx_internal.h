@@ -188,8 +188,12 @@ struct SearchRules {
     bool wide_class = false;            // with chip_class (mimc3_match_ncc_wide_class): the radius limit is wide_u8_max_radius(ocw); beyond R 15 an
                                         // 8-bit pair runs the matrix-core wide kernel (mode 1 always, mode 0 where wide_mode0 names it or the
                                         // float wide kernel does not take the call), any other class the float wide kernel where that takes it
+    bool wide_planes = false;           // with wide_class and chip_planes (mimc3_match_ncc_wide_planes): beyond R 15 a scaled-integer pair runs the
+                                        // matrix-core wide kernel on the u16 planes (mode 1 always, an 8-bit pair included; mode 0 where
+                                        // wide_planes_mode0 names it or the float wide kernel does not take the call), up to
+                                        // wide_u16_max_radius(ocw); R <= 15 is the chip_planes entry
 };
-enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8, ChipU16, WideU8 };       // last_path 6 .. 14
+enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8, ChipU16, WideU8, WideU16 };       // last_path 6 .. 15
 struct PlaneSet {
     const void *p0, *p1, *sat0, *sat1, *satz0, *satz1;
     int32_t H, W, Wp;

@@ -292,6 +292,13 @@ hipError_t launch_match_full_chip_u16(MatchU8Args a, int forms, hipStream_t stre
 int wide_u8_max_radius(int ocw);
 bool wide_u8_layout_query(int ocw, int R, int out[4]);
 hipError_t launch_match_wide_u8(MatchU8Args a, int forms, hipStream_t stream);
+// ... and on the u16 planes of a SCALED-INTEGER pair (q < 4096; match_wide_u16_kernel.hip; mimc3_match_ncc_wide_planes): the arguments and
+// forms of launch_match_full_chip_u16 with 16 <= a.full_R <= wide_u16_max_radius(a.ocw) -- that kernel over the same grid of 32 x 32 cell
+// tiles.  wide_u16_max_radius: the largest R <= 47 whose two tiles, two chip planes and surface fit a CU's LDS (47 up to ocw 68, 27 at
+// ocw 80; 0 outside 1 .. kFullChipMaxOcw).  wide_u16_layout_query: as wide_u8_layout_query (false outside 16 .. wide_u16_max_radius(ocw))
+int wide_u16_max_radius(int ocw);
+bool wide_u16_layout_query(int ocw, int R, int out[4]);
+hipError_t launch_match_wide_u16(MatchU8Args a, int forms, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344,"MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all

@@ -1,5 +1,5 @@
 // search.cpp -- the host layer of the exhaustive-search family of the C ABI (include/mimc3_hip.h): mimc3_match_ncc_full, _full_multi,
-// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _full_chip_planes, _wide, _wide_class, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
+// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _full_chip_planes, _wide, _wide_class, _wide_planes, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
 // _pyramid_any), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
 // (SearchRules); search_check makes every refusal, pick_kernel selects the kernel, plane_set points at the planes it reads (building
 // them on first use), launch_search is the one place that launches.  The stack's layer adds (stack.cpp) go through the same functions.
@@ -47,7 +47,8 @@ static int check_class(mimc3_ctx *c, PairClass widest, const std::string &en)
 //   2. the context's state, MIMC3_ESTATE: no images; a chip-atlas context
 //   3. the pair's class, MIMC3_EUNSUPPORTED (chip_class in mode 1: any pair that is not 8-bit; chip_planes in mode 1: any pair that is
 //      neither 8-bit nor scaled-integer; wide_class beyond R 15 in mode 0: a pair that is not 8-bit at an (ocw, R) the float wide kernel does
-//      not take)
+//      not take; wide_planes beyond R 15: in mode 1 a radius beyond mimc3_wide_planes_max_radius(ocw), in mode 0 a scaled-integer pair
+//      beyond that radius at an (ocw, R) the float wide kernel does not take -- every other class as wide_class)
 //   4. MIMC3_EINVAL again: a coarsest pyramid level smaller than a chip; a mode other than 0 or 1; forward-backward rows without d_fb.
 //      The _dev entries of the full searches have always made the last two with the arguments, under 1, and keep doing so: without
 //      images they answer a bad mode with MIMC3_EINVAL where their host entries and the pyramids answer MIMC3_ESTATE.
@@ -78,7 +79,13 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
     if (c->child) return fail(MIMC3_ESTATE, en + ": not on a chip-atlas context");
     RC_TRY(check_class(c, call.mode == 1 && rules.chip_planes ? kScaledInt : call.mode == 1 && rules.chip_class ? kU8 : rules.widest, en));
     // (wide_class beyond R 15, mode 0: a pair that is not 8-bit has the float wide kernel alone, which takes the six chip sizes up to its own radius)
-    if (rules.wide_class && call.R > 15 && call.mode == 0 && !c->u8_ok && !wide_float_takes(call.ocw, call.R))
+    if (rules.wide_planes && call.R > 15 && (call.mode == 1 || (call.mode == 0 && !c->u8_ok && c->u16_ok))) {
+        // (the matrix-core wide kernel on the u16 planes reaches wide_u16_max_radius(ocw); in mode 0 the float wide kernel serves what it takes)
+        const int32_t lim = wide_u16_max_radius(call.ocw);
+        if (call.R > lim && (call.mode == 1 || !wide_float_takes(call.ocw, call.R)))
+            return fail(MIMC3_EUNSUPPORTED, en + ": beyond R 15 the u16-plane matrix-core kernel takes R <= mimc3_wide_planes_max_radius(ocw) = " +
+                                            std::to_string(lim) + " at ocw " + std::to_string(call.ocw));
+    } else if (rules.wide_class && call.R > 15 && call.mode == 0 && !c->u8_ok && !wide_float_takes(call.ocw, call.R))
         return fail(MIMC3_EUNSUPPORTED, en + ": beyond R 15 a pair that is not 8-bit needs ocw one of 7, 15, 16, 30, 32, 40 and R <= mimc3_wide_max_radius(ocw)");
     if (rules.pyramid && std::min(c->H >> (call.levels - 1), c->W >> (call.levels - 1)) < 2 * call.ocw + 1)
         return fail(MIMC3_EINVAL, en + ": level " + std::to_string(call.levels - 1) + " is smaller than a chip");
@@ -130,10 +137,23 @@ static bool chip_mode0(SearchKernel, int32_t ocw) { return ocw >= 1 && ocw <= kF
 // series was faster than every pass of the float kernel's in the same session -- on BASELINE C2
 // every configuration measured (ocw 7, 16, 40; R 16 .. 47; npeaks 0 and 4: 3.4 to 32.2 times faster; ocw 15, 30, 32 at R 16 and 47 in a second run: 9.4 to 25.8), so no (ocw, R) stays on the float kernel
 static bool wide_mode0(int32_t ocw, int32_t R) { return ocw >= 1 && ocw <= kFullChipMaxOcw && R >= 16 && R <= wide_u8_max_radius(ocw); }
+// The same rule for a scaled-integer pair (mimc3_match_ncc_wide_planes, mode 0) on the series of tools/wide_u16_time.py
+// (profiles/full_search_wide_u16/): an (ocw, R) the float wide kernel also takes goes to the matrix-core wide kernel on
+// the u16 planes where every pass of its series was faster than every pass of the float kernel's in the same session -- on BASELINE C2 as 12-bit DN and as
+// its d/dx pair every configuration measured (ocw 7, 16, 40; R 16 .. 47; npeaks 0 and 4: 2.4 to 19.1 times faster; ocw 15, 30, 32 at R 16 and 47 in a second run:
+// 5.0 to 16.9), so no (ocw, R) stays on the float kernel
+static bool wide_planes_mode0(int32_t ocw, int32_t R) { return ocw >= 1 && ocw <= kFullChipMaxOcw && R >= 16 && R <= wide_u16_max_radius(ocw); }
 
 int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel)
 {
-    if (call.R > 15 && rules.wide_class) {
+    if (call.R > 15 && rules.wide_planes && (call.mode == 1 || (!c->u8_ok && c->u16_ok))) {
+        // (mode 1: search_check has refused every pair that is neither 8-bit nor scaled-integer, and every radius beyond the kernel's;
+        //  mode 0, a scaled-integer pair: search_check has refused what neither kernel takes)
+        const bool u16 = call.mode == 1 || (call.R <= wide_u16_max_radius(call.ocw) &&
+                                            (wide_planes_mode0(call.ocw, call.R) || !wide_float_takes(call.ocw, call.R)));
+        kernel = u16 ? WideU16 : Wide;
+    }
+    else if (call.R > 15 && rules.wide_class) {
         // (mode 1: search_check has refused every pair that is not 8-bit; mode 0: every pair the float wide kernel cannot take)
         const bool u8 = call.mode == 1 || (c->u8_ok && (wide_mode0(call.ocw, call.R) || !wide_float_takes(call.ocw, call.R)));
         kernel = u8 ? WideU8 : Wide;
@@ -251,7 +271,7 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl)
     if (kernel == Mx || kernel == ChipU8 || kernel == WideU8) {
         if (!c->sat_u8_ok) RC_TRY(build_u8_tables(c));
         pl.p0 = c->pl0.p; pl.p1 = c->pl1.p; pl.sat0 = c->sat0.p; pl.sat1 = c->sat1.p;
-    } else if (kernel == U16 || kernel == ChipU16) {
+    } else if (kernel == U16 || kernel == ChipU16 || kernel == WideU16) {
         if (!c->hpl_valid || !c->sat_u16_ok) RC_TRY(build_u16(c, true));
         pl.p0 = c->hpl0.p; pl.p1 = c->hpl1.p; pl.sat0 = c->hsat0.p; pl.sat1 = c->hsat1.p; pl.satz0 = c->hsz0.p; pl.satz1 = c->hsz1.p;
     } else {
@@ -269,17 +289,18 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
 {
     static const char *const what[] = {"full-search kernel launch", "full-search u16 kernel launch", "full-search f32 kernel launch",
                                        "full-search general f32 kernel launch", "wide-search kernel launch", "full-search any-chip kernel launch",
-                                       "full-search any-chip u8 kernel launch", "full-search any-chip u16 kernel launch", "wide-search u8 kernel launch"};
+                                       "full-search any-chip u8 kernel launch", "full-search any-chip u16 kernel launch", "wide-search u8 kernel launch",
+                                       "wide-search u16 kernel launch"};
     hipStream_t s = call.stream;
     MatchU8Args u = u8_args(c, call.d_xyuvav, call.xy_stride, call.xy_col, call.N, call.off_u, call.off_v, call.ocw, call.swap, call.d_out);
     u.H = pl.H; u.W = pl.W; u.Wp = pl.Wp;
     u.full_shift = call.d_shift; u.full_R = call.R; u.full_peak = call.d_peak;
     if (call.d_cand) { u.full_cand = call.d_cand; u.full_npeaks = call.npeaks; }
-    if (kernel < F32g || kernel == ChipU8 || kernel == ChipU16 || kernel == WideU8) u.full_surf = call.d_surf;       // (the float kernels take it as an argument of its own)
+    if (kernel < F32g || kernel == ChipU8 || kernel == ChipU16 || kernel == WideU8 || kernel == WideU16) u.full_surf = call.d_surf;       // (the float kernels take it as an argument of its own)
     u.p0 = static_cast<const unsigned char *>(pl.p0); u.p1 = static_cast<const unsigned char *>(pl.p1);
     if (pl.sat0) { u.sat0 = pl.sat0; u.sat1 = pl.sat1; u.satz0 = pl.satz0; u.satz1 = pl.satz1; u.sat_ws = sat_pitch(pl.Wp); }
     u.scale0 = pl.scale0; u.scale1 = pl.scale1;
-    const bool flags = kernel == Mx || kernel == ChipU8 || kernel == ChipU16 || kernel == WideU8;
+    const bool flags = kernel == Mx || kernel == ChipU8 || kernel == ChipU16 || kernel == WideU8 || kernel == WideU16;
     if (flags) HIP_TRY(c->mxl[0].reserve((size_t)call.N));             // one class byte per point, zero before the launch
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     hipError_t e;
@@ -306,6 +327,12 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
         const char *fe = getenv("MIMC3_WIDE_U8_FORMS");
         const int forms = fe ? atoi(fe) & 3 : 3;
         e = launch_match_wide_u8(u, forms ? forms : 3, s);
+    } else if (kernel == WideU16) {
+        // (MIMC3_WIDE_U16_FORMS: the same measurement-only switch for this kernel's two forms -- tools/wide_u16_time.py times the clean form
+        //  with it; DESIGN 4.1t names it.  With 1 the flagged points get no result: never set it around a real search)
+        const char *fe = getenv("MIMC3_WIDE_U16_FORMS");
+        const int forms = fe ? atoi(fe) & 3 : 3;
+        e = launch_match_wide_u16(u, forms ? forms : 3, s);
     } else if (kernel == U16) e = launch_match_full_u16(u, s);
     else if (kernel == F32i) e = launch_match_full_f32(u, s);
     else if (kernel == F32g) e = launch_match_full_f32g(u, call.d_surf, s);
@@ -327,6 +354,7 @@ static const SearchRules kFullChip = {kFloat, true, false, kCandOptional, false,
 static const SearchRules kFullChipClass = {kFloat, true, false, kCandOptional, false, false, false, false, true, true};     // (any_ocw, chip_class)
 static const SearchRules kFullChipPlanes = {kFloat, true, false, kCandOptional, false, false, false, false, true, true, true};    // (..., chip_planes)
 static const SearchRules kWideClass = {kFloat, true, false, kCandOptional, false, false, false, false, true, true, false, true};    // (any_ocw, chip_class, wide_class)
+static const SearchRules kWidePlanes = {kFloat, true, false, kCandOptional, false, false, false, false, true, true, true, true, true};    // (..., chip_planes, wide_class, wide_planes)
 static const SearchRules kFullSurf = {kFloat, false, false, kCandOptional, false, false, false, true};     // (class_surf: surf is mandatory)
 static const SearchRules kWide = {kFloat, false, true, kCandOptional};
 static const SearchRules kFullFb = {kFloat, true, false, kCandOptional, true};
@@ -698,6 +726,30 @@ extern "C" int mimc3_match_ncc_wide_class(mimc3_ctx *c, const double *xyuvav, in
                                           float *surf)
 {
     return search_host(c, kWideClass, "mimc3_match_ncc_wide_class", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
+}
+
+// ... and with the scaled-integer pair (12-bit DN, a filtered 8-bit pair) on the matrix cores as well (match_wide_u16_kernel.hip): R <= 15
+// IS mimc3_match_ncc_full_chip_planes
+extern "C" int mimc3_wide_planes_max_radius(int32_t ocw) { return wide_u16_max_radius(ocw); }
+extern "C" int mimc3_wide_planes_layout(int32_t ocw, int32_t R, int32_t out[4])
+{
+    int l[4];
+    if (!out || !wide_u16_layout_query(ocw, R, l)) return 0;
+    for (int i = 0; i < 4; i++) out[i] = l[i];
+    return 1;
+}
+extern "C" int mimc3_match_ncc_wide_planes_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                               const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                               float *d_out, float *d_cand, float *d_surf, void *stream)
+{
+    return search_dev(c, dev_call("mimc3_match_ncc_wide_planes_dev", d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, d_surf, stream),
+                      kWidePlanes);
+}
+extern "C" int mimc3_match_ncc_wide_planes(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                           int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *out, float *cand,
+                                           float *surf)
+{
+    return search_host(c, kWidePlanes, "mimc3_match_ncc_wide_planes", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
 }
 
 // ... and with forward-backward consistency
