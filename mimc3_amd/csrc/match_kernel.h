@@ -167,7 +167,8 @@ __device__ __forceinline__ void mx_climb_area(int lu, int lv, int ocw, int dx2, 
     px = lox; py = loy;                                         // (the box of cell c: window pixels c .. c + 2 ocw)
     pw = min(hix + 2 * ocw + 1, 2 * dx2) - lox; ph = min(hiy + 2 * ocw + 1, 2 * dy2) - loy;
 }
-// the area's bounds in a record (U8PointRec::npiv, bits 8-27), and the whole tile: what a point without window nulls carries
+// the area's bounds in a record (U8PointRec::npiv, bits 8-27), and the whole tile: what a point carries when areas are off (mx_area_on).
+// The clean form finishes the NCC of the area's cells alone (whole bands of four tile rows), so a clean point carries its area as well
 __device__ __forceinline__ uint32_t mx_area_pack(const int (&a)[4]) { return ((uint32_t)a[0] | (uint32_t)a[1] << 5 | (uint32_t)a[2] << 10 | (uint32_t)a[3] << 15) << 8; }
 constexpr uint32_t kMxAreaTile = (0u | 31u << 5 | 0u << 10 | 31u << 15) << 8;
 constexpr uint32_t kRecNpivMask = 0xffu;
@@ -233,10 +234,12 @@ size_t u8_lists_bytes(int N);
 U8PointRec *u8_list_recs(int32_t *lists, int N);
 bool u8_point_records_on();        // (tuning / A-B: MIMC3_U8_RECS=0 keeps the memory headers)
 bool u8_advance_on();              // (tuning / A-B: MIMC3_U8_ADVANCE=0, or no records, leaves the advance list empty)
+bool mx_area_on();                 // (tuning / A-B: MIMC3_MX_AREA=0, or no advance list, gives clean points the whole tile as their area)
 hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream);
 // (u8_classify_kernel.hip; wn_on / gen_on: which forms for null-ridden points run behind the clean form)
-// advance: also write the advance list (needs the records) -- else its length is 0
-hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, bool advance, hipStream_t stream);
+// advance: also write the advance list (needs the records) -- else its length is 0; clean_area: clean points' records carry their
+// climb area (mx_climb_area) instead of the whole tile
+hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, bool advance, bool clean_area, hipStream_t stream);
 // exhaustive-search NCC offsets on the same surfaces (mimc3_match_ncc_full): every point on the matrix cores -- the clean form, then
 // the window-null and general forms over the points it flags (a.mx_flags: N bytes, zero before the call); a.full_R in 1..15,
 // a.ocw one of 7, 15, 16, 30, 32, 40; a.out [N][8]; a.full_peak (optional, int32 [N]) gets every point's arg-max cell k = (su + R)(2R + 1)

@@ -36,6 +36,9 @@
 // and derived of that point: the clean form starts from that one record, and a point it appends takes its record along.
 // Behind its clean list the same launch tries the advance list: window-null points whose climb area holds no null, for which the clean
 // form's cells inside that area are exact (mx_climb_area, match_kernel.h) -- finished only if every scan stays inside it.
+// Clean points carry their climb area as well (MIMC3_MX_AREA=0: the whole tile): the accumulator rows are banded (band_row below), one
+// iteration of the NCC finish is four consecutive tile rows, and the RecCfg form finishes only the bands that meet the area -- a clean
+// point whose climb leaves its area goes to the rest list as one whose climb leaves the tile does.
 // (The exhaustive search classifies in the clean form's header and hands on through the class byte alone: every one of its points
 // stays on this kernel's forms, which run behind in flag mode.)
 #include <hip/hip_runtime.h>
@@ -159,9 +162,15 @@ struct FullMultiSurfCfg : FullMultiCfg<OCW_, GEN_, CN_> {
 //   bm[c][lane]     : 0xff in the bytes of a chip-row B operand that hold chip pixels (the others are Toeplitz padding) -- the same bytes as hb
 //   hb[c][lane]     : B operand of the row-box sums -- byte i of chunk c <-> window column x = 16 w + 64 c + 16 h + i, cell column
 //                     s = 16 w + n:  1 if s <= x < s + CW  (the wave index cancels)
-//   vb[m][c][lane]  : A operand of the vertical sums -- cell row dy = 16 m + n; K slot (h, i) of chunk c <-> tile row
-//                     y = 64 c + 16 (i >> 2) + 4 h + (i & 3), where the accumulator layout of the row sums puts it (register i & 3 of row
-//                     tile 4 c + (i >> 2)):  1 if dy <= y < dy + CW
+//   vb[m][c][lane]  : A operand of the vertical sums -- cell row dy = 16 m + band_row(n), the banded row order of the product
+//                     accumulators (band_row below); K slot (h, i) of chunk c <-> tile row
+//                     y = 64 c + 16 (i >> 2) + 4 (i & 3) + h, where the accumulator layout of the row sums puts it (register i & 3 of row
+//                     tile 4 c + (i >> 2); the row sums read their A operand through the products' banded rows):  1 if dy <= y < dy + CW
+// Banded accumulator rows: MFMA row j of a 16 x 16 cell tile holds tile row 4 (j & 3) + (j >> 2), so that register i of lane (n, h) --
+// MFMA row 4 h + i -- is tile row 4 i + h: the four lane groups of register i cover the four CONSECUTIVE rows 4 i .. 4 i + 3, and one
+// iteration of the NCC finish is one band of four rows, which a whole wave can skip.  The A operand of the products and the ones-band
+// of the vertical box sums put their rows in this order; the surfaces in LDS stay in natural order
+constexpr int band_row(int j) { return 4 * (j & 3) + (j >> 2); }
 template <int CW, int KCW, int KCV>
 struct alignas(16) Bands {
     uint32_t hb[KCW][64][4], vb[2][KCV][64][4], bm[KCW][64][4];
@@ -176,7 +185,7 @@ struct alignas(16) Bands {
                 }
                 for (int m = 0; m < 2; m++)
                     for (int c = 0; c < KCV; c++) {
-                        const int dy = 16 * m + n, y = 64 * c + 16 * (i >> 2) + 4 * h + (i & 3);
+                        const int dy = 16 * m + band_row(n), y = 64 * c + 16 * (i >> 2) + 4 * (i & 3) + h;
                         if (dy <= y && y < dy + CW) vb[m][c][l][i >> 2] |= 1u << (8 * (i & 3));
                     }
             }
@@ -572,7 +581,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
 
     // lane (n, h) of wave w: cell column s = 16 w + n; byte i of K chunk c <-> window column 16 w + 64 c + 16 h + i
     const int n = lane & 15, h = lane >> 4;
-    const unsigned char *arow = WT + n * PW + 16 * wave + 16 * h;       // A operand: tile row r + 16 mt + n
+    const unsigned char *arow = WT + band_row(n) * PW + 16 * wave + 16 * h;      // A operand: tile row r + 16 mt + band_row(n)
     const int boff = CH0 + 16 * h - n;                                   // B operand: chip-row bytes 64 c + 16 h - n + i
     const uint32_t bsh = (uint32_t)boff & 3u;
     const unsigned char *brow = CH + (boff & ~3);
@@ -803,6 +812,12 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         }
     }
 
+    if constexpr (C::REC) {      // (formed here: left alone, the compiler sinks these sums into the finish's skippable bands and carries their byte planes there)
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) asm volatile("" : "+v"(boxb[m][i]), "+v"(boxq[m][i]));
+    }
     MIMC3_MX_STAMP(2)
     __syncthreads();                                        // the tile's bytes become the NCC surface
 
@@ -836,7 +851,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
             dn1 = (double)n1; dsx1 = (double)sx1; va1 = dn1 * (double)sxx1 - dsx1 * dsx1;
         }
         auto cell_in = [&](int m, int i, double &dn, double &dsx, double &va, int &sxy, int &sy, int &syy) __attribute__((always_inline)) {
-            const int ry = 16 * m + 4 * h + i;
+            const int ry = 16 * m + 4 * i + h;                  // (banded rows: band_row)
             sy = boxb[m][i]; syy = boxq[m][i];
             sxy = acc[m][i] + 128 * ((int)SXo + sy) - 16384 * NPX;          // (over all chip positions: a null is a zero factor)
             if (GEN && cn) {                                   // chip nulls take window pixels out of sy, syy
@@ -853,10 +868,20 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
                 dn = rowT4 ? dn1 : dn0; dsx = rowT4 ? dsx1 : dsx0; va = rowT4 ? va1 : va0;
             }
         };
+        // Iteration ci = 4 m + i finishes the band of tile rows 4 ci .. 4 ci + 3 of the wave's 16 columns.  REC: a climb reads no cell
+        // outside the record's climb area (the scans are confined to it, best-of-pivots reads end positions of scans, the fit reads
+        // visited cells), so the bands that miss its rows -- all eight in a wave whose columns miss it -- are left as the tile's bytes
+        uint32_t bands = 0xffu;
+        if constexpr (C::REC) {
+            const uint32_t ar = area_w >> 8, w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tix >> 6));
+            const uint32_t x0 = ar & 31u, x1 = (ar >> 5) & 31u, y0 = (ar >> 10) & 31u, y1 = (ar >> 15) & 31u;
+            bands = (w >= (x0 >> 4) && w <= (x1 >> 4)) ? ((2u << (y1 >> 2)) - (1u << (y0 >> 2))) & 0xffu : 0u;
+        }
         uint32_t amb = 0u;
 #pragma unroll
         for (int ci = 0; ci < 8; ci++) {
-            const int m = ci >> 2, i = ci & 3, ry = 16 * m + 4 * h + i;
+            if (C::REC && !((bands >> ci) & 1u)) continue;
+            const int m = ci >> 2, i = ci & 3, ry = 16 * m + 4 * i + h;
             double dn, dsx, va; int sxy, sy, syy;
             cell_in(m, i, dn, dsx, va, sxy, sy, syy);
             const double dsy = (double)sy;
@@ -871,8 +896,8 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         if (__any(amb != 0u)) {                            // rare (2^-15 of the cells): the reference's own operations
 #pragma unroll
             for (int ci = 0; ci < 8; ci++) {
-                if (!__any((amb >> ci) & 1u)) continue;
-                const int m = ci >> 2, i = ci & 3, ry = 16 * m + 4 * h + i;
+                if (!__any((amb >> ci) & 1u)) continue;        // (a skipped band has no bit)
+                const int m = ci >> 2, i = ci & 3, ry = 16 * m + 4 * i + h;
                 double dn, dsx, va; int sxy, sy, syy;
                 cell_in(m, i, dn, dsx, va, sxy, sy, syy);
                 const double dsy = (double)sy;
@@ -924,7 +949,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     // predicated: one wave-uniform loop, no divergent control flow (the compiler's exec-mask bookkeeping for a per-lane `while` was half
     // the loop's instructions).
     bool alive = lane < npiv && inside(su, sv);
-    bool left = false;                                       // a scan would leave the tile (REC: the record's area -- the whole tile for a clean point)
+    bool left = false;                                       // a scan would leave the tile (REC: the record's area)
     [[maybe_unused]] int axlo = 1, aylo = 1;
     [[maybe_unused]] uint32_t awx = 29u, awy = 29u;
     if constexpr (C::REC) mx_area_scan_bounds(area_w, axlo, awx, aylo, awy);
@@ -966,7 +991,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
 
     // ---- exact replay: the visited state only decides HOW MANY scans of a pivot really happen (newncc != 0, :699) -- sequential over
     //      pivots; lane r holds the visited bits of tile row r (match_px_kernel.hip, "exact replay", with 32-bit rows)
-    int T = 0;
+    uint32_t tp = 0u;                                        // lane k: pivot k's scans performed | the tile-relative cell it ended on << 8 (x), << 16 (y)
     uint32_t vrow = 0u;
     {
         const uint32_t head = (uint32_t)(relx(start_u) & 0xff) | ((uint32_t)(rely(start_v) & 0xff) << 8) | ((uint32_t)nsc << 16);
@@ -1000,26 +1025,24 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
                 if (fresh3 == 0ull) break;
                 if (d == 5u) break;
             }
-            T = (lane == kk) ? t : T;
+            // (the loop has stepped the centre past the t scans performed: where the pivot ended -- kept with t, so no lane decodes its codes again)
+            const uint32_t tpk = (uint32_t)t | ((uint32_t)ccx & 0xffu) << 8 | ((uint32_t)(cy1 + 1) & 0xffu) << 16;
+            tp = (lane == kk) ? tpk : tp;
         }
     }
+    const int T = (int)(tp & 0xffu);
     // a pivot whose speculation was cut at 16 scans and whose real climb consumed all of them: the register-tiled kernel decides
     if (__any(alive && T == nsc)) { hand_on(kMxRest); return; }
     if (lane < 32) vis[lane] = vrow;
     MIMC3_MX_STAMP(5)
 
     // ---- best of pivots (:744-752): after its last updating scan a pivot sits on the arg-max cell
-    int peak_u = dx2, peak_v = dy2;
+    int px = relx(dx2), py = rely(dy2);                      // the peak as a tile-relative cell
     float best = -2.0f;
     {
-        int fu = start_u, fv = start_v;
-        for (int t = 0; t < T; t++) {
-            const uint32_t d = ((t < 8 ? dlo : dhi) >> (4 * (t & 7))) & 15u;
-            fu += (int)(d & 3u) - 1; fv += (int)(d >> 2) - 1;
-        }
+        const int fx = (int)((tp >> 8) & 0xffu), fy = (int)(tp >> 16);           // (a pivot without a scan: not read)
         const bool upd = (updm & ((T >= 32 ? 0u : (1u << T)) - 1u)) != 0u;      // some scan among the T performed raised the maximum
-        const uint32_t fpos = ((uint32_t)fv << 16) | (uint32_t)fu;
-        const float fmax = upd ? val[rely(fv) * VP + relx(fu)] : -2.0f;
+        const float fmax = upd ? val[fy * VP + fx] : -2.0f;
         float bv = (lane < npiv) ? fmax : -__builtin_inff();
         int bi = lane;
         argmax_row16(bv, bi);
@@ -1032,23 +1055,27 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         bv = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bv)));
         bi = __builtin_amdgcn_readfirstlane(bi);
         if (bv > -2.0f) {                                    // strict >, first pivot attaining the maximum wins
-            const uint32_t pk = (uint32_t)__builtin_amdgcn_readlane((int)fpos, bi & 63);
-            peak_u = (int)(pk & 0xffffu); peak_v = (int)(pk >> 16); best = bv;
+            const uint32_t pk = (uint32_t)__builtin_amdgcn_readlane((int)tp, bi & 63);
+            px = (int)((pk >> 8) & 0xffu); py = (int)(pk >> 16); best = bv;
         }
     }
     __builtin_amdgcn_wave_barrier();                          // (one wave: its LDS operations are performed in order)
     // ---- 3x3 quadratic fit (:757-788), the reference's arithmetic value by value (match_px_kernel.hip) ------------------------------
+    // the nine cells: lane 3 r + c loads cell (px - 1 + c, py - 1 + r) and its visited bit -- clamped addresses and a select, no branch --
+    // and the values reach the fit's lanes by readlane
+    float n9[9];
+    {
+        const int j = lane < 9 ? lane : 0, r = (j * 11) >> 5, c = j - 3 * r;
+        const int x = px - 1 + c, y = py - 1 + r;
+        const bool in = (unsigned)x < 32u && (unsigned)y < 32u;                                  // (a cell outside the tile was never scanned)
+        const int xc = in ? x : 0, yc = in ? y : 0;
+        const uint32_t seen = (vis[yc] >> xc) & 1u;
+        const float cv = val[yc * VP + xc];
+        const float nv = (in && seen != 0u) ? cv : -2.0f;
+#pragma unroll
+        for (int k = 0; k < 9; k++) n9[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nv), k));
+    }
     if (lane < 5) {
-        float n9[9];
-        const int px = relx(peak_u), py = rely(peak_v);
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const int x = px - 1 + c, y = py - 1 + r;
-                const bool in = (unsigned)x < 32u && (unsigned)y < 32u;                          // (a cell outside the tile was never scanned)
-                n9[3 * r + c] = (in && ((vis[in ? y : 0] >> (x & 31)) & 1u)) ? val[y * VP + x] : -2.0f;
-            }
         const float e0 = 6 * n9[0] - 12 * n9[1] + 6 * n9[2] + 6 * n9[3] - 12 * n9[4] + 6 * n9[5] + 6 * n9[6] - 12 * n9[7] + 6 * n9[8];
         const float e1 = 9 * n9[0] - 9 * n9[2] - 9 * n9[6] + 9 * n9[8];
         const float e2 = 6 * n9[0] + 6 * n9[1] + 6 * n9[2] - 12 * n9[3] - 12 * n9[4] - 12 * n9[5] + 6 * n9[6] + 6 * n9[7] + 6 * n9[8];
@@ -1065,7 +1092,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         const float num = lane == 0 ? (float)(-2 * cp2 * cp3 + cp1 * cp4) : (float)(-2 * cp0 * cp4 + cp1 * cp3);
         const double det = 4 * cp0 * cp2 - cp1 * cp1;
         float o = (float)((double)num / det);
-        o += (float)(lane == 0 ? peak_u - dx2 : peak_v - dy2);
+        o += (float)(lane == 0 ? px + OCW + tx0 - dx2 : py + OCW + ty0 - dy2);
         if (lane < 2) p.out[3 * (size_t)gidx + lane] = o;
         if (lane == 0) p.out[3 * (size_t)gidx + 2] = best;
     }
@@ -1204,6 +1231,13 @@ bool u8_advance_on()
     return on != 0 && u8_point_records_on();
 }
 
+bool mx_area_on()
+{
+    // tuning / A-B: 0 = a clean point's area is the whole tile (every band finished, only a climb that leaves the tile handed on)
+    static const int on = getenv("MIMC3_MX_AREA") ? atoi(getenv("MIMC3_MX_AREA")) : 1;
+    return on != 0 && u8_advance_on();
+}
+
 bool u8_point_records_on()
 {
     static const int on = getenv("MIMC3_U8_RECS") ? atoi(getenv("MIMC3_U8_RECS")) : 1;      // tuning / A-B: 0 = the headers read memory, as without records
@@ -1234,7 +1268,7 @@ hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
     // there, and a point it hands on takes its record along to the rest list
     a.point_recs = nullptr; a.rest_recs = nullptr;
     if (u8_point_records_on()) { a.point_recs = u8_list_recs(lists, a.N); a.rest_recs = u8_list_recs(lists, a.N) + (size_t)a.N; }
-    hipError_t e = launch_u8_classify(a, lists, u8_advance_on(), stream);
+    hipError_t e = launch_u8_classify(a, lists, u8_advance_on(), mx_area_on(), stream);
     if (e == hipSuccess) e = mx::classify_stats(a, lists, stream);
     if (e == hipSuccess) e = a.point_recs ? launch_rec_form(a, stream) : launch_form<false, false>(a, stream);
     a.point_list = nullptr; a.point_count = nullptr; a.point_recs = nullptr;

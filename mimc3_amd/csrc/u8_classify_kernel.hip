@@ -15,6 +15,8 @@
 // A third list rides along: the advance list -- the REST-LIST POSITIONS of the rest points that mx_takes, whose chip is null-free and whose
 // window holds nulls, but none in the climb area (mx_climb_area, match_kernel.h: one more table query).  The matrix-core launch tries
 // them behind its clean list and marks those it finishes in their rest records; counted and ranked like the other two.
+// A clean point's record carries its climb area too (clean_area; no query, its window holds no null): the matrix-core kernel's clean
+// form finishes the NCC of the area's row bands alone.
 // No same-address atomic per point (100,000 of them serialise into a millisecond) and no spinning on another block: the order inside
 // both lists is the point order, whatever the order the blocks run in.
 #include <hip/hip_runtime.h>
@@ -29,7 +31,7 @@ namespace {
 constexpr int kClsThreads = 256, kClsWaves = kClsThreads / 64;
 
 // the point's class, and in `r` everything that was read and derived on the way: the header of the kernel that takes the point
-__device__ __forceinline__ uint8_t classify_point(const MatchU8Args &p, int g, U8PointRec &r, bool advance_on, bool &adv)
+__device__ __forceinline__ uint8_t classify_point(const MatchU8Args &p, int g, U8PointRec &r, bool advance_on, bool clean_area, bool &adv)
 {
     const int OCW = p.ocw, CW = 2 * OCW + 1, PAD = p.pad;
     typedef unsigned long long SatT;
@@ -64,6 +66,13 @@ __device__ __forceinline__ uint8_t classify_point(const MatchU8Args &p, int g, U
         int ab[4], ax, ay, aw, ah;
         mx_climb_area(lu, lv, OCW, dx2, dy2, csx, csy, tx0, ty0, ab, ax, ay, aw, ah);
         if (sat_nulls_u8_thread(sat_win, p.sat_ws, u0 + p.off_u - dx2 + PAD + ax, v0 + p.off_v - dy2 + PAD + ay, aw, ah) == 0) { adv = true; area = mx_area_pack(ab); }
+    }
+    // a clean point carries its climb area too (no query: its window holds no null): the clean form finishes the NCC of the area's row
+    // bands alone, and a climb that leaves the area goes to the rest list as one that leaves the tile does
+    if (clean_area && cls == 0) {
+        int ab[4], ax, ay, aw, ah;
+        mx_climb_area(lu, lv, OCW, dx2, dy2, csx, csy, tx0, ty0, ab, ax, ay, aw, ah);
+        area = mx_area_pack(ab);
     }
     r.g = g; r.u0 = u0; r.v0 = v0; r.lu = lu; r.lv = lv; r.npiv = (int32_t)((uint32_t)npiv | area); r.pbeg = pbeg;
     r.win_nulls = win_nulls; r.chipQ = chipQ; r.colQ = 0; r.rowQ = 0;
@@ -100,7 +109,7 @@ __device__ __forceinline__ int block_rank(bool on, int *wsum, int *before)
     return total;
 }
 
-__global__ __launch_bounds__(kClsThreads) void u8_classify_count(MatchU8Args p, int32_t *blk, U8PointRec *stage, uint8_t *advf)
+__global__ __launch_bounds__(kClsThreads) void u8_classify_count(MatchU8Args p, int32_t *blk, U8PointRec *stage, uint8_t *advf, bool clean_area)
 {
     __shared__ int wsum[kClsWaves];
     const int g = blockIdx.x * kClsThreads + threadIdx.x;
@@ -108,7 +117,7 @@ __global__ __launch_bounds__(kClsThreads) void u8_classify_count(MatchU8Args p, 
     bool adv = false;
     if (g < p.N) {
         U8PointRec r;
-        cls = classify_point(p, g, r, advf != nullptr, adv);
+        cls = classify_point(p, g, r, advf != nullptr, clean_area, adv);
         p.mx_flags[g] = cls;
         if (stage) rec_copy(stage + g, &r);
         if (advf) advf[g] = adv ? 1 : 0;
@@ -166,7 +175,7 @@ static inline size_t recs_offset_ints(int N) { return (kU8ListHead + 3 * (size_t
 size_t u8_lists_bytes(int N) { return sizeof(int32_t) * recs_offset_ints(N) + 3 * (size_t)N * sizeof(U8PointRec); }
 U8PointRec *u8_list_recs(int32_t *lists, int N) { return reinterpret_cast<U8PointRec *>(lists + recs_offset_ints(N)); }
 
-hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, bool advance, hipStream_t stream)
+hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, bool advance, bool clean_area, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
     if (!a.mx_flags || !a.sat0 || !a.sat1 || !a.ovf_count || !lists || !a.piv_uv || !a.piv_off) return hipErrorInvalidValue;
@@ -176,7 +185,7 @@ hipError_t launch_u8_classify(const MatchU8Args &a, int32_t *lists, bool advance
     // the advance list needs the records (the clean form reads an advance point's header from its rest record); null = the list is empty
     uint8_t *advf = (advance && stage) ? reinterpret_cast<uint8_t *>(blk + scratch_count_ints(a.N)) : nullptr;
     const unsigned nb = classify_blocks(a.N);
-    hipLaunchKernelGGL(u8_classify_count, dim3(nb), dim3(kClsThreads), 0, stream, a, blk, stage, advf);
+    hipLaunchKernelGGL(u8_classify_count, dim3(nb), dim3(kClsThreads), 0, stream, a, blk, stage, advf, clean_area && stage != nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(u8_classify_fill, dim3(nb), dim3(kClsThreads), 0, stream, a, static_cast<const int32_t *>(blk), lists, static_cast<const U8PointRec *>(stage),
