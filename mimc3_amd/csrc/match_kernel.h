@@ -106,6 +106,8 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     union { const uint32_t *rt0; struct U8PointRec *point_recs; };
     union { const uint32_t *rt1; struct U8PointRec *rest_recs; };
     int32_t rt_tw;                                  // tiles per plane row
+    int32_t replay_shortcut;                        // DLC kernels: the exact replay tries the winning pivot alone first (replay_shortcut_on;
+                                                    // filled by the launchers; in the four bytes the table pointers' alignment left unused)
     // packed summed-area tables of the two planes (sat_kernel.hip; policies with P::SAT), (Hp + 1) rows of sat_ws entries
     const void *sat0, *sat1;
     const void *satz0, *satz1;      // u16 planes: null counts (u32), same geometry
@@ -235,6 +237,11 @@ U8PointRec *u8_list_recs(int32_t *lists, int N);
 bool u8_point_records_on();        // (tuning / A-B: MIMC3_U8_RECS=0 keeps the memory headers)
 bool u8_advance_on();              // (tuning / A-B: MIMC3_U8_ADVANCE=0, or no records, leaves the advance list empty)
 bool mx_area_on();                 // (tuning / A-B: MIMC3_MX_AREA=0, or no advance list, gives clean points the whole tile as their area)
+// The exact replay of both DLC kernels first replays the winning pivot alone (match_mx_kernel.hip, "the shortcut"; match_px_kernel.hip's
+// fast register form); tests / A-B: MIMC3_REPLAY_SHORTCUT=0 forces the full replay.  What a point did, as the diagnostics count it
+// (MIMC3_MX_STATS, MIMC3_U8_STATS):
+bool replay_shortcut_on();
+constexpr uint32_t kReplayShort = 0u, kReplayShortU = 1u, kReplayFellBack = 2u, kReplayNoPre = 3u;   // taken with U empty / with U built, fell back, preconditions failed
 hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream);
 // (u8_classify_kernel.hip; wn_on / gen_on: which forms for null-ridden points run behind the clean form)
 // advance: also write the advance list (needs the records) -- else its length is 0; clean_area: clean points' records carry their

@@ -194,7 +194,7 @@ struct alignas(16) Bands {
 };
 template <int CW, int KCW, int KCV> __device__ const Bands<CW, KCW, KCV> kBands{};
 
-constexpr int kStatW = 8;
+constexpr int kStatW = 9;        // (slot 7: advance list, slot 8: replay-shortcut outcome + 1)
 
 // u8 pixels back from the signed bytes of an A operand, squared, split into the byte planes (x^2 & 255) and (x^2 >> 8), as signed bytes
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
@@ -955,8 +955,8 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     if constexpr (C::REC) mx_area_scan_bounds(area_w, axlo, awx, aylo, awy);
     uint32_t dlo = 0u, dhi = 0u, updm = 0u;
     int nsc = 0;
+    float smax = -2.0f;                                      // the running maximum after all recorded scans (-2: no scan raised it)
     {
-        float smax = -2.0f;
 #pragma unroll 1
         for (int t = 0; t < kSpecRounds; t++) {
             if (!__any(alive)) break;
@@ -993,53 +993,108 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     //      pivots; lane r holds the visited bits of tile row r (match_px_kernel.hip, "exact replay", with 32-bit rows)
     uint32_t tp = 0u;                                        // lane k: pivot k's scans performed | the tile-relative cell it ended on << 8 (x), << 16 (y)
     uint32_t vrow = 0u;
-    {
-        const uint32_t head = (uint32_t)(relx(start_u) & 0xff) | ((uint32_t)(rely(start_v) & 0xff) << 8) | ((uint32_t)nsc << 16);
-        for (int kk = 0; kk < npiv; kk++) {
-            const uint32_t hd = (uint32_t)__builtin_amdgcn_readlane((int)head, kk);
-            const int n_k = (int)(hd >> 16);
-            int ccx = (int)(hd & 0xffu), cy1 = (int)((hd >> 8) & 0xffu) - 1;      // centre column, centre row - 1 (tile-relative)
-            unsigned long long cur = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)dhi, kk) << 32) |
-                                     (uint32_t)__builtin_amdgcn_readlane((int)dlo, kk);
-            int t = 0;
-            while (t < n_k) {
-                // rows cy1 .. cy1 + 2 (= lanes) test and set their three bits; fresh3 = the lanes that held an unvisited one
-                unsigned long long fresh3, sv2;
-                uint32_t tmp;
-                const uint32_t m3 = 7u << (ccx - 1);
-                asm volatile("v_subrev_u32_e32 %[tmp], %[y], %[l1]\n\t"
-                             "v_cmp_gt_u32_e32 vcc, 3, %[tmp]\n\t"
-                             "s_and_saveexec_b64 %[sv], vcc\n\t"
-                             "v_bitop3_b32 %[tmp], %[m], %[v], %[m] bitop3:0x30\n\t"      // m3 & ~vrow
-                             "v_cmp_ne_u32_e32 vcc, 0, %[tmp]\n\t"
-                             "v_or_b32_e32 %[v], %[m], %[v]\n\t"
-                             "s_mov_b64 exec, %[sv]\n\t"
-                             "s_mov_b64 %[fr], vcc"
-                             : [tmp] "=&v"(tmp), [sv] "=&s"(sv2), [fr] "=s"(fresh3), [v] "+v"(vrow)
-                             : [y] "s"(cy1), [l1] "v"(lane), [m] "s"(m3)
-                             : "vcc", "scc");
-                t++;
-                const uint32_t d = (uint32_t)cur & 15u;
-                cur >>= 4;
-                ccx += (int)(d & 3u) - 1; cy1 += (int)(d >> 2) - 1;
-                if (fresh3 == 0ull) break;
-                if (d == 5u) break;
+    const uint32_t head = (uint32_t)(relx(start_u) & 0xff) | ((uint32_t)(rely(start_v) & 0xff) << 8) | ((uint32_t)nsc << 16);
+    auto replay_pivot = [&](int kk) __attribute__((always_inline)) -> uint32_t {
+        const uint32_t hd = (uint32_t)__builtin_amdgcn_readlane((int)head, kk);
+        const int n_k = (int)(hd >> 16);
+        int ccx = (int)(hd & 0xffu), cy1 = (int)((hd >> 8) & 0xffu) - 1;      // centre column, centre row - 1 (tile-relative)
+        unsigned long long cur = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)dhi, kk) << 32) |
+                                 (uint32_t)__builtin_amdgcn_readlane((int)dlo, kk);
+        int t = 0;
+        while (t < n_k) {
+            // rows cy1 .. cy1 + 2 (= lanes) test and set their three bits; fresh3 = the lanes that held an unvisited one
+            unsigned long long fresh3, sv2;
+            uint32_t tmp;
+            const uint32_t m3 = 7u << (ccx - 1);
+            asm volatile("v_subrev_u32_e32 %[tmp], %[y], %[l1]\n\t"
+                         "v_cmp_gt_u32_e32 vcc, 3, %[tmp]\n\t"
+                         "s_and_saveexec_b64 %[sv], vcc\n\t"
+                         "v_bitop3_b32 %[tmp], %[m], %[v], %[m] bitop3:0x30\n\t"      // m3 & ~vrow
+                         "v_cmp_ne_u32_e32 vcc, 0, %[tmp]\n\t"
+                         "v_or_b32_e32 %[v], %[m], %[v]\n\t"
+                         "s_mov_b64 exec, %[sv]\n\t"
+                         "s_mov_b64 %[fr], vcc"
+                         : [tmp] "=&v"(tmp), [sv] "=&s"(sv2), [fr] "=s"(fresh3), [v] "+v"(vrow)
+                         : [y] "s"(cy1), [l1] "v"(lane), [m] "s"(m3)
+                         : "vcc", "scc");
+            t++;
+            const uint32_t d = (uint32_t)cur & 15u;
+            cur >>= 4;
+            ccx += (int)(d & 3u) - 1; cy1 += (int)(d >> 2) - 1;
+            if (fresh3 == 0ull) break;
+            if (d == 5u) break;
+        }
+        // (the loop has stepped the centre past the t scans performed: where the pivot ended -- kept with t, so no lane decodes its codes again)
+        return (uint32_t)t | ((uint32_t)ccx & 0xffu) << 8 | ((uint32_t)(cy1 + 1) & 0xffu) << 16;
+    };
+    // ---- the shortcut: only three things are read behind the replay -- the pivot that wins best-of-pivots with its end cell and maximum,
+    //      the visited bits of the fit's nine cells, and T of a lane still alive at the cap.  With no lane alive and M* = max M_k > -2
+    //      (M_k = lane k's smax: pivot k's maximum if its real climb performed every recorded scan), let w be the first pivot with
+    //      M_w = M*.  Every real climb is a prefix of the recorded one, so the cells visited before pivot w are a subset of U, the 3 x 3
+    //      neighbourhoods of all recorded scans of the pivots before w; a smaller visited set cannot end a climb sooner.  So if w, replayed
+    //      alone from U, performs all its scans and its last one did not move, its real climb does too: it ends on the same cell with M*,
+    //      no earlier pivot reaches M* and no later one exceeds it (strict >, :747), and that last scan visited the fit's nine cells.
+    //      Otherwise the full replay runs from an empty visited set, as without the shortcut.  
+    int px = relx(dx2), py = rely(dy2);                      // the peak as a tile-relative cell
+    float best = -2.0f;
+    bool shortcut = false;
+    uint32_t outcome = kReplayNoPre;
+    if (p.replay_shortcut && !__any(alive)) {
+        float bv = smax;                                     // (a lane without a pivot never scanned: -2)
+        int bi = lane;
+        argmax_row16(bv, bi);
+#pragma unroll
+        for (int o = 16; o <= 32; o <<= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        bv = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bv)));
+        const int w = __builtin_amdgcn_readfirstlane(bi) & 63;
+        if (bv > -2.0f) {
+            const unsigned long long before = __ballot(nsc > 0) & ((1ull << w) - 1ull);      // the pivots in front of w that scan at all
+            if (before != 0ull) {                            // U: those lanes walk their deltas again, three row masks per scan
+                if (lane < 32) vis[lane] = 0u;
+                __builtin_amdgcn_wave_barrier();
+                if (lane < w) {
+                    int cx = relx(start_u), cy = rely(start_v);
+                    unsigned long long cur = ((unsigned long long)dhi << 32) | dlo;
+                    for (int t = 0; t < nsc; t++) {          // (every recorded scan lies inside the tile: cx, cy in 1 .. 30)
+                        const uint32_t m3 = 7u << (cx - 1);
+                        atomicOr(&vis[cy - 1], m3); atomicOr(&vis[cy], m3); atomicOr(&vis[cy + 1], m3);
+                        const uint32_t d = (uint32_t)cur & 15u;
+                        cur >>= 4;
+                        cx += (int)(d & 3u) - 1; cy += (int)(d >> 2) - 1;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                vrow = vis[lane & 31];
             }
-            // (the loop has stepped the centre past the t scans performed: where the pivot ended -- kept with t, so no lane decodes its codes again)
-            const uint32_t tpk = (uint32_t)t | ((uint32_t)ccx & 0xffu) << 8 | ((uint32_t)(cy1 + 1) & 0xffu) << 16;
-            tp = (lane == kk) ? tpk : tp;
+            const uint32_t tpw = replay_pivot(w);
+            const int n_w = __builtin_amdgcn_readlane(nsc, w);
+            const uint32_t lastw = (uint32_t)__builtin_amdgcn_readlane((int)(n_w > 8 ? dhi : dlo), w);
+            shortcut = (int)(tpw & 0xffu) == n_w && ((lastw >> (4 * ((n_w - 1) & 7))) & 15u) == 5u;
+            if (shortcut) { px = (int)((tpw >> 8) & 0xffu); py = (int)(tpw >> 16); best = bv; }
+            else vrow = 0u;
+            outcome = shortcut ? (before != 0ull ? kReplayShortU : kReplayShort) : kReplayFellBack;
         }
     }
-    const int T = (int)(tp & 0xffu);
-    // a pivot whose speculation was cut at 16 scans and whose real climb consumed all of them: the register-tiled kernel decides
-    if (__any(alive && T == nsc)) { hand_on(kMxRest); return; }
+    if (p.stats && lane == 0) p.stats[kStatW * (size_t)blockIdx.x + 8] = outcome + 1ull;
+    if (!shortcut) {
+        for (int kk = 0; kk < npiv; kk++) {
+            const uint32_t tpk = replay_pivot(kk);
+            tp = (lane == kk) ? tpk : tp;
+        }
+        const int T = (int)(tp & 0xffu);
+        // a pivot whose speculation was cut at 16 scans and whose real climb consumed all of them: the register-tiled kernel decides
+        if (__any(alive && T == nsc)) { hand_on(kMxRest); return; }
+    }
     if (lane < 32) vis[lane] = vrow;
     MIMC3_MX_STAMP(5)
 
     // ---- best of pivots (:744-752): after its last updating scan a pivot sits on the arg-max cell
-    int px = relx(dx2), py = rely(dy2);                      // the peak as a tile-relative cell
-    float best = -2.0f;
-    {
+    if (!shortcut) {
+        const int T = (int)(tp & 0xffu);
         const int fx = (int)((tp >> 8) & 0xffu), fy = (int)(tp >> 16);           // (a pivot without a scan: not read)
         const bool upd = (updm & ((T >= 32 ? 0u : (1u << T)) - 1u)) != 0u;      // some scan among the T performed raised the maximum
         const float fmax = upd ? val[fy * VP + fx] : -2.0f;
@@ -1136,10 +1191,12 @@ static hipError_t launch_one(MatchU8Args a, hipStream_t stream)
         unsigned long long hsum[kStatW] = {0};
         size_t live = 0;
         size_t adv_tried = 0, adv_done = 0;              // (slot 7: an advance-list workgroup's 1 = tried, 2 = finished; it writes no phase clocks)
+        size_t rs[4] = {0, 0, 0, 0};                     // (slot 8: the replay shortcut's outcome + 1 of a workgroup that reached the replay)
         for (size_t b = 0; b < (size_t)nb; b++) {
             if (hh[kStatW * b]) live++;
             for (int i = 0; i < 7; i++) hsum[i] += hh[kStatW * b + i];
             adv_tried += hh[kStatW * b + 7] != 0; adv_done += hh[kStatW * b + 7] == 2;
+            if (hh[kStatW * b + 8]) rs[(hh[kStatW * b + 8] - 1) & 3]++;
         }
         free(hh);
         const double d = live ? (double)live : 1.0;
@@ -1157,6 +1214,9 @@ static hipError_t launch_one(MatchU8Args a, hipStream_t stream)
             (void)hipMemcpy(&nadv, a.point_count + 2, sizeof(nadv), hipMemcpyDeviceToHost);
             fprintf(stderr, "[mimc3 mx stats] advance: list %d tried %zu finished %zu\n", nadv, adv_tried, adv_done);
         }
+        if (!C::FULL)
+            fprintf(stderr, "[mimc3 mx stats] replay shortcut: taken with U empty %zu, taken with U built %zu, fell back %zu, preconditions failed %zu\n",
+                    rs[kReplayShort], rs[kReplayShortU], rs[kReplayFellBack], rs[kReplayNoPre]);
     }
     return hipGetLastError();
 }
@@ -1261,6 +1321,7 @@ hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
     a.mx_wn_on = wn_env > 0 ? 1 : 0;
     a.mx_gen_on = gen_env != 0 ? 1 : 0;
     a.mx_classified = 1;
+    a.replay_shortcut = replay_shortcut_on() ? 1 : 0;
     a.point_flags = nullptr;
     a.point_count = lists; a.point_list = lists + kU8ListHead;
     a.rest_count = lists + 1; a.rest_list = lists + kU8ListHead + (size_t)a.N;

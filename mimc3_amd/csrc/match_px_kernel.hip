@@ -584,6 +584,12 @@ struct PxCfg {
     // instantiation: the plain configurations keep their register allocation.
     static constexpr bool MANYP = MANY_;
     static constexpr bool REC = false;                  // the header comes from u8_classify's point record (PxRec)
+    // The exact replay tries the winning pivot alone first ("The shortcut" in the kernel).  Its few extra live values cost nothing where
+    // registers are free, but every configuration that already spills at its register cap would spill 4 to 20 bytes more (tools/kres.py):
+    // on where the compiler's figures show no scratch gained and the same occupancy -- the 33-pixel chips of every policy but the
+    // non-integral f32 one (whose kernel spills), and the 15-pixel chips of the 8-bit policies and of non-integral f32.
+    static constexpr bool SHORTCUT = !MANY_ && ((OCW_ == 16 && !std::is_same<P_, PxF32>::value) ||
+                                                (OCW_ == 7 && (std::is_same<P_, PxU8>::value || std::is_same<P_, PxU8o>::value || std::is_same<P_, PxF32>::value)));
     // Tail tasks without masks (sparse-correction configs): a tail dword is all chip pixels except the LAST dword of a
     // chip row, whose pad bytes carry no pixel.  If no lane owns more than one such dword, the evaluation runs every tail
     // task with a full mask and takes the pad pixels of that one dword out again (one extra dword per lane and cell)
@@ -718,7 +724,7 @@ __device__ __forceinline__ AccT<typename C::P::Sum> eval_round(const unsigned ch
     return acc;
 }
 
-static constexpr int kStatW = 16;      // diagnostics: 8 phase clocks + cell counts (clean, dirty, evaluate calls) + null-list use
+static constexpr int kStatW = 20;      // diagnostics: 8 phase clocks + cell counts (clean, dirty, evaluate calls) + null-list use + the replay shortcut's four outcomes
 #ifndef MIMC3_SUM_BATCH
 #define MIMC3_SUM_BATCH 32
 #endif
@@ -1807,6 +1813,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
             //      :699) -- that part is sequential over pivots and is all that is done here.
             MIMC3_STAMP(5)
             int T = 0;                                   // lane k: number of scans pivot k really performs
+            bool shortcut = false;                       // the winning pivot alone was replayed: peak and best are set, no lane has a T
             const bool regmask = (pt.csx <= 64 && pt.csy <= 64);
             // visited set in REGISTERS when it fits: lane r holds the 64-bit column mask of compact row r;
             // a scan's 3x3 = 3 rows x 3 adjacent bits, tested/set with readlane + scalar ops (no LDS
@@ -1844,7 +1851,8 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
                     if (t < 8) dlo |= d << (4 * (t & 7)); else dhi |= d << (4 * (t & 7));
                 }
                 const uint32_t head = (uint32_t)(start_u - OCW) | ((uint32_t)(start_v - OCW) << 8) | ((uint32_t)nsc << 16);
-                for (int kk = 0; kk < npiv; kk++) {
+                // one pivot's real climb against the visited set: scans performed | the compact cell it ended on << 8 (x), << 16 (y)
+                auto replay_pivot = [&](int kk) __attribute__((always_inline)) -> uint32_t {
                     const uint32_t hd = (uint32_t)__builtin_amdgcn_readlane((int)head, kk);
                     const int n_k = (int)(hd >> 16);
                     int ccx = (int)(hd & 0xffu), cy1 = (int)((hd >> 8) & 0xffu) - 1;      // centre column, centre row - 1
@@ -1915,8 +1923,67 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
                         if (fresh3 == 0ull) break;
                         if (d == 5u) break;
                     }
-                    T = (lane == kk) ? t : T;
+                    return (uint32_t)t | ((uint32_t)ccx & 0xffu) << 8 | ((uint32_t)(cy1 + 1) & 0xffu) << 16;      // (the loop has stepped the centre past the scans performed)
+                };
+                // The shortcut (match_mx_kernel.hip, "the shortcut"): with no lane alive and M* = max smax > -2, the first
+                // pivot w with smax = M* is replayed alone from U, the 3 x 3 neighbourhoods of every recorded scan of the pivots before
+                // it.  If it performs all its scans and the last one did not move, it is the winner with M* on that cell, and its last
+                // scan has visited the fit's nine cells; otherwise the full replay runs from an empty visited set.
+                uint32_t outcome = kReplayNoPre;
+                if (C::SHORTCUT && regmask && p.replay_shortcut && !__any(alive)) {
+                    float bv = smax;                         // (a lane without a pivot never scanned: -2)
+                    int bi = lane;
+                    argmax_row16(bv, bi);
+#pragma unroll
+                    for (int o = 16; o <= 32; o <<= 1) {
+                        const float ov = __shfl_xor(bv, o, 64);
+                        const int oi = __shfl_xor(bi, o, 64);
+                        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+                    }
+                    bv = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bv)));
+                    const int w = __builtin_amdgcn_readfirstlane(bi) & 63;
+                    if (bv > -2.0f) {
+                        const unsigned long long before = __ballot(nsc > 0) & ((1ull << w) - 1ull);     // the pivots in front of w that scan at all
+                        if (before != 0ull) {                // U, through the (still empty) LDS bit rows: those lanes walk their deltas again
+                            if (lane < w) {
+                                int cx = start_u - OCW, cy = start_v - OCW;
+                                unsigned long long cur = ((unsigned long long)dhi << 32) | dlo;
+                                for (int t = 0; t < nsc; t++) {      // (a scan's centre lies in [1, cs - 2]: rows cy - 1 .. cy + 1 exist)
+                                    const unsigned long long m3 = 7ull << (cx - 1);
+#pragma unroll
+                                    for (int r = -1; r <= 1; r++) {
+                                        uint32_t *row = &vis[((cy + r) * vpitch) >> 5];
+                                        atomicOr(row, (uint32_t)m3);
+                                        if (vpitch > 32) atomicOr(row + 1, (uint32_t)(m3 >> 32));
+                                    }
+                                    const uint32_t d = (uint32_t)cur & 15u;
+                                    cur >>= 4;
+                                    cx += (int)(d & 3u) - 1; cy += (int)(d >> 2) - 1;
+                                }
+                            }
+                            __builtin_amdgcn_wave_barrier();
+                            if (lane < pt.csy) {             // ... and the bit rows are left empty again: the publish below, or the fallback, fills them
+                                uint32_t *row = &vis[(lane * vpitch) >> 5];
+                                vlo = row[0]; row[0] = 0u;
+                                if (vpitch > 32) { vhi = row[1]; row[1] = 0u; }
+                            }
+                            __builtin_amdgcn_wave_barrier();
+                        }
+                        const uint32_t tpw = replay_pivot(w);
+                        const int n_w = __builtin_amdgcn_readlane(nsc, w);
+                        const uint32_t lastw = (uint32_t)__builtin_amdgcn_readlane((int)(n_w > 8 ? dhi : dlo), w);
+                        shortcut = (int)(tpw & 0xffu) == n_w && ((lastw >> (4 * ((n_w - 1) & 7))) & 15u) == 5u;
+                        if (shortcut) { peak_u = (int)((tpw >> 8) & 0xffu) + OCW; peak_v = (int)(tpw >> 16) + OCW; best = bv; }
+                        else { vlo = 0u; vhi = 0u; }
+                        outcome = shortcut ? (before != 0ull ? kReplayShortU : kReplayShort) : kReplayFellBack;
+                    }
                 }
+                if (p.stats && tid == 0) p.stats[kStatW * (size_t)blockIdx.x + 16 + outcome] += 1;
+                if (!shortcut)
+                    for (int kk = 0; kk < npiv; kk++) {
+                        const uint32_t tpk = replay_pivot(kk);
+                        T = (lane == kk) ? (int)(tpk & 0xffu) : T;
+                    }
             } else
             for (int kk = 0; kk < npiv; kk++) {
                 unsigned long long tr;
@@ -1988,6 +2055,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
             MIMC3_STAMP(7)
             // lane k: where pivot k ended and with which maximum (:744-752): after the last updating scan
             // the pivot sits on the arg-max cell, so the running maximum is that cell's NCC
+            if (shortcut) return 1;
             int fu = start_u, fv = start_v;
             bool upd = false;
             for (int t = 0; t < T; t++) {
@@ -2310,6 +2378,7 @@ static hipError_t launch_cfg(MatchU8Args a, int max_abs_u, int max_abs_v, int ma
     // (long corridors on a big chip -- BASELINE C4: 33 pivots, ocw 32 -- lose with it too: 166.7 vs 165.6 ms)
     a.lookahead = look >= 0 ? look : ((kNoisy || (C::LPC >= 64 && max_npiv > 24)) ? 0 : 1);
     a.debug_stop = dbg;
+    a.replay_shortcut = replay_shortcut_on() ? 1 : 0;
     static unsigned long long *d_stats = nullptr;
     static const bool want_stats = getenv("MIMC3_U8_STATS") != nullptr;
     static size_t stats_n = 0;
@@ -2343,6 +2412,8 @@ static hipError_t launch_cfg(MatchU8Args a, int max_abs_u, int max_abs_v, int ma
         fprintf(stderr, "[mimc3 u8 stats] cells/point: clean-box %.1f dirty-box %.1f in %.1f evaluation batches; null lists in use %.3f of points, %.0f window / %.0f chip entries per point\n",
                 (double)h[8] / a.N, (double)h[9] / a.N, (double)h[10] / a.N, (double)h[11] / a.N, (double)h[12] / a.N, (double)h[13] / a.N);
         fprintf(stderr, "[mimc3 u8 stats] replay on pre-decoded scan centres: %.3f of points; dirty-list boxes without a null: %.2f per point\n", (double)h[14] / a.N, (double)h[15] / a.N);
+        fprintf(stderr, "[mimc3 u8 stats] replay shortcut: taken with U empty %llu, taken with U built %llu, fell back %llu, preconditions failed %llu\n",
+                h[16 + kReplayShort], h[16 + kReplayShortU], h[16 + kReplayFellBack], h[16 + kReplayNoPre]);
     }
     return hipGetLastError();
 }
@@ -2523,6 +2594,13 @@ hipError_t launch_range_tiles(const unsigned short *plane, int H, int W, int Wp,
 {
     hipLaunchKernelGGL(range_tiles, dim3((W + 127) / 128, (H + 127) / 128), dim3(256), 0, s, plane, H, W, Wp, pad, d_out2);
     return hipGetLastError();
+}
+
+bool replay_shortcut_on()
+{
+    // tests / A-B: 0 = the exact replay of both DLC kernels always runs over every pivot
+    static const int on = getenv("MIMC3_REPLAY_SHORTCUT") ? atoi(getenv("MIMC3_REPLAY_SHORTCUT")) : 1;
+    return on != 0;
 }
 
 bool match_u8_supported(int ocw, int max_reach_u, int max_reach_v)
