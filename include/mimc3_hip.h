@@ -765,12 +765,45 @@ int mimc3_stack_add_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32
  * lay, wsum -- is bit for bit the state after mimc3_stack_add, on every pixel class, and the two may be mixed freely.  A weighted
  * stack's wsum gets 1.0 per finite cell, as from mimc3_stack_add.  On a stack of R >= 16 the call IS mimc3_stack_add (the wide kernel),
  * byte for byte: a caller does not have to branch.  mimc3_ctx_last_path reports the kernel that ran (6 / 7 / 8 / 9; 10 beyond R 15).
- * Not covered: scaled layers through the class kernels, an accumulation fused into the search (the layer scratch round trip stays). */
+ * Not covered: scaled layers through the class kernels; the layer scratch round trip stays here (mimc3_stack_add_fused below fuses
+ * the accumulation into the run-time-ocw matrix-core searches). */
 int mimc3_stack_add_class(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap);
 /* Device-resident variant, under the contract of mimc3_stack_add_dev (a first call on a pair builds the planes and tables its kernel
  * reads on the context's own stream and waits for them first). */
 int mimc3_stack_add_class_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
                               void *stream);
+/* One layer from the resident pair at ANY chip half-width 1 <= ocw <= 80 and any stack radius, accumulated in the search's own tail.
+ *   Definition: the layer is mimc3_match_ncc_wide_planes(mode 0, npeaks 0, shift = the stack's, R = the stack's, surf) on the resident
+ *   pair (at R <= 15 that is mimc3_match_ncc_full_chip_planes), added as mimc3_stack_add_surfaces adds it with the refused points taken
+ *   from the record (status -3).  The stack's state afterwards -- sum, cnt, lay, wsum -- is bit for bit the state after that two-call
+ *   chain; at the six chip sizes 7, 15, 16, 30, 32, 40 it is the state after mimc3_stack_add / mimc3_stack_add_class as well, and all
+ *   the adds may be mixed freely.  A weighted stack's wsum gets 1.0 per finite cell.
+ *   Which kernel runs (mimc3_ctx_last_path reports it after every add):
+ *     8-bit pair       12 ("u8_mfma_chip") at R <= 15, 14 ("u8_mfma_wide") at 16 <= R <= 47, at every ocw 1..80, the six included --
+ *                      the ACCUMULATING forms of the run-time-ocw matrix-core kernels: every workgroup adds the finished surface of its
+ *                      point into the stack from LDS (one lane owns a cell: plain read-modify-writes), no tail runs, and no record,
+ *                      candidate or surface is written.  One launch pair over all N points: no layer scratch, no record scratch, no chunks.
+ *     scaled-integer   13 ("u16_mfma_chip") at R <= 15, 15 ("u16_mfma_wide") up to mimc3_wide_planes_max_radius(ocw), the same way
+ *                      (12-bit DN, the pair after mimc3_ctx_filter_images).
+ *     any other pair   (16-bit DN, floats) not fused: the kernel mimc3_match_ncc_wide_planes(mode 0, surf) runs (8 / 9 at the six and
+ *                      11 elsewhere up to R 15, 10 beyond at the six) through the layer scratch and the accumulation of mimc3_stack_add in
+ *                      chunks of mimc3_stack_chunk(R); where no kernel takes (ocw, R) the call is refused.
+ *   mimc3_stack_fused_max_radius(ctx, ocw): the largest stack radius this entry takes for the resident pair's class at that ocw -- 47
+ *   on an 8-bit pair, mimc3_wide_planes_max_radius(ocw) on a scaled-integer one, else 15, or mimc3_wide_max_radius(ocw) at the six; 0
+ *   for an ocw outside 1..80, without images and on a chip-atlas context.  (On a pair that is neither 8-bit nor scaled-integer the
+ *   first query builds the pair's f32 planes, as a search would.)
+ *   Refusals, all before anything is allocated, enqueued or counted (the stack and mimc3_stack_info stay as they were): ocw outside
+ *   1..80, a null pointer, N <= 0: MIMC3_EINVAL; no images, a chip-atlas context: MIMC3_ESTATE; the stack's own, as every add words them
+ *   (no stack, 65,535 layers: MIMC3_ESTATE; N differs: MIMC3_EINVAL); a stack radius beyond mimc3_stack_fused_max_radius(ctx, ocw):
+ *   MIMC3_EINVAL, with the limit in the message; the host entry: a chip that leaves the image, a search box that leaves the zero border:
+ *   MIMC3_EBOUNDS.
+ *   Not covered: scaled layers (mimc3_stack_add_scaled) through these kernels, the pyramids, several GPUs, 16-bit kernels at other chip sizes. */
+int mimc3_stack_add_fused(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap);
+/* Device-resident variant, under the contract of mimc3_stack_add_dev: a point that breaks the host entry's bounds adds no cell and
+ * counts as a layer (a first call on a pair builds the planes and tables its kernel reads on the context's own stream and waits for them). */
+int mimc3_stack_add_fused_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
+                              void *stream);
+int32_t mimc3_stack_fused_max_radius(mimc3_ctx *ctx, int32_t ocw);
 /* One layer from the caller's surfaces -- of another context, of a later kernel, crafted: surf [N][S^2] in k order, refused [N]
  * (not 0 = refused) or NULL (no point is).  Refusals: the stack's, as above. */
 int mimc3_stack_add_surfaces(mimc3_ctx *ctx, const float *surf /*host [N][S^2]*/, const uint8_t *refused /*host [N] or NULL*/, int32_t N);

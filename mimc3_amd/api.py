@@ -105,6 +105,10 @@ _lib.mimc3_stack_add.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_in
 _lib.mimc3_stack_add_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
 _lib.mimc3_stack_add_class.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32]
 _lib.mimc3_stack_add_class_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
+_lib.mimc3_stack_add_fused.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32]
+_lib.mimc3_stack_add_fused_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
+_lib.mimc3_stack_fused_max_radius.argtypes = [_vp, C.c_int32]
+_lib.mimc3_stack_fused_max_radius.restype = C.c_int32
 _lib.mimc3_stack_add_surfaces.argtypes = [_vp, _f32p, _vp, C.c_int32]
 _lib.mimc3_stack_add_surfaces_dev.argtypes = [_vp, _vp, _vp, C.c_int32, _vp]
 _lib.mimc3_stack_finish.argtypes = [_vp, C.c_int32, C.c_int32, _f32p, _vp, _vp, _vp]
@@ -902,6 +906,29 @@ class Context:
         """Device-pointer variant (enqueue only)."""
         _check(_lib.mimc3_stack_add_class_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), ocw, 1 if swap else 0, stream),
                "stack_add_class_dev")
+
+    def stack_add_fused(self, xyuvav, offset, ocw, swap=False):
+        """One layer from the resident pair at any chip half-width 1..80 and any stack radius up to stack_fused_max_radius(ocw)
+        (mimc3_stack_add_fused): the layer is match_ncc_wide_planes(mode=0, surface=True) with the stack's shift and radius, added as
+        stack_add_surfaces adds it -- the stack afterwards is bit for bit that chain's, and stack_add's at the six chip sizes.  An 8-bit
+        or scaled-integer pair runs the accumulating forms of the run-time-ocw matrix-core kernels ("u8_mfma_chip" / "u8_mfma_wide",
+        "u16_mfma_chip" / "u16_mfma_wide"): one launch pair over all points that adds every surface into the stack from LDS, with no
+        layer scratch and no chunks; any other pair goes through the layer scratch on the kernel that entry runs.  last_path() reports
+        the kernel."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        _check(_lib.mimc3_stack_add_fused(self._h, xy, xy.shape[0], np.ascontiguousarray(offset, np.int32), ocw, 1 if swap else 0),
+               "stack_add_fused")
+
+    def stack_add_fused_dev(self, d_xyuvav, n, offset, ocw, stream=0, swap=False):
+        """Device-pointer variant (enqueue only)."""
+        _check(_lib.mimc3_stack_add_fused_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), ocw, 1 if swap else 0, stream),
+               "stack_add_fused_dev")
+
+    def stack_fused_max_radius(self, ocw):
+        """The largest stack radius stack_add_fused takes for the resident pair's class at this ocw: 47 on an 8-bit pair,
+        wide_planes_max_radius(ocw) on a scaled-integer one, else 15, or wide_max_radius(ocw) at the six chip sizes; 0 for an ocw
+        outside 1..80 or without a pair."""
+        return int(_lib.mimc3_stack_fused_max_radius(self._h, int(ocw)))
 
     def stack_add_surfaces(self, surf, refused=None):
         """One layer from the caller's surfaces float32[n][(2 radius + 1)^2] in k order; refused bool[n] (None = no point is)."""

@@ -164,6 +164,11 @@ struct SearchCall {
     float *d_out, *d_cand, *d_surf, *d_fb;
     int32_t *d_peak;                    // pyramid levels: every point's arg-max cell
     hipStream_t stream;
+    // a fused stack layer (mimc3_stack_add_fused on the four run-time-ocw matrix-core kernels): the stack's planes from the call's first
+    // point on -- the kernel runs its accumulating forms and writes nothing else (d_out, d_cand, d_surf null); null = an ordinary search
+    double *stk_sum;
+    uint16_t *stk_cnt, *stk_lay;
+    double *stk_wsum;                   // a weighted stack's, or null
 };
 enum PairClass { kU8, kScaledInt, kIntegralF32, kFloat };             // a pair's class; an entry takes every class up to its rules' widest
 enum CandRule { kCandAbsent, kCandOptional, kCandMandatory };
@@ -200,6 +205,8 @@ struct PlaneSet {
     double scale0, scale1;
 };
 bool full_ocw_ok(int32_t ocw);
+// the resident pair's class; that of a pair which is neither 8-bit nor scaled-integer needs its f32 planes: built on first use (drains the stream)
+int pair_class(mimc3_ctx *c, PairClass &cls);
 int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules);
 // host entries, after search_check: every chip inside the image, then every search box of half-width R + ocw around uv0 + offset + shift
 // inside the planes' zero border (host copies; shift null = zero)

@@ -37,6 +37,7 @@
 #include "match_kernel.h"
 #include "sat_kernel.h"
 #include "match_full_tail.h"
+#include "stack_acc.h"
 
 namespace mimc3 {
 
@@ -112,6 +113,15 @@ struct Cfg {                                        // (VP, PEAK, MULTI: what ma
     // occupancy target, waves per SIMD: the most that leaves the kernel without scratch (at 6 the clean form of the small chips spills,
     // at 4 the masked one), never above what LDS admits at the smallest chip of the class anyway (16, 7, 2 workgroups per CU)
     static constexpr int MINW = KCW_ == 1 ? (GEN_ ? 3 : 5) : KCW_ == 2 ? (GEN_ ? 2 : 3) : 1;
+    static constexpr bool ACC = false;              // (the accumulating forms: AccCfg below)
+};
+// The accumulating (ACC) forms, a third output beside the record and SURF forms: the finished surface is added into the stack where
+// the SURF form stores it (stack_acc.h) and no tail runs -- no record, candidate or surface is written.  Configurations of their own, so
+// that the names, registers and code of every Cfg instantiation stay what they were; the occupancy targets are the record forms'
+// (the accumulation runs after the cell registers are dead: no scratch at any of them, tools/kres.py)
+template <int KCW_, bool GEN_>
+struct AccCfg : Cfg<KCW_, GEN_, false, false> {
+    static constexpr bool ACC = true;
 };
 
 __device__ __forceinline__ uint32_t alignb(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
@@ -233,6 +243,7 @@ __global__ __launch_bounds__(kNT, C::MINW) void match_ncc_full_chip_u8(MatchU8Ar
     const int Wp = p.Wp, PAD = p.pad;
     // a point that leaves before its surface exists: the record (NaN or a status), every candidate slot, an all-NaN surface
     auto no_record = [&](float status) __attribute__((always_inline)) {
+        if constexpr (C::ACC) { mx::stack_acc_none(p, gidx, tid, status); return; }       // (no cell; the layer counts unless refused)
         if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_cand_fill<C>(p, gidx, status); }
         if constexpr (C::SURF) {
             float *sf = p.full_surf + (size_t)gidx * (size_t)NC;
@@ -587,6 +598,10 @@ __global__ __launch_bounds__(kNT, C::MINW) void match_ncc_full_chip_u8(MatchU8Ar
         }
     }
     __syncthreads();
+    if constexpr (C::ACC) {                                 // the surface into the stack, in the SURF store's place; no tail
+        mx::stack_acc<NT, VP>(p, val, gidx, S, tid);
+        return;
+    }
     if constexpr (C::SURF) {                                // the surface in k order (u outer): coalesced stores, LDS reads at stride VP
         float *sf = p.full_surf + (size_t)gidx * (size_t)NC;
         for (int k = tid; k < NC; k += NT) {
@@ -624,6 +639,27 @@ static hipError_t launch_kcw(const MatchU8Args &a, hipStream_t stream)
     }
 }
 
+template <bool GEN>
+static hipError_t launch_kcw_acc(const MatchU8Args &a, hipStream_t stream)
+{
+    switch (chip_u8_layout(a.ocw).KCW) {
+    case 1: return launch_one<AccCfg<1, GEN>>(a, stream);
+    case 2: return launch_one<AccCfg<2, GEN>>(a, stream);
+    case 3: return launch_one<AccCfg<3, GEN>>(a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// the accumulating forms: the same two launches, the clean form's hand-over of flagged points unchanged
+static hipError_t launch_forms_acc(MatchU8Args a, int forms, hipStream_t stream)
+{
+    hipError_t e = hipSuccess;
+    if (forms & 1) e = launch_kcw_acc<false>(a, stream);
+    a.point_flags = a.mx_flags; a.flag_value = kMxNulls;
+    if (e == hipSuccess && (forms & 2)) e = launch_kcw_acc<true>(a, stream);
+    return e;
+}
+
 // the clean form over all points, then the masked form in flag mode over the points it flagged
 template <bool MULTI, bool SURF>
 static hipError_t launch_forms(MatchU8Args a, int forms, hipStream_t stream)
@@ -651,6 +687,10 @@ hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t strea
     if (!a.p0 || !a.p1 || !a.mx_flags || !a.sat0 || !a.sat1 || a.full_peak || a.full_R < 1 || a.full_R > 15 || a.ocw < 1 || a.ocw > kFullChipMaxOcw)
         return hipErrorInvalidValue;
     a.point_flags = nullptr;
+    if (forms & kFormsAcc) {            // the stack's planes in the list-mode slots; nothing else is written
+        if (!a.stk_sum || !a.stk_cnt || !a.stk_lay || a.out || a.full_cand || a.full_surf) return hipErrorInvalidValue;
+        return fchip8::launch_forms_acc(a, forms, stream);
+    }
     if (a.full_cand) {
         if (a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks) return hipErrorInvalidValue;
         return a.full_surf ? fchip8::launch_forms<true, true>(a, forms, stream) : fchip8::launch_forms<true, false>(a, forms, stream);

@@ -76,12 +76,17 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
         int32_t *ovf_count;
         float *full_surf;           // exhaustive search, optional: f32 [N][(2 full_R + 1)^2], every point's surface in k order; null = none
     };
-    const int32_t *point_list, *point_count;   // list mode: workgroup b handles point_list[b], b < *point_count (nullptr = all N points)
+    // list mode: workgroup b handles point_list[b], b < *point_count (nullptr = all N points).
+    // (The accumulating forms of the run-time-ocw matrix-core searches, stack_acc.h: the stack's planes from the launch's first point on --
+    //  sum f64 [N][S^2], cnt u16 [N][S^2], lay u16 [N], wsum f64 [N][S^2] or null.  Those kernels have neither list mode nor a fail or
+    //  rest list, so the four pointers share these slots; the launchers read them only when `forms` asks for the accumulating forms)
+    union { const int32_t *point_list; double *stk_sum; };
+    union { const int32_t *point_count; uint16_t *stk_cnt; };
     // PxU8o: points whose chip or window does not fit a local 8-bit range.  Matrix-core DLC kernel behind u8_classify: the rest list --
     // a point the kernel meets but does not take (a climb that leaves the tile or outlasts the recorded scans: a few dozen per launch)
     // is appended with one atomicAdd, and the register-tiled kernel runs over that list right behind
-    union { int32_t *fail_list; int32_t *rest_list; };
-    union { int32_t *fail_count; int32_t *rest_count; };
+    union { int32_t *fail_list; int32_t *rest_list; uint16_t *stk_lay; };
+    union { int32_t *fail_count; int32_t *rest_count; double *stk_wsum; };
     // matrix-core kernel (match_mx_kernel.hip): one class byte per grid point -- 0 = its clean form takes the point, kMxWn / kMxNulls =
     // its window-null / general form does, kMxRest = none does.  The DLC path gets every byte from u8_classify (u8_classify_kernel.hip)
     // before the first launch; the exhaustive search zeroes them and lets the clean form classify (plain stores: a shared list counter
@@ -286,8 +291,12 @@ hipError_t launch_match_full_chip(MatchU8Args a, float *surf, hipStream_t stream
 // mimc3_match_ncc_full_chip_class): a.p0 / a.p1 the u8 planes, a.sat0 / a.sat1 their packed tables, a.mx_flags N class bytes, zero before
 // the call; a.full_shift, a.full_R, a.full_cand / a.full_npeaks, a.full_surf and a.out as launch_match_full_mx takes them, no a.full_peak.
 // forms: bit 0 the clean form over all points (it flags the points that hold a null), bit 1 the masked form over the flagged points --
-// 3 is the search, 1 and 2 are for timing the forms apart.  full_chip_u8_layout: K chunks per chip row, 16-row tiles and K chunks of the
+// 3 is the search, 1 and 2 are for timing the forms apart.  Bit 2 (kFormsAcc, with any of the above; this kernel and the three below)
+// selects the ACCUMULATING forms (stack_acc.h): each point's finished surface is added into the stack at a.stk_sum / a.stk_cnt / a.stk_lay
+// (/ a.stk_wsum) in the tail's place -- no record, candidate or surface is written, so a.out, a.full_cand and a.full_surf must be null.
+// full_chip_u8_layout: K chunks per chip row, 16-row tiles and K chunks of the
 // box sums, dynamic LDS bytes of a launch at this ocw (false outside 1 .. kFullChipMaxOcw)
+constexpr int kFormsAcc = 4;
 bool full_chip_u8_layout(int ocw, int out[4]);
 hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t stream);
 // ... and on the u16 planes of a SCALED-INTEGER pair (q < 4096; match_full_chip_u16_kernel.hip; mimc3_match_ncc_full_chip_planes): a.p0 / a.p1

@@ -35,6 +35,7 @@
 #include "match_kernel.h"
 #include "sat_kernel.h"
 #include "match_full_tail.h"
+#include "stack_acc.h"
 #include "match_wide_tail.h"
 
 namespace mimc3 {
@@ -153,6 +154,15 @@ struct Cfg {                                        // (VP, NT, PEAK, MULTI: wha
     static constexpr bool GEN = GEN_, PEAK = false, MULTI = MULTI_, SURF = SURF_;
     // occupancy target, waves per SIMD: the most that leaves the kernel without scratch (tools/kres.py, profiles/full_search_wide_u16/kres.txt)
     static constexpr int MINW = GEN_ ? (KCW_ == 1 ? 2 : 1) : (KCW_ == 1 ? 3 : KCW_ == 2 ? 2 : 1);
+    static constexpr bool ACC = false;              // (the accumulating forms: AccCfg below)
+};
+// The accumulating (ACC) forms, a third output beside the record and SURF forms: the finished surface is added into the stack where
+// the SURF form stores it (stack_acc.h) and no tail runs -- no record, candidate or surface is written.  Configurations of their own, so
+// that the names, registers and code of every Cfg instantiation stay what they were; the occupancy targets are the record forms'
+// (the accumulation runs after the cell registers are dead: no scratch at any of them, tools/kres.py)
+template <int KCW_, bool GEN_>
+struct AccCfg : Cfg<KCW_, GEN_, false, false> {
+    static constexpr bool ACC = true;
 };
 
 __device__ __forceinline__ uint32_t alignb(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
@@ -281,6 +291,7 @@ __global__ __launch_bounds__(kNT, C::MINW) void match_ncc_wide_u16(MatchU8Args p
     const int Wp = p.Wp, PAD = p.pad;
     // a point that leaves before its surface exists: the record (NaN or a status), every candidate slot, an all-NaN surface
     auto no_record = [&](float status) __attribute__((always_inline)) {
+        if constexpr (C::ACC) { mx::stack_acc_none(p, gidx, tid, status); return; }       // (no cell; the layer counts unless refused)
         if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_cand_fill<C>(p, gidx, status); }
         if constexpr (C::SURF) {
             float *sf = p.full_surf + (size_t)gidx * (size_t)NC;
@@ -682,6 +693,10 @@ __global__ __launch_bounds__(kNT, C::MINW) void match_ncc_wide_u16(MatchU8Args p
         }
     }
     __syncthreads();                                        // the surface is complete; the tiles' bytes are dead
+    if constexpr (C::ACC) {                                 // the surface into the stack, in the SURF store's place; no tail
+        mx::stack_acc<NT, VP>(p, val, gidx, S, tid);
+        return;
+    }
     if constexpr (C::SURF) {                                // the surface in k order (u outer): coalesced stores, LDS reads at stride VP
         float *sf = p.full_surf + (size_t)gidx * (size_t)NC;
         for (int k = tid; k < NC; k += NT) {
@@ -724,6 +739,27 @@ static hipError_t launch_kcw(const MatchU8Args &a, hipStream_t stream)
     }
 }
 
+template <bool GEN>
+static hipError_t launch_kcw_acc(const MatchU8Args &a, hipStream_t stream)
+{
+    switch (wide_u16_layout(a.ocw, a.full_R).KCW) {
+    case 1: return launch_one<AccCfg<1, GEN>>(a, stream);
+    case 2: return launch_one<AccCfg<2, GEN>>(a, stream);
+    case 3: return launch_one<AccCfg<3, GEN>>(a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// the accumulating forms: the same two launches, the clean form's hand-over of flagged points unchanged
+static hipError_t launch_forms_acc(MatchU8Args a, int forms, hipStream_t stream)
+{
+    hipError_t e = hipSuccess;
+    if (forms & 1) e = launch_kcw_acc<false>(a, stream);
+    a.point_flags = a.mx_flags; a.flag_value = kMxNulls;
+    if (e == hipSuccess && (forms & 2)) e = launch_kcw_acc<true>(a, stream);
+    return e;
+}
+
 // the clean form over all points, then the masked form in flag mode over the points it flagged
 template <bool MULTI, bool SURF>
 static hipError_t launch_forms(MatchU8Args a, int forms, hipStream_t stream)
@@ -754,6 +790,10 @@ hipError_t launch_match_wide_u16(MatchU8Args a, int forms, hipStream_t stream)
         a.full_R < wide16::kRMin || a.full_R > wide16::max_radius(a.ocw) || (a.Wp & 3))
         return hipErrorInvalidValue;
     a.point_flags = nullptr;
+    if (forms & kFormsAcc) {            // the stack's planes in the list-mode slots; nothing else is written
+        if (!a.stk_sum || !a.stk_cnt || !a.stk_lay || a.out || a.full_cand || a.full_surf) return hipErrorInvalidValue;
+        return wide16::launch_forms_acc(a, forms, stream);
+    }
     if (a.full_cand) {
         if (a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks) return hipErrorInvalidValue;
         return a.full_surf ? wide16::launch_forms<true, true>(a, forms, stream) : wide16::launch_forms<true, false>(a, forms, stream);

@@ -17,7 +17,7 @@ bool full_ocw_ok(int32_t ocw) { return ocw == 7 || ocw == 15 || ocw == 16 || ocw
 static bool wide_float_takes(int32_t ocw, int32_t R) { return full_ocw_ok(ocw) && R <= wide_max_radius(ocw); }
 
 // the pair's class; that of a pair which is neither 8-bit nor scaled-integer needs its f32 planes: built here on first use (drains the stream)
-static int pair_class(mimc3_ctx *c, PairClass &cls)
+int pair_class(mimc3_ctx *c, PairClass &cls)
 {
     cls = c->u8_ok ? kU8 : kScaledInt;
     if (c->u8_ok || c->u16_ok) return 0;
@@ -301,6 +301,13 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
     if (pl.sat0) { u.sat0 = pl.sat0; u.sat1 = pl.sat1; u.satz0 = pl.satz0; u.satz1 = pl.satz1; u.sat_ws = sat_pitch(pl.Wp); }
     u.scale0 = pl.scale0; u.scale1 = pl.scale1;
     const bool flags = kernel == Mx || kernel == ChipU8 || kernel == ChipU16 || kernel == WideU8 || kernel == WideU16;
+    // a fused stack layer: the accumulating forms of the four run-time-ocw matrix-core kernels (no other kernel has them)
+    const int acc = call.stk_sum ? kFormsAcc : 0;
+    if (acc) {
+        if (kernel != ChipU8 && kernel != ChipU16 && kernel != WideU8 && kernel != WideU16)
+            return fail(MIMC3_EUNSUPPORTED, std::string(call.entry) + ": this kernel has no accumulating form");
+        u.stk_sum = call.stk_sum; u.stk_cnt = call.stk_cnt; u.stk_lay = call.stk_lay; u.stk_wsum = call.stk_wsum;
+    }
     if (flags) HIP_TRY(c->mxl[0].reserve((size_t)call.N));             // one class byte per point, zero before the launch
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     hipError_t e;
@@ -314,25 +321,25 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
         // (over no point: nothing has flagged one); read at every call, so that one process can time the forms apart
         const char *fe = getenv("MIMC3_CHIP_U8_FORMS");
         const int forms = fe ? atoi(fe) & 3 : 3;
-        e = launch_match_full_chip_u8(u, forms ? forms : 3, s);
+        e = launch_match_full_chip_u8(u, (forms ? forms : 3) | acc, s);
     } else if (kernel == ChipU16) {
         // (MIMC3_CHIP_U16_FORMS: the same measurement-only switch for this kernel's two forms -- tools/full_chip_u16_time.py times the clean
         //  form with it; DESIGN 4.1r names it.  With 1 the flagged points get no result: never set it around a real search)
         const char *fe = getenv("MIMC3_CHIP_U16_FORMS");
         const int forms = fe ? atoi(fe) & 3 : 3;
-        e = launch_match_full_chip_u16(u, forms ? forms : 3, s);
+        e = launch_match_full_chip_u16(u, (forms ? forms : 3) | acc, s);
     } else if (kernel == WideU8) {
         // (MIMC3_WIDE_U8_FORMS: the same measurement-only switch for this kernel's two forms -- tools/wide_u8_time.py times the clean form
         //  with it; DESIGN 4.1s names it.  With 1 the flagged points get no result: never set it around a real search)
         const char *fe = getenv("MIMC3_WIDE_U8_FORMS");
         const int forms = fe ? atoi(fe) & 3 : 3;
-        e = launch_match_wide_u8(u, forms ? forms : 3, s);
+        e = launch_match_wide_u8(u, (forms ? forms : 3) | acc, s);
     } else if (kernel == WideU16) {
         // (MIMC3_WIDE_U16_FORMS: the same measurement-only switch for this kernel's two forms -- tools/wide_u16_time.py times the clean form
         //  with it; DESIGN 4.1t names it.  With 1 the flagged points get no result: never set it around a real search)
         const char *fe = getenv("MIMC3_WIDE_U16_FORMS");
         const int forms = fe ? atoi(fe) & 3 : 3;
-        e = launch_match_wide_u16(u, forms ? forms : 3, s);
+        e = launch_match_wide_u16(u, (forms ? forms : 3) | acc, s);
     } else if (kernel == U16) e = launch_match_full_u16(u, s);
     else if (kernel == F32i) e = launch_match_full_f32(u, s);
     else if (kernel == F32g) e = launch_match_full_f32g(u, call.d_surf, s);

@@ -3,7 +3,9 @@
 // pair's class), or a caller's array -- accumulated per cell in f64, and the tail
 // of the exhaustive search over their mean.  The stack is state of the context that the image setters do not touch.  Every entry
 // validates everything before its first launch.  A layer from the resident pair is a search of the exhaustive-search family: checked,
-// selected and launched through that layer's functions (search.cpp).
+// selected and launched through that layer's functions (search.cpp).  mimc3_stack_add_fused takes a layer at any chip size and radius: on an
+// 8-bit or scaled-integer pair the run-time-ocw matrix-core search adds every surface into the stack itself (its accumulating forms,
+// stack_acc.h: no layer scratch); any other pair goes through the layer scratch as above.
 #include <cmath>
 #include <cstring>
 #include "ctx_internal.h"
@@ -125,26 +127,22 @@ static SearchCall layer_call(const char *entry, const double *d_xyuvav, int32_t 
     return SearchCall{entry, false, d_xyuvav, 6, 2, n, off_u, off_v, d_shift, ocw, R, 0, swap ? 1 : 0, cls ? 0 : 1, 0, rec, nullptr, layer, nullptr, nullptr, s};
 }
 
-static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
-                         void *stream, const char *entry, bool cls)
+// A checked layer through the layer scratch: the search `rules` select for `call` (its R the stack's, its points, shifts, records and
+// surfaces set per chunk here) in chunks of mimc3_stack_chunk(R) points, each followed by stack_add_kernel over its surfaces and records
+static int stack_add_chunked(mimc3_ctx *c, const double *d_xyuvav, int32_t N, SearchCall call, const SearchRules &rules)
 {
-    const std::string en(entry);
-    // the search's refusals and the stack's own, before anything is allocated or enqueued
-    RC_TRY(layer_check(c, entry, d_xyuvav, N, ocw, false, cls));
-    RC_TRY(stack_add_state(c, N, en));
-    RC_TRY(stack_add_radius(c, ocw, en));
     auto &k = c->stk;
     const size_t NC = stack_cells(c);
     const size_t chunk = (size_t)(N < mimc3::stack_chunk(k.R) ? N : mimc3::stack_chunk(k.R));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipStream_t s = call.stream;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NC));
     HIP_TRY(k.rec.reserve(sizeof(float) * 8 * chunk));
     float *layer = static_cast<float *>(k.layer.p), *rec = static_cast<float *>(k.rec.p);
-    SearchCall call = layer_call(entry, d_xyuvav, 0, off_u, off_v, static_cast<const int32_t *>(k.shift.p), ocw, k.R, swap, rec, layer, s, cls);
+    call.d_out = rec; call.d_surf = layer;
     SearchKernel kernel;
     PlaneSet planes;
-    RC_TRY(pick_kernel(c, call, cls ? kClassLayerRules : kLayerRules, kernel));
+    RC_TRY(pick_kernel(c, call, rules, kernel));
     RC_TRY(plane_set(c, kernel, 0, planes));                    // (planes a first call builds: on the context's stream, which it drains)
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     TimingSuspended whole(c);           // (the events bracket the whole call)
@@ -161,6 +159,19 @@ static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_
     k.layers++;
     if (whole.was) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
     return 0;
+}
+
+static int stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
+                         void *stream, const char *entry, bool cls)
+{
+    const std::string en(entry);
+    // the search's refusals and the stack's own, before anything is allocated or enqueued
+    RC_TRY(layer_check(c, entry, d_xyuvav, N, ocw, false, cls));
+    RC_TRY(stack_add_state(c, N, en));
+    RC_TRY(stack_add_radius(c, ocw, en));
+    const SearchCall call = layer_call(entry, d_xyuvav, 0, off_u, off_v, static_cast<const int32_t *>(c->stk.shift.p), ocw, c->stk.R, swap, nullptr,
+                                       nullptr, static_cast<hipStream_t>(stream), cls);
+    return stack_add_chunked(c, d_xyuvav, N, call, cls ? kClassLayerRules : kLayerRules);
 }
 
 extern "C" int mimc3_stack_add_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
@@ -201,6 +212,94 @@ extern "C" int mimc3_stack_add(mimc3_ctx *c, const double *xyuvav, int32_t N, co
 extern "C" int mimc3_stack_add_class(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap)
 {
     return stack_add_host(c, xyuvav, N, offset, ocw, swap, "mimc3_stack_add_class", true);
+}
+
+// ---- a layer at any chip size and radius, accumulated in the matrix-core search's own tail (mimc3_stack_add_fused; the definition is
+//      in include/mimc3_hip.h).  The layer is mimc3_match_ncc_wide_planes(mode 0, surf)'s: that entry's rules, as a layer ----
+static const SearchRules kFusedRules = {kFloat, true, false, kCandAbsent, false, false, true, false, true, true, true, true, true};
+static int fused_check(mimc3_ctx *c, const char *entry, const double *xyuvav, int32_t N, int32_t ocw, bool host)
+{
+    SearchCall call{};
+    call.entry = entry; call.host = host; call.d_xyuvav = xyuvav; call.N = N; call.ocw = ocw;
+    return search_check(c, call, kFusedRules);
+}
+// The largest stack radius the entry takes for the resident pair's class at a valid ocw: the matrix-core wide kernels' own on an 8-bit
+// and on a scaled-integer pair; on any other pair what mimc3_match_ncc_wide_planes(mode 0) takes -- the float wide kernel at the six,
+// R 15 elsewhere
+static int fused_max_radius(mimc3_ctx *c, int32_t ocw, PairClass &cls, int32_t &lim)
+{
+    RC_TRY(pair_class(c, cls));
+    const int32_t w = full_ocw_ok(ocw) ? mimc3::wide_max_radius(ocw) : 0;
+    lim = cls == kU8 ? mimc3::wide_u8_max_radius(ocw) : cls == kScaledInt ? mimc3::wide_u16_max_radius(ocw) : w > 15 ? w : 15;
+    return 0;
+}
+
+extern "C" int32_t mimc3_stack_fused_max_radius(mimc3_ctx *c, int32_t ocw)
+{
+    if (!c || ocw < 1 || ocw > mimc3::kFullChipMaxOcw || !c->d_i0 || !c->d_i1 || c->child) return 0;
+    PairClass cls;
+    int32_t lim = 0;
+    return fused_max_radius(c, ocw, cls, lim) ? 0 : lim;
+}
+
+static int stack_add_fused_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t swap,
+                               void *stream, const char *entry)
+{
+    const std::string en(entry);
+    // the search's refusals, the stack's own and the radius, before anything is allocated, enqueued or counted
+    RC_TRY(fused_check(c, entry, d_xyuvav, N, ocw, false));
+    RC_TRY(stack_add_state(c, N, en));
+    auto &k = c->stk;
+    PairClass cls;
+    int32_t lim = 0;
+    RC_TRY(fused_max_radius(c, ocw, cls, lim));
+    if (k.R > lim)
+        return mimc3::fail(MIMC3_EINVAL, en + ": the stack's R exceeds mimc3_stack_fused_max_radius(ctx, ocw) = " + std::to_string(lim));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SearchCall call = layer_call(entry, d_xyuvav, N, off_u, off_v, static_cast<const int32_t *>(k.shift.p), ocw, k.R, swap, nullptr, nullptr, s, true);
+    // any other class: what mimc3_match_ncc_wide_planes(mode 0, surf) runs, through the layer scratch
+    if (cls != kU8 && cls != kScaledInt) return stack_add_chunked(c, d_xyuvav, N, call, kFusedRules);
+    // the accumulating forms: one search over all N points that adds every finished surface into the stack itself
+    const SearchKernel kernel = cls == kU8 ? (k.R <= 15 ? ChipU8 : WideU8) : (k.R <= 15 ? ChipU16 : WideU16);
+    call.stk_sum = static_cast<double *>(k.sum.p); call.stk_cnt = static_cast<uint16_t *>(k.cnt.p);
+    call.stk_lay = static_cast<uint16_t *>(k.lay.p); call.stk_wsum = stack_wsum(c, 0);
+    PlaneSet planes;
+    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(plane_set(c, kernel, 0, planes));                    // (planes a first call builds: on the context's stream, which it drains)
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    TimingSuspended whole(c);           // (the events bracket the whole call)
+    RC_TRY(launch_search(c, kernel, planes, call));
+    k.layers++;
+    if (whole.was) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_stack_add_fused_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
+                                         int32_t swap, void *stream)
+{
+    return stack_add_fused_dev(c, d_xyuvav, N, off_u, off_v, ocw, swap, stream, "mimc3_stack_add_fused_dev");
+}
+
+extern "C" int mimc3_stack_add_fused(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap)
+{
+    const char *entry = "mimc3_stack_add_fused";
+    const std::string en(entry);
+    if (!offset) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    RC_TRY(fused_check(c, entry, xyuvav, N, ocw, true));
+    RC_TRY(stack_add_state(c, N, en));
+    PairClass cls;
+    int32_t lim = 0;
+    RC_TRY(fused_max_radius(c, ocw, cls, lim));
+    if (c->stk.R > lim)
+        return mimc3::fail(MIMC3_EINVAL, en + ": the stack's R exceeds mimc3_stack_fused_max_radius(ctx, ocw) = " + std::to_string(lim));
+    // the chip inside the image, the search box inside the planes' zero border (as mimc3_stack_add)
+    RC_TRY(search_check_host(c, entry, xyuvav, N, offset, c->stk.h_shift.data(), ocw, c->stk.R));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
+    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
+    RC_TRY(stack_add_fused_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, swap, c->stream, entry));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 extern "C" int mimc3_stack_add_surfaces_dev(mimc3_ctx *c, const float *d_surf, const uint8_t *d_refused, int32_t N, void *stream)

@@ -20,5 +20,6 @@ for line in p.stderr.splitlines():
     if "LDS Size" in t and "name" in cur:
         d = subprocess.run(["c++filt", cur["name"]], capture_output=True, text=True).stdout.strip()
         d = d.replace("mimc3::", "").replace("void ", "")
-        print("%-88s vgpr %4s sgpr %4s scratch %10s occ %s" % (d[:88], cur.get("vgpr"), cur.get("sgpr"), cur.get("scratch"), cur.get("occ")))
+        lds = t.split(":")[-1].split("[")[0].strip()                # (static LDS; a kernel's dynamic LDS is its launch's)
+        print("%-88s vgpr %4s sgpr %4s scratch %10s occ %s lds %s" % (d[:88], cur.get("vgpr"), cur.get("sgpr"), cur.get("scratch"), cur.get("occ"), lds))
         cur = {}
