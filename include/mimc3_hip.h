@@ -695,8 +695,8 @@ int mimc3_match_ncc_wide_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *   mimc3_match_ncc_wide's surface, and the tail is that entry's (one workgroup per point, the candidates from up to 95 x 95 cells), so
  *   a stack of ONE layer returns the bytes of mimc3_match_ncc_wide.  The state is 10 bytes per cell whatever R is: 18 GB at 200,000
  *   points and R 47.
- *   Not covered: several GPUs, the pyramid entries, MIMC3_hip_offsets; an accumulation fused into the search (a layer beyond R 15, and
- *   every scaled layer, is written to the layer scratch and read back once).
+ *   Not covered: several GPUs, the pyramid entries, MIMC3_hip_offsets.  (These entries write a layer beyond R 15, and every scaled
+ *   layer, to the layer scratch and read it back once; mimc3_stack_add_fused and mimc3_stack_add_scaled_fused do not.)
  *
  *   Layers of another time baseline: scaled and weighted (mimc3_stack_add_scaled, mimc3_stack_add_surfaces_scaled).  Pairs of different
  *   separation share a velocity, not a displacement: what moved d px in the stack's interval moved s d px in a pair s times as long.
@@ -731,8 +731,8 @@ int mimc3_match_ncc_wide_fb_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *       (double)v, and the stack's bytes are those of mimc3_stack_add / mimc3_stack_add_surfaces.
  *     every layer at the same power-of-two weight:  sum and wsum are the unweighted sum and cnt times that power, exactly, and the mean
  *       is the unweighted mean bit for bit.
- *   Not covered by the scaled layers: several GPUs, the pyramid entries, forward-backward, MIMC3_hip_offsets, and fusing the
- *   accumulation into the search. */
+ *   Not covered by the scaled layers: several GPUs, the pyramid entries, forward-backward, MIMC3_hip_offsets.  (Fusing the accumulation
+ *   into the search: mimc3_stack_add_scaled_fused, on 8-bit and scaled-integer pairs.) */
 #define MIMC3_STACK_CHUNK 65536
 /* Sizes and zeroes the stack and uploads shift (host [N][2], or NULL).  1 <= R <= 15.  A second call discards the first stack; N = 0
  * releases its memory (R and shift are then ignored).  A chip-atlas context: MIMC3_ESTATE.  Returns when the stack is ready. */
@@ -765,8 +765,8 @@ int mimc3_stack_add_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32
  * lay, wsum -- is bit for bit the state after mimc3_stack_add, on every pixel class, and the two may be mixed freely.  A weighted
  * stack's wsum gets 1.0 per finite cell, as from mimc3_stack_add.  On a stack of R >= 16 the call IS mimc3_stack_add (the wide kernel),
  * byte for byte: a caller does not have to branch.  mimc3_ctx_last_path reports the kernel that ran (6 / 7 / 8 / 9; 10 beyond R 15).
- * Not covered: scaled layers through the class kernels; the layer scratch round trip stays here (mimc3_stack_add_fused below fuses
- * the accumulation into the run-time-ocw matrix-core searches). */
+ * Not covered: scaled layers through the templated class kernels; the layer scratch round trip stays here (mimc3_stack_add_fused and
+ * mimc3_stack_add_scaled_fused below fuse the accumulation into the run-time-ocw matrix-core searches). */
 int mimc3_stack_add_class(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap);
 /* Device-resident variant, under the contract of mimc3_stack_add_dev (a first call on a pair builds the planes and tables its kernel
  * reads on the context's own stream and waits for them first). */
@@ -797,7 +797,8 @@ int mimc3_stack_add_class_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N,
  *   (no stack, 65,535 layers: MIMC3_ESTATE; N differs: MIMC3_EINVAL); a stack radius beyond mimc3_stack_fused_max_radius(ctx, ocw):
  *   MIMC3_EINVAL, with the limit in the message; the host entry: a chip that leaves the image, a search box that leaves the zero border:
  *   MIMC3_EBOUNDS.
- *   Not covered: scaled layers (mimc3_stack_add_scaled) through these kernels, the pyramids, several GPUs, 16-bit kernels at other chip sizes. */
+ *   Not covered: the pyramids, several GPUs, 16-bit kernels at other chip sizes (scaled layers through these kernels:
+ *   mimc3_stack_add_scaled_fused below). */
 int mimc3_stack_add_fused(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t swap);
 /* Device-resident variant, under the contract of mimc3_stack_add_dev: a point that breaks the host entry's bounds adds no cell and
  * counts as a layer (a first call on a pair builds the planes and tables its kernel reads on the context's own stream and waits for them). */
@@ -841,6 +842,43 @@ int mimc3_stack_add_scaled(mimc3_ctx *ctx, const double *xyuvav, int32_t N, cons
 /* Device-resident variant, under the contract of mimc3_stack_add_dev. */
 int mimc3_stack_add_scaled_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
                                int32_t layer_R, int32_t swap, double scale, double weight, void *stream);
+/* mimc3_stack_add_scaled at ANY chip half-width 1 <= ocw <= 80 and any layer radius the pair's class reaches, resampled in the search's
+ * own tail.
+ *   Definition: the layer is mimc3_match_ncc_wide_planes(mode 0, npeaks 0, shift = Lsh, R = layer_R, surf) on the resident pair (at
+ *   layer_R <= 15 that is mimc3_match_ncc_full_chip_planes), Lsh the layer shift of the definition above, added as
+ *   mimc3_stack_add_surfaces_scaled(surf, refused, layer_R, scale, weight) adds it with the refused points taken from the record (status
+ *   -3).  The stack's state afterwards -- sum, cnt, lay, wsum, and whether it is weighted -- is bit for bit the state after that
+ *   two-call chain; at the six chip sizes with layer_R <= mimc3_wide_max_radius(ocw) it is the state after mimc3_stack_add_scaled as
+ *   well; scale 1, weight 1, layer_R = R gives the bytes of mimc3_stack_add_fused; every kind of add may be mixed with every other.
+ *   Limits: 1 <= ocw <= 80; 1 <= layer_R <= mimc3_stack_fused_max_radius(ctx, ocw), whatever the stack's R (1..47, begun by either
+ *   mimc3_stack_begin or _begin_wide): the stack's radius and the layer's are independent.
+ *   Which kernel runs (mimc3_ctx_last_path reports it after every add), chosen by layer_R:
+ *     8-bit pair       12 ("u8_mfma_chip") at layer_R <= 15, 14 ("u8_mfma_wide") beyond -- the accumulating forms of mimc3_stack_add_fused,
+ *                      which here RESAMPLE: after the barrier that completes a point's layer surface in LDS the workgroup walks the
+ *                      STACK's cells, and each takes its bilinear value from the surface by the definition above, operation for
+ *                      operation (one lane owns a stack cell: plain read-modify-writes).  One launch pair over all N points: no layer
+ *                      scratch, no record scratch, no chunks, no LDS beyond the search's own.
+ *     scaled-integer   13 ("u16_mfma_chip") / 15 ("u16_mfma_wide"), the same way (12-bit DN, the pair after mimc3_ctx_filter_images).
+ *     any other pair   (16-bit DN, floats) not fused: the kernel mimc3_match_ncc_wide_planes(mode 0, surf) runs (8 / 9 at the six and 11
+ *                      elsewhere up to layer_R 15, 10 beyond at the six) through the layer scratch and the accumulation of
+ *                      mimc3_stack_add_scaled in chunks of min(mimc3_stack_chunk(R), mimc3_stack_chunk(layer_R)) -- which gives those
+ *                      pairs scaled layers at every chip size up to layer_R 15; where no kernel takes (ocw, layer_R) the call is refused.
+ *   Before the launch, on the call's stream, what every scaled add enqueues: the wsum plane of a stack that this add makes weighted
+ *   (the first weight != 1.0), and the layer shift.
+ *   Refusals, all before anything is allocated, enqueued or counted (the stack's bytes, mimc3_stack_info and mimc3_stack_weighted stay
+ *   as they were): those of mimc3_stack_add_fused (ocw outside 1..80, a null pointer, N <= 0: MIMC3_EINVAL; no images, a chip-atlas
+ *   context: MIMC3_ESTATE; no stack, 65,535 layers: MIMC3_ESTATE; N differs: MIMC3_EINVAL); a scale outside 2^-6..2^6, a weight that is
+ *   not finite and > 0, a layer_R outside 1..mimc3_stack_fused_max_radius(ctx, ocw) (the limit is in the message), |scale shift| >=
+ *   2^30: MIMC3_EINVAL; the host entry: a chip that leaves the image, the LAYER's box (layer_R + ocw around uv0 + offset + Lsh) that
+ *   leaves the zero border: MIMC3_EBOUNDS.
+ *   Not covered: mimc3_stack_add_surfaces_scaled is unchanged (a caller's surfaces go through stack_add_scaled_kernel); 16-bit pairs
+ *   beyond layer_R 15 at chip sizes outside the six; the pyramids; several GPUs; MIMC3_hip_offsets. */
+int mimc3_stack_add_scaled_fused(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw, int32_t layer_R,
+                                 int32_t swap, double scale, double weight);
+/* Device-resident variant, under the contract of mimc3_stack_add_dev: a point that breaks the host entry's bounds adds no cell and
+ * counts as a layer. */
+int mimc3_stack_add_scaled_fused_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
+                                     int32_t layer_R, int32_t swap, double scale, double weight, void *stream);
 /* One scaled layer from the caller's surfaces, which the caller searched around mimc3_stack_layer_shift: surf [N][Sl^2] in k order,
  * 1 <= layer_R <= 47, refused [N] or NULL.  Refusals: as above, without those of the search. */
 int mimc3_stack_add_surfaces_scaled(mimc3_ctx *ctx, const float *surf /*host [N][Sl^2]*/, const uint8_t *refused /*host [N] or NULL*/,

@@ -121,6 +121,9 @@ _lib.mimc3_stack_weighted.argtypes = [_vp]
 _lib.mimc3_stack_add_scaled.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double]
 _lib.mimc3_stack_add_scaled_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                             C.c_double, _vp]
+_lib.mimc3_stack_add_scaled_fused.argtypes = [_vp, _f64p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double]
+_lib.mimc3_stack_add_scaled_fused_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                                  C.c_double, _vp]
 _lib.mimc3_stack_add_surfaces_scaled.argtypes = [_vp, _f32p, _vp, C.c_int32, C.c_int32, C.c_double, C.c_double]
 _lib.mimc3_stack_add_surfaces_scaled_dev.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_double, _vp]
 _lib.mimc3_match_ncc_pyramid.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _i32p]
@@ -927,7 +930,7 @@ class Context:
     def stack_fused_max_radius(self, ocw):
         """The largest stack radius stack_add_fused takes for the resident pair's class at this ocw: 47 on an 8-bit pair,
         wide_planes_max_radius(ocw) on a scaled-integer one, else 15, or wide_max_radius(ocw) at the six chip sizes; 0 for an ocw
-        outside 1..80 or without a pair."""
+        outside 1..80 or without a pair.  Also the largest LAYER radius stack_add_scaled_fused takes, whatever the stack's radius."""
         return int(_lib.mimc3_stack_fused_max_radius(self._h, int(ocw)))
 
     def stack_add_surfaces(self, surf, refused=None):
@@ -983,6 +986,35 @@ class Context:
         r = self._scaled_radius("stack_add_scaled_dev", scale, radius, ocw)
         _check(_lib.mimc3_stack_add_scaled_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), ocw, r, 1 if swap else 0, float(scale),
                                                float(weight), stream), "stack_add_scaled_dev")
+
+    def _scaled_fused_radius(self, what, scale, radius, ocw):
+        if radius is not None:
+            return int(radius)
+        r, lim = stack_layer_radius(self.stack_info()[1], scale), self.stack_fused_max_radius(ocw)
+        if r > lim:
+            raise ValueError(f"{what}: scale {scale} wants a layer radius of {r}, beyond stack_fused_max_radius({ocw}) = {lim}: "
+                             f"pass a radius explicitly (the stack's outer cells then get no count from this layer)")
+        return r
+
+    def stack_add_scaled_fused(self, xyuvav, offset, ocw, scale, weight=1.0, radius=None, swap=False):
+        """stack_add_scaled at any chip half-width 1..80 and any layer radius up to stack_fused_max_radius(ocw), resampled in the
+        search's own tail (mimc3_stack_add_scaled_fused): the layer is match_ncc_wide_planes(mode=0, surface=True) at `radius` (None:
+        stack_layer_radius of the stack's radius) around stack_layer_shift(scale), added as stack_add_surfaces_scaled adds it -- the
+        stack afterwards is bit for bit that chain's, and stack_add_scaled's at the six chip sizes.  An 8-bit or scaled-integer pair
+        runs the accumulating forms of the run-time-ocw matrix-core kernels ("u8_mfma_chip" / "u8_mfma_wide", "u16_mfma_chip" /
+        "u16_mfma_wide"): one launch pair over all points, every workgroup resampling its point's surface from LDS into the stack,
+        with no layer scratch and no chunks; any other pair goes through the layer scratch on the kernel that entry runs.
+        last_path() reports the kernel."""
+        xy = np.ascontiguousarray(xyuvav, np.float64)
+        r = self._scaled_fused_radius("stack_add_scaled_fused", scale, radius, ocw)
+        _check(_lib.mimc3_stack_add_scaled_fused(self._h, xy, xy.shape[0], np.ascontiguousarray(offset, np.int32), ocw, r, 1 if swap else 0,
+                                                 float(scale), float(weight)), "stack_add_scaled_fused")
+
+    def stack_add_scaled_fused_dev(self, d_xyuvav, n, offset, ocw, scale, weight=1.0, radius=None, stream=0, swap=False):
+        """Device-pointer variant (enqueue only)."""
+        r = self._scaled_fused_radius("stack_add_scaled_fused_dev", scale, radius, ocw)
+        _check(_lib.mimc3_stack_add_scaled_fused_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), ocw, r, 1 if swap else 0,
+                                                     float(scale), float(weight), stream), "stack_add_scaled_fused_dev")
 
     def stack_add_surfaces_scaled(self, surf, radius, scale, weight=1.0, refused=None):
         """One scaled layer from the caller's surfaces float32[n][(2 radius + 1)^2] in k order, searched around

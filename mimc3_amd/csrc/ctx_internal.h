@@ -169,6 +169,11 @@ struct SearchCall {
     double *stk_sum;
     uint16_t *stk_cnt, *stk_lay;
     double *stk_wsum;                   // a weighted stack's, or null
+    // ... a SCALED one (mimc3_stack_add_scaled_fused): the stack's shift [N][2] and radius, the layer's scale and weight -- d_shift and R are
+    // then the LAYER's shift and radius; stk_shift null = an unscaled layer
+    const int32_t *stk_shift;
+    int32_t stk_R;
+    double stk_scale, stk_weight;
 };
 enum PairClass { kU8, kScaledInt, kIntegralF32, kFloat };             // a pair's class; an entry takes every class up to its rules' widest
 enum CandRule { kCandAbsent, kCandOptional, kCandMandatory };

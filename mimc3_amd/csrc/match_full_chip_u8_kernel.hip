@@ -599,7 +599,7 @@ __global__ __launch_bounds__(kNT, C::MINW) void match_ncc_full_chip_u8(MatchU8Ar
     }
     __syncthreads();
     if constexpr (C::ACC) {                                 // the surface into the stack, in the SURF store's place; no tail
-        mx::stack_acc<NT, VP>(p, val, gidx, S, tid);
+        mx::stack_acc_any<NT, VP>(p, val, gidx, S, tid);     // (resampled where the layer is a scaled one: a launch-uniform branch)
         return;
     }
     if constexpr (C::SURF) {                                // the surface in k order (u outer): coalesced stores, LDS reads at stride VP
@@ -689,6 +689,7 @@ hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t strea
     a.point_flags = nullptr;
     if (forms & kFormsAcc) {            // the stack's planes in the list-mode slots; nothing else is written
         if (!a.stk_sum || !a.stk_cnt || !a.stk_lay || a.out || a.full_cand || a.full_surf) return hipErrorInvalidValue;
+        if (a.stk_shift && !mx::stack_acc_scaled_ok(a)) return hipErrorInvalidValue;
         return fchip8::launch_forms_acc(a, forms, stream);
     }
     if (a.full_cand) {

@@ -42,7 +42,10 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     const unsigned char *p0, *p1;   // zero-bordered planes of i0, i1 (u8 or f32 pixels): pixel (u,v) at [(v+pad)*Wp + u+pad]
     int32_t Wp, pad;                // plane pitch (PIXELS; a whole number of dwords) and border
     float thr;                      // smallest f32 whose f64 value is >= MIN_DN (f32 policy)
-    double scale0, scale1;          // u16 policy: plane k stores value * 2^s_k; scale_k = 2^-s_k (1.0 otherwise)
+    // u16 policy: plane k stores value * 2^s_k; scale_k = 2^-s_k (1.0 otherwise).  (The accumulating forms of the run-time-ocw
+    // matrix-core searches, which read no plane scale: a SCALED layer's scale and weight, stack_acc.h)
+    union { double scale0; double stk_scale; };
+    union { double scale1; double stk_weight; };
     int32_t H, W;
     const double *xyuvav;
     int32_t xy_stride, xy_col;      // see MatchArgs
@@ -108,9 +111,11 @@ struct MatchU8Args {                // arguments of the register-tiled kernel fa
     // record of a point it appends (both writable: u8_classify fills them).  ALIASED SLOTS: a caller sets either the range tiles (PxU8o,
     // the only policy that reads rt0 / rt1) or the records (the PxU8 launches behind u8_classify), never both, and clears them before
     // the argument block goes to a kernel of the other kind -- a non-null rt0 in a PxU8 launch is a record pointer
-    union { const uint32_t *rt0; struct U8PointRec *point_recs; };
+    // (The accumulating forms of the run-time-ocw matrix-core searches, which read neither: stk_shift, the STACK's shift [N][2] of a scaled
+    //  layer -- full_shift is then the layer shift -- or null = an unscaled layer, and stk_R, the stack's radius)
+    union { const uint32_t *rt0; struct U8PointRec *point_recs; const int32_t *stk_shift; };
     union { const uint32_t *rt1; struct U8PointRec *rest_recs; };
-    int32_t rt_tw;                                  // tiles per plane row
+    union { int32_t rt_tw; int32_t stk_R; };        // tiles per plane row
     int32_t replay_shortcut;                        // DLC kernels: the exact replay tries the winning pivot alone first (replay_shortcut_on;
                                                     // filled by the launchers; in the four bytes the table pointers' alignment left unused)
     // packed summed-area tables of the two planes (sat_kernel.hip; policies with P::SAT), (Hp + 1) rows of sat_ws entries
@@ -294,9 +299,13 @@ hipError_t launch_match_full_chip(MatchU8Args a, float *surf, hipStream_t stream
 // 3 is the search, 1 and 2 are for timing the forms apart.  Bit 2 (kFormsAcc, with any of the above; this kernel and the three below)
 // selects the ACCUMULATING forms (stack_acc.h): each point's finished surface is added into the stack at a.stk_sum / a.stk_cnt / a.stk_lay
 // (/ a.stk_wsum) in the tail's place -- no record, candidate or surface is written, so a.out, a.full_cand and a.full_surf must be null.
+// With a.stk_shift set the layer is a SCALED one (mimc3_stack_add_scaled_fused): a.full_R and a.full_shift are the layer's, a.stk_R (1 ..
+// kStackAccMaxRadius) and a.stk_shift the stack's, a.stk_scale and a.stk_weight the layer's scale and weight, and every workgroup
+// resamples its point's surface onto the stack's cells (stack_acc_scaled); a.stk_shift null is the unscaled layer, as before.
 // full_chip_u8_layout: K chunks per chip row, 16-row tiles and K chunks of the
 // box sums, dynamic LDS bytes of a launch at this ocw (false outside 1 .. kFullChipMaxOcw)
 constexpr int kFormsAcc = 4;
+constexpr int kStackAccMaxRadius = 47;  // (stack_kernel.h's kStackMaxRadius: stack_kernel.hip asserts the two equal)
 bool full_chip_u8_layout(int ocw, int out[4]);
 hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t stream);
 // ... and on the u16 planes of a SCALED-INTEGER pair (q < 4096; match_full_chip_u16_kernel.hip; mimc3_match_ncc_full_chip_planes): a.p0 / a.p1

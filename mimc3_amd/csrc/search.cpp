@@ -307,6 +307,8 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
         if (kernel != ChipU8 && kernel != ChipU16 && kernel != WideU8 && kernel != WideU16)
             return fail(MIMC3_EUNSUPPORTED, std::string(call.entry) + ": this kernel has no accumulating form");
         u.stk_sum = call.stk_sum; u.stk_cnt = call.stk_cnt; u.stk_lay = call.stk_lay; u.stk_wsum = call.stk_wsum;
+        // (a scaled layer: in the slots of the plane scales and the range tiles, which these kernels do not read)
+        if (call.stk_shift) { u.stk_shift = call.stk_shift; u.stk_R = call.stk_R; u.stk_scale = call.stk_scale; u.stk_weight = call.stk_weight; }
     }
     if (flags) HIP_TRY(c->mxl[0].reserve((size_t)call.N));             // one class byte per point, zero before the launch
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));

@@ -5,7 +5,8 @@
 // validates everything before its first launch.  A layer from the resident pair is a search of the exhaustive-search family: checked,
 // selected and launched through that layer's functions (search.cpp).  mimc3_stack_add_fused takes a layer at any chip size and radius: on an
 // 8-bit or scaled-integer pair the run-time-ocw matrix-core search adds every surface into the stack itself (its accumulating forms,
-// stack_acc.h: no layer scratch); any other pair goes through the layer scratch as above.
+// stack_acc.h: no layer scratch); any other pair goes through the layer scratch as above.  mimc3_stack_add_scaled_fused is the same for a layer
+// of another time baseline: the search runs at the layer's radius around the layer shift and resamples every surface into the stack.
 #include <cmath>
 #include <cstring>
 #include "ctx_internal.h"
@@ -421,25 +422,25 @@ static int stack_scaled_prepare(mimc3_ctx *c, double scale, double weight, hipSt
     return 0;
 }
 
-static int stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t layer_R,
-                                int32_t swap, double scale, double weight, void *stream, const char *entry)
+// A checked scaled layer through the layer scratch: the search `rules` select for `call` (its R the layer's; its points, layer shifts,
+// records and surfaces set per chunk here) in chunks of min(mimc3_stack_chunk(R), mimc3_stack_chunk(layer_R)) points, each followed by
+// stack_add_scaled_kernel over its surfaces and records
+static int stack_add_scaled_chunked(mimc3_ctx *c, const double *d_xyuvav, int32_t N, SearchCall call, const SearchRules &rules, double scale,
+                                    double weight)
 {
-    const std::string en(entry);
-    RC_TRY(layer_check(c, entry, d_xyuvav, N, ocw, false));
-    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::wide_max_radius(ocw), scale, weight, en));
     auto &k = c->stk;
+    const int32_t layer_R = call.R;
     const size_t NC = stack_cells(c), NCl = (size_t)((2 * layer_R + 1) * (2 * layer_R + 1));
     const size_t chunk = stack_scaled_chunk(c, N, layer_R);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipStream_t s = call.stream;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(k.layer.reserve(sizeof(float) * chunk * NCl));
     HIP_TRY(k.rec.reserve(sizeof(float) * 8 * chunk));
     float *layer = static_cast<float *>(k.layer.p), *rec = static_cast<float *>(k.rec.p);
-    // mimc3_match_ncc_wide(npeaks 0, shift = the layer shift, R = layer_R, surf): the float kernel up to 15, the wide kernel beyond
-    SearchCall call = layer_call(entry, d_xyuvav, 0, off_u, off_v, nullptr, ocw, layer_R, swap, rec, layer, s);
+    call.d_out = rec; call.d_surf = layer;
     SearchKernel kernel;
     PlaneSet planes;
-    RC_TRY(pick_kernel(c, call, kLayerRules, kernel));
+    RC_TRY(pick_kernel(c, call, rules, kernel));
     RC_TRY(plane_set(c, kernel, 0, planes));                    // (as mimc3_stack_add_dev)
     if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
     TimingSuspended whole(c);           // (the events bracket the whole call)
@@ -458,6 +459,17 @@ static int stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N,
     k.layers++;
     if (whole.was) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
     return 0;
+}
+
+static int stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw, int32_t layer_R,
+                                int32_t swap, double scale, double weight, void *stream, const char *entry)
+{
+    const std::string en(entry);
+    RC_TRY(layer_check(c, entry, d_xyuvav, N, ocw, false));
+    RC_TRY(stack_scaled_check(c, N, layer_R, mimc3::wide_max_radius(ocw), scale, weight, en));
+    // mimc3_match_ncc_wide(npeaks 0, shift = the layer shift, R = layer_R, surf): the float kernel up to 15, the wide kernel beyond
+    const SearchCall call = layer_call(entry, d_xyuvav, 0, off_u, off_v, nullptr, ocw, layer_R, swap, nullptr, nullptr, static_cast<hipStream_t>(stream));
+    return stack_add_scaled_chunked(c, d_xyuvav, N, call, kLayerRules, scale, weight);
 }
 
 extern "C" int mimc3_stack_add_scaled_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
@@ -483,6 +495,77 @@ extern "C" int mimc3_stack_add_scaled(mimc3_ctx *c, const double *xyuvav, int32_
     RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
     RC_TRY(stack_add_scaled_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, layer_R, swap, scale, weight,
                                 c->stream, entry));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- a scaled layer at any chip size and layer radius, resampled in the matrix-core search's own tail (mimc3_stack_add_scaled_fused; the
+//      definition is in include/mimc3_hip.h).  The layer is mimc3_match_ncc_wide_planes(mode 0, surf)'s around the layer shift ----
+// what both entries check beyond the search's refusals, before anything is allocated, enqueued or counted: the stack's own, then the
+// scale, the weight, the layer radius against mimc3_stack_fused_max_radius(ctx, ocw) and the layer shift's range
+static int stack_scaled_fused_check(mimc3_ctx *c, int32_t N, int32_t ocw, int32_t layer_R, double scale, double weight, PairClass &cls,
+                                    const std::string &en)
+{
+    RC_TRY(stack_add_state(c, N, en));
+    int32_t lim = 0;
+    RC_TRY(fused_max_radius(c, ocw, cls, lim));
+    return stack_scaled_check(c, N, layer_R, lim, scale, weight, en);
+}
+
+static int stack_add_scaled_fused_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
+                                      int32_t layer_R, int32_t swap, double scale, double weight, void *stream, const char *entry)
+{
+    const std::string en(entry);
+    PairClass cls;
+    RC_TRY(fused_check(c, entry, d_xyuvav, N, ocw, false));
+    RC_TRY(stack_scaled_fused_check(c, N, ocw, layer_R, scale, weight, cls, en));
+    auto &k = c->stk;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SearchCall call = layer_call(entry, d_xyuvav, N, off_u, off_v, nullptr, ocw, layer_R, swap, nullptr, nullptr, s, true);
+    // any other class: what mimc3_match_ncc_wide_planes(mode 0, surf) runs, through the layer scratch and stack_add_scaled_kernel
+    if (cls != kU8 && cls != kScaledInt) return stack_add_scaled_chunked(c, d_xyuvav, N, call, kFusedRules, scale, weight);
+    // the accumulating forms: one search over all N points, every workgroup resampling its finished surface into the stack itself
+    const SearchKernel kernel = cls == kU8 ? (layer_R <= 15 ? ChipU8 : WideU8) : (layer_R <= 15 ? ChipU16 : WideU16);
+    PlaneSet planes;
+    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(plane_set(c, kernel, 0, planes));                    // (planes a first call builds: on the context's stream, which it drains)
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, s));
+    TimingSuspended whole(c);           // (the events bracket the whole call)
+    RC_TRY(stack_scaled_prepare(c, scale, weight, s));          // (the wsum plane of a stack this add makes weighted; the layer shift)
+    call.d_shift = static_cast<const int32_t *>(k.lsh.p);
+    call.stk_sum = static_cast<double *>(k.sum.p); call.stk_cnt = static_cast<uint16_t *>(k.cnt.p);
+    call.stk_lay = static_cast<uint16_t *>(k.lay.p); call.stk_wsum = stack_wsum(c, 0);
+    call.stk_shift = static_cast<const int32_t *>(k.shift.p); call.stk_R = k.R; call.stk_scale = scale; call.stk_weight = weight;
+    RC_TRY(launch_search(c, kernel, planes, call));
+    k.layers++;
+    if (whole.was) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
+    return 0;
+}
+
+extern "C" int mimc3_stack_add_scaled_fused_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, int32_t ocw,
+                                                int32_t layer_R, int32_t swap, double scale, double weight, void *stream)
+{
+    return stack_add_scaled_fused_dev(c, d_xyuvav, N, off_u, off_v, ocw, layer_R, swap, scale, weight, stream, "mimc3_stack_add_scaled_fused_dev");
+}
+
+extern "C" int mimc3_stack_add_scaled_fused(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], int32_t ocw,
+                                            int32_t layer_R, int32_t swap, double scale, double weight)
+{
+    const char *entry = "mimc3_stack_add_scaled_fused";
+    const std::string en(entry);
+    if (!offset) return mimc3::fail(MIMC3_EINVAL, en + ": bad argument");
+    PairClass cls;
+    RC_TRY(fused_check(c, entry, xyuvav, N, ocw, true));
+    RC_TRY(stack_scaled_fused_check(c, N, ocw, layer_R, scale, weight, cls, en));
+    // the chip inside the image, the layer's search box inside the planes' zero border (as mimc3_stack_add_scaled)
+    std::vector<int32_t> lsh(c->stk.h_shift.size());
+    RC_TRY(stack_layer_shift(c, scale, lsh.data(), en));
+    RC_TRY(search_check_host(c, entry, xyuvav, N, offset, lsh.data(), ocw, layer_R));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->xy.reserve(sizeof(double) * 6 * (size_t)N));
+    RC_TRY(h2d_copy(c, c->xy.p, xyuvav, sizeof(double) * 6 * (size_t)N));
+    RC_TRY(stack_add_scaled_fused_dev(c, static_cast<const double *>(c->xy.p), N, offset[0], offset[1], ocw, layer_R, swap, scale, weight,
+                                      c->stream, entry));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

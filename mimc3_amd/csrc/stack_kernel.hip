@@ -5,6 +5,7 @@
 // stack_add_scaled_kernel accumulates a layer of another time baseline: every stack cell takes the bilinear value of the layer's surface
 // at scale x its displacement, times the layer's weight; a weighted stack keeps the weights' sum per cell in a third plane, wsum.
 #include "stack_kernel.h"
+#include "stack_acc.h"
 #include "match_full_tail.h"
 #include "match_wide_tail.h"
 
@@ -84,16 +85,8 @@ __global__ __launch_bounds__(256) void stack_add_kernel(const float *__restrict_
 // One workgroup per point.  The point's layer surface, Sl x Sl floats (36,100 bytes at Sl = 95: dynamic LDS, sized by Rl at the launch),
 // is read from HBM once into LDS in its k order; then the stack's cells are walked with k contiguous over the threads, so the
 // read-modify-writes of sum, cnt and wsum are coalesced.  One lane owns a cell (plain read-modify-writes), thread 0 counts lay.
-// Every f64 operation below is the definition's, in its order (-ffp-contract=off: nothing fuses).  pu is s su give or take 1/2 and an
-// ulp, so |pu| < 64 x 47 + 1 and (int)fu is exact.
-__device__ __forceinline__ void stack_scaled_axis(double s, int32_t shift, int d, int32_t lshift, int Rl, double &a, int &j)
-{
-    const double p = s * (double)((int64_t)shift + d) - (double)lshift;
-    const double f = __builtin_floor(p);
-    a = p - f;
-    j = (int)f + Rl;
-}
-
+// Every f64 operation below is the definition's, in its order (-ffp-contract=off: nothing fuses); stack_scaled_axis is stack_acc.h's,
+// which the accumulating forms of the matrix-core searches share.
 __global__ __launch_bounds__(256) void stack_add_scaled_kernel(const float *__restrict__ surf, const float *__restrict__ rec,
                                                                const uint8_t *__restrict__ refused, const int32_t *__restrict__ shift,
                                                                const int32_t *__restrict__ lshift, int R, int Rl, double s, double w,
@@ -209,6 +202,7 @@ struct StackWideCfg {
 };
 static_assert(mx::kWideLmBytes % 16 == 0, "the surface behind the bit plane stays 16-byte aligned");
 static_assert(2 * kStackMaxRadius + 1 < StackWideCfg<false>::VP, "the surface pitch");
+static_assert(kStackAccMaxRadius == kStackMaxRadius, "the accumulating forms of the searches take every stack (match_kernel.h)");
 static_assert((2 * kStackMaxRadius + 1) * (2 * kStackMaxRadius + 1) <= 64 * 32 * mx::kWideLmWords, "the bit plane of the candidate tail");
 
 template <bool MULTI>
