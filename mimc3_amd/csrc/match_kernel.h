@@ -247,6 +247,7 @@ U8PointRec *u8_list_recs(int32_t *lists, int N);
 bool u8_point_records_on();        // (tuning / A-B: MIMC3_U8_RECS=0 keeps the memory headers)
 bool u8_advance_on();              // (tuning / A-B: MIMC3_U8_ADVANCE=0, or no records, leaves the advance list empty)
 bool mx_area_on();                 // (tuning / A-B: MIMC3_MX_AREA=0, or no advance list, gives clean points the whole tile as their area)
+bool mx_box_table_on();            // (tuning / A-B: MIMC3_MX_BOX_TABLE=0 gives the record forms the MFMA box sums back; else they read the window plane's table)
 // The exact replay of both DLC kernels first replays the winning pivot alone (match_mx_kernel.hip, "the shortcut"; match_px_kernel.hip's
 // fast register form); tests / A-B: MIMC3_REPLAY_SHORTCUT=0 forces the full replay.  What a point did, as the diagnostics count it
 // (MIMC3_MX_STATS, MIMC3_U8_STATS):

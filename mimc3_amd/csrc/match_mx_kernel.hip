@@ -13,7 +13,8 @@
 //              sum ab = sum a'b' + 128 sum_box b + 128 sum a - 128^2 CW^2        (a null is a zero factor: no mask anywhere)
 //   * window-side sums  sy = sum_box b, syy = sum_box b^2  of every cell: row-box sums by MFMA against a band of ones
 //     (b^2 as two byte planes), then the vertical CW-row sums by a second MFMA against a band of ones (the row sums split
-//     into byte planes; an accumulator tile is the next MFMA's B operand as it stands: its rows are the K index);
+//     into byte planes; an accumulator tile is the next MFMA's B operand as it stands: its rows are the K index) -- the record
+//     forms (RecCfg) read them from the window plane's packed table instead, for the cells they will finish (BOXT below);
 //   * null pixels (the two forms for null-ridden points, built and tested but not taken by default: launch_match_mx has the
 //     measurements).  A window null q of the box takes a(q) out of n, sx, sxx: with zb = [b == 0] as the A operand the corrections
 //     are three more correlations on the same pipe -- sum zb (box count), sum a zb (same B operand as sxy), sum a^2 zb (a^2 as two
@@ -115,13 +116,18 @@ struct Cfg {
     static constexpr bool MULTI = false;                // full mode: also write the best local maxima as candidates to full_cand (FullMultiCfg)
     static constexpr bool SURF = false;                 // full mode: also store the finished surface to full_surf (FullSurfCfg, FullMultiSurfCfg)
     static constexpr bool REC = false;                  // the header comes from u8_classify's point record (RecCfg)
+    static constexpr bool BOXT = false;                 // the window-side box sums come from the window plane's packed table (RecCfg), not from MFMAs
 };
 // The clean form behind u8_classify with point records (U8PointRec, match_kernel.h): workgroup b starts from the record at list position b
 // -- one load behind the list length -- instead of the list entry, the point row and pivot range, the last pivot and the table queries,
 // each of which waited for the one before.  Everything behind the header is Cfg<OCW_, false>'s
-template <int OCW_>
+// BOXT_: sum_box b and sum_box b^2 of the cells the finish will run are read from the window plane's packed table (sat_kernel.h: four
+// entries per cell, the T4 column and row by a clamp of the far corner -- sat_cell_corners) instead of being recomputed for all 1,024
+// cells by MFMAs against bands of ones; false (MIMC3_MX_BOX_TABLE=0): the MFMA box sums, as in every other form
+template <int OCW_, bool BOXT_ = true>
 struct RecCfg : Cfg<OCW_, false, false> {
     static constexpr bool REC = true;
+    static constexpr bool BOXT = BOXT_;
 };
 // Exhaustive search (mimc3_match_ncc_full): the same surface builder on the cell tile whose origin is c - R (the search centre
 // c = uv0 + offset + shift, 1 <= R <= 15: all (2R + 1)^2 cells in the tile), no never-written row / column (T4), and instead of the
@@ -725,7 +731,40 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
     //      Box[dy][s] = sum_{y = dy}^{dy + CW - 1} R[y][s] by MFMA (A = the band of ones, B = the byte planes of R: the four registers
     //      of a 16-row accumulator tile are one dword of the B operand -- the accumulator layout has R's rows where B has its K index)
     v4i boxb[2], boxq[2], boxz[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    {
+    [[maybe_unused]] uint32_t bands_t = 0xffu;               // BOXT: the bands the finish will run (wave-uniform)
+    if constexpr (C::BOXT) {
+        // From the window plane's packed table (built once per image): the sums depend on the plane and the box position alone.  Only
+        // the cells of the bands the finish will run -- a wave whose columns miss the climb area loads nothing -- four entries per cell
+        // at 32-bit offsets from the entry of the tile's pixel (0, 0), the four bands of an accumulator tile in flight together, each
+        // cell combined to its two sums as its entries arrive.  The never-written last column and row (T4) are zeros of the staged tile
+        // but real pixels of the table: sat_cell_corners ends such a box in front of them.  Exact integers, the same as the MFMAs'
+        const uint32_t ar = area_w >> 8, w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+        const uint32_t x0 = ar & 31u, x1 = (ar >> 5) & 31u, y0 = (ar >> 10) & 31u, y1 = (ar >> 15) & 31u;
+        bands_t = (w >= (x0 >> 4) && w <= (x1 >> 4)) ? ((2u << (y1 >> 2)) - (1u << (y0 >> 2))) & 0xffu : 0u;
+        const int zx = Dx2 - 1 - tx0, zy = Dy2 - 1 - ty0, xl = csx - 2 - tx0, yl = csy - 2 - ty0;
+        const uint32_t ws8 = 8u * (uint32_t)p.sat_ws;
+        const unsigned char *sb = reinterpret_cast<const unsigned char *>(sat_win + (size_t)(wv0 + ty0) * p.sat_ws + (wu0 + tx0));
+#pragma unroll
+        for (int m = 0; m < 2; m++) {
+            SatT q[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if (!((bands_t >> (4 * m + i)) & 1u)) continue;
+                uint32_t o[4];
+                sat_cell_corners(16 * wave + n, 16 * m + 4 * i + h, CW, xl, yl, zx, zy, ws8, o);
+#pragma unroll
+                for (int c = 0; c < 4; c++) q[i][c] = *reinterpret_cast<const SatT *>(sb + o[c]);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if (!((bands_t >> (4 * m + i)) & 1u)) continue;
+                int s, ss;
+                sat_u8_sums(q[i][3] - q[i][1] - q[i][2] + q[i][0], s, ss);
+                asm volatile("" : "+v"(s), "+v"(ss));         // (formed here: the finish carries two registers per cell, not eight)
+                boxb[m][i] = s; boxq[m][i] = ss;
+            }
+        }
+    } else {
         const Bands<CW, KCW, KCV> &bd = kBands<CW, KCW, KCV>;
         v4i hb[KCW];
 #pragma unroll
@@ -812,7 +851,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         }
     }
 
-    if constexpr (C::REC) {      // (formed here: left alone, the compiler sinks these sums into the finish's skippable bands and carries their byte planes there)
+    if constexpr (C::REC && !C::BOXT) {      // (formed here: left alone, the compiler sinks these sums into the finish's skippable bands and carries their byte planes there)
 #pragma unroll
         for (int m = 0; m < 2; m++)
 #pragma unroll
@@ -872,7 +911,8 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_mx(MatchU8Args p
         // outside the record's climb area (the scans are confined to it, best-of-pivots reads end positions of scans, the fit reads
         // visited cells), so the bands that miss its rows -- all eight in a wave whose columns miss it -- are left as the tile's bytes
         uint32_t bands = 0xffu;
-        if constexpr (C::REC) {
+        if constexpr (C::BOXT) bands = bands_t;
+        else if constexpr (C::REC) {
             const uint32_t ar = area_w >> 8, w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tix >> 6));
             const uint32_t x0 = ar & 31u, x1 = (ar >> 5) & 31u, y0 = (ar >> 10) & 31u, y1 = (ar >> 15) & 31u;
             bands = (w >= (x0 >> 4) && w <= (x1 >> 4)) ? ((2u << (y1 >> 2)) - (1u << (y0 >> 2))) & 0xffu : 0u;
@@ -1271,17 +1311,25 @@ static hipError_t launch_form(const MatchU8Args &a, hipStream_t stream)
     }
 }
 
+template <bool BOXT>
 static hipError_t launch_rec_form(const MatchU8Args &a, hipStream_t stream)
 {
     switch (a.ocw) {
-    case 7: return mx::launch_one<mx::RecCfg<7>>(a, stream);
-    case 15: return mx::launch_one<mx::RecCfg<15>>(a, stream);
-    case 16: return mx::launch_one<mx::RecCfg<16>>(a, stream);
-    case 30: return mx::launch_one<mx::RecCfg<30>>(a, stream);
-    case 32: return mx::launch_one<mx::RecCfg<32>>(a, stream);
-    case 40: return mx::launch_one<mx::RecCfg<40>>(a, stream);
+    case 7: return mx::launch_one<mx::RecCfg<7, BOXT>>(a, stream);
+    case 15: return mx::launch_one<mx::RecCfg<15, BOXT>>(a, stream);
+    case 16: return mx::launch_one<mx::RecCfg<16, BOXT>>(a, stream);
+    case 30: return mx::launch_one<mx::RecCfg<30, BOXT>>(a, stream);
+    case 32: return mx::launch_one<mx::RecCfg<32, BOXT>>(a, stream);
+    case 40: return mx::launch_one<mx::RecCfg<40, BOXT>>(a, stream);
     default: return hipErrorInvalidValue;
     }
+}
+
+bool mx_box_table_on()
+{
+    // tuning / A-B: 0 = the record forms compute the window-side box sums by MFMA, as the other forms do
+    static const int on = getenv("MIMC3_MX_BOX_TABLE") ? atoi(getenv("MIMC3_MX_BOX_TABLE")) : 1;
+    return on != 0;
 }
 
 bool u8_advance_on()
@@ -1331,7 +1379,7 @@ hipError_t launch_match_mx(MatchU8Args a, int32_t *lists, hipStream_t stream)
     if (u8_point_records_on()) { a.point_recs = u8_list_recs(lists, a.N); a.rest_recs = u8_list_recs(lists, a.N) + (size_t)a.N; }
     hipError_t e = launch_u8_classify(a, lists, u8_advance_on(), mx_area_on(), stream);
     if (e == hipSuccess) e = mx::classify_stats(a, lists, stream);
-    if (e == hipSuccess) e = a.point_recs ? launch_rec_form(a, stream) : launch_form<false, false>(a, stream);
+    if (e == hipSuccess) e = a.point_recs ? (mx_box_table_on() ? launch_rec_form<true>(a, stream) : launch_rec_form<false>(a, stream)) : launch_form<false, false>(a, stream);
     a.point_list = nullptr; a.point_count = nullptr; a.point_recs = nullptr;
     a.point_flags = a.mx_flags;
     if (e == hipSuccess && a.mx_wn_on) { a.flag_value = kMxWn; e = launch_form<true, false>(a, stream); }

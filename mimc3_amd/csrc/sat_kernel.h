@@ -48,6 +48,30 @@ __device__ __forceinline__ T sat_box(const T *__restrict__ S, int Ws, int x, int
     return r1[w] - r0[w] - r1[0] + r0[0];
 }
 
+// The window-side box of one cell of the matrix-core clean form's tile (match_mx_kernel.hip, RecCfg), as the byte offsets of its four
+// table corners from the entry of the tile's pixel (0, 0); ws8 = the table's pitch in bytes.  Cell (rx, ry) of the tile owns the cw x cw
+// box whose top-left tile pixel is (rx, ry).  T4: tile column zx and tile row zy -- the search area's last column and row -- are never
+// written and count as zeros, while the table holds the plane's real pixels there, so a box that reaches them ends in front of them:
+// its far corner is clamped to (zx, zy).  Reachable cells (rx <= xl = zx - cw + 1, ry <= yl = zy - cw + 1) touch at most that column
+// and row themselves.  A cell beyond them is never read: it takes the box of the last reachable column / row, so that its corners
+// stay inside the search area (hence the table) and its sums stay those of an ordinary box.  o = (top-left, top-right, bottom-left,
+// bottom-right); the box sum is o[3] - o[1] - o[2] + o[0] of the entries, as in sat_box
+__device__ __forceinline__ void sat_cell_corners(int rx, int ry, int cw, int xl, int yl, int zx, int zy, uint32_t ws8, uint32_t (&o)[4])
+{
+    const int x = min(rx, max(xl, 0)), y = min(ry, max(yl, 0));
+    const int w = max(min(cw, zx - x), 0), h = max(min(cw, zy - y), 0);
+    o[0] = __umul24((uint32_t)y, ws8) + 8u * (uint32_t)x;           // (24-bit factors: y, h < 128, and a table row is far below 16 MB)
+    o[1] = o[0] + 8u * (uint32_t)w;
+    o[2] = o[0] + __umul24((uint32_t)h, ws8);
+    o[3] = o[2] + 8u * (uint32_t)w;
+}
+// sum b and sum b^2 of a box from its packed u8 query (exact up to 81^2 pixels, see above)
+__device__ __forceinline__ void sat_u8_sums(unsigned long long q, int &s, int &ss)
+{
+    s = (int)((uint32_t)q & ((1u << kSatSqShift8) - 1u));
+    ss = (int)((uint32_t)(q >> kSatSqShift8) & ((1u << (kSatNullShift8 - kSatSqShift8)) - 1u));
+}
+
 // Null count of a w x h box of a u8 plane from its packed table, exact for ANY box size.  The packed fields of one query are exact up to
 // 8,224 pixels (sum b < 2^21; beyond that the field above takes a carry and the null count comes back off by it -- a window of
 // 16,384 - carry nulls would read as null-free).  Larger boxes are cut into sub-boxes of at most 64 x 64 pixels, one per lane, and the
