@@ -1,5 +1,5 @@
-"""GPU: the run-time-ocw matrix-core searches -- match_ncc_full_chip_class ("u8_mfma_chip"), match_ncc_full_chip_planes ("u16_mfma_chip")
-and match_ncc_wide_class beyond +-15 px ("u8_mfma_wide") -- at every pixel phase of chip and window origin with every null class, with
+"""GPU: the run-time-ocw matrix-core searches -- match_ncc_full_chip_class ("u8_mfma_chip"), match_ncc_full_chip_planes ("u16_mfma_chip"),
+match_ncc_wide_class beyond +-15 px ("u8_mfma_wide") and match_ncc_wide_planes beyond +-15 px ("u16_mfma_wide") -- at every pixel phase of chip and window origin with every null class, with
 one null at every position that a byte mask or a chunk boundary can get wrong, with search boxes at the end of the zero-bordered plane
 and at fractional coordinates.
 
@@ -25,8 +25,7 @@ def api():
 
 
 # ---- 1. every phase pair with every null class ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("part", list(cp.PARTS))
-@pytest.mark.parametrize("case", cp.PHASE_CASES, ids=[cp.case_id(c) for c in cp.PHASE_CASES])
+@pytest.mark.parametrize("case,part", cp.PHASE_PARTS, ids=[f"{cp.case_id(c)}-{p}" for c, p in cp.PHASE_PARTS])
 def test_every_phase_with_every_null_class(api, case, part):
     """the 64 points of the phase fixture at the four offsets in u: with the a-priori shift, without it, and two calls swapped"""
     entry, kind, ocw, radius = case
@@ -34,7 +33,7 @@ def test_every_phase_with_every_null_class(api, case, part):
     calls = cp.phase_calls(f)
     with api.Context(0) as ctx:
         ctx.set_images(f.i0, f.i1)
-        for k in cp.PARTS[part]:
+        for k in cp.part_calls(part):
             offset, shift, swap = calls[k]
             o_rec, o_surf = cp.phase_oracle(case, k)
             cp.check_call(ctx, entry, f, f.xy, radius, offset, shift, swap, o_rec, o_surf,
@@ -61,7 +60,7 @@ def test_one_null_at_every_mask_and_chunk_boundary(api, case):
 @pytest.mark.parametrize("case", cp.PLANE_END_CASES, ids=[cp.case_id(c) for c in cp.PLANE_END_CASES])
 def test_search_boxes_that_end_in_the_last_rows_and_columns_of_the_plane(api, case):
     """A check that nothing is disturbed, not a check of values, as tests/test_pixel_phases.py makes it for match_ncc_full: the tile loads
-    of all three kernels are clamped to the plane (tlim); the wide kernel's last partial tile reaches furthest past the box.  Two points
+    of all four kernels are clamped to the plane (tlim); the wide kernel's last partial tile reaches furthest past the box.  Two points
     whose box ends in the plane's last row, or in its last column at the last of the four offsets, are appended to the fixture's.  Such a
     box lies wholly in the zero border, so both come back -3, and every other point's record, candidates and surface are byte for byte
     what they are without them."""
@@ -121,3 +120,19 @@ def test_the_u8_pair_through_the_u16_kernel_is_the_u8_kernels_bytes(api):
             for x, y, name in zip(a, b, ("record", "candidates", "surface")):
                 assert_bits_equal(x, y, f"call {k}: {name}")
             cp.vs_oracle(b, *cp.phase_oracle(case, k), shift, 7, 4, f"call {k}: the u16 kernel vs the oracle")
+
+
+def test_the_u8_pair_through_the_wide_u16_kernel_is_the_wide_u8_kernels_bytes(api):
+    """mode 1 of match_ncc_wide_planes takes an 8-bit pair: the phase fixture's u8 pair through both wide kernels, the same bytes"""
+    case = ("wide", "u8", 10, 16)
+    f = cp.phase_fixture(case)
+    calls = cp.phase_calls(f)
+    with api.Context(0) as ctx:
+        ctx.set_images(f.i0, f.i1)
+        for k in (3, 8):
+            offset, shift, swap = calls[k]
+            a = cp.search(ctx, "wide", f.xy, offset, 10, 16, 4, shift, swap)
+            b = cp.search(ctx, "wplanes", f.xy, offset, 10, 16, 4, shift, swap)
+            for x, y, name in zip(a, b, ("record", "candidates", "surface")):
+                assert_bits_equal(x, y, f"call {k}: {name}")
+            cp.vs_oracle(b, *cp.phase_oracle(case, k), shift, 16, 4, f"call {k}: the wide u16 kernel vs the oracle")

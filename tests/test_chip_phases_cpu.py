@@ -1,15 +1,20 @@
-"""CPU: the fixtures of tests/chip_phase_common.py qualified, over exactly the calls tests/test_chip_phases.py makes.
+"""CPU: the fixtures of tests/chip_phase_common.py qualified, over exactly the calls tests/test_chip_phases.py and
+tests/test_chip_phases_acc.py make.
 
   * every case of section 1 reaches every (chip phase, window phase, null class) cell -- a condition on the fixture: if it does not hold,
     change the fixture, never the condition; its points are live, and a chip or window read one pixel aside changes every surface;
   * every case of section 2 holds exactly one null per point, where the list says, and moving that null by one pixel changes the surface;
     the wide kernel's per-tile null query, restated, finds each planted null in exactly the tile windows the intervals say;
-  * the comparison the GPU tests use rejects an oracle surface whose chip was read one pixel aside, and one with a null left unmasked."""
+    on the u16 planes every tile of the grid has a null in the first and last column and row of its window and one a pixel outside;
+  * the comparison the GPU tests use rejects an oracle surface whose chip was read one pixel aside, and one with a null left unmasked;
+  * the judge of the accumulating forms (chip_phase_common.acc_judge) takes NumpyStack fed the oracle's layer, and rejects a stack into
+    which the layer went twice -- as a layer, or cell by cell behind one layer count -- and a layer whose chip was read one pixel aside."""
 import numpy as np
 import pytest
 
 import chip_phase_common as cp
 from phase_common import fractional, plane_end_points, search_shifts, trunc
+from stack_common import NumpyStack, refused_of
 from u8_advance_common import BORDER
 
 PHASE_IDS = [cp.case_id(c) for c in cp.PHASE_CASES]
@@ -28,11 +33,20 @@ def test_every_phase_pair_occurs_with_every_null_class(case):
     cells = cp.call_cells(f, radius, [c for c in calls if not c[2]])
     assert all(cells[(a, b, null)] >= 1 for a in range(4) for b in range(4) for null in range(4)), \
         [k for k in ((a, b, null) for a in range(4) for b in range(4) for null in range(4)) if cells[k] < 1]
-    if entry == "planes":
+    if entry in ("planes", "wplanes"):
         par = {(a & 1, b & 1, null) for (a, b, null), n in cells.items() if n}
         assert len(par) == 16
     sw = cp.call_cells(f, radius, [c for c in calls if c[2]])
     assert len({k[:2] for k in sw}) >= 8                        # (the swapped calls: at least two of the four window phases)
+
+
+def test_the_gpu_tests_parts_make_every_call_of_every_case_once():
+    """a case in halves (chip_phase_common.HALVES) makes the ten calls that the parts of PARTS make: the conditions below, which run
+    over PARTS, are conditions on the GPU test's own calls"""
+    for case in cp.PHASE_CASES:
+        made = sorted(k for c, p in cp.PHASE_PARTS if c == case for k in cp.part_calls(p))
+        assert made == list(range(10)) == sorted(k for p in cp.PARTS for k in cp.PARTS[p]), case
+    assert len(cp.PHASE_PARTS) == 3 * len(cp.PHASE_CASES) + 2 * len(cp.HALVED_CASES) and set(cp.HALVED_CASES) <= set(cp.PHASE_CASES)
 
 
 def test_the_grids_beyond_16_px_keep_odd_spacings_and_boxes_apart():
@@ -130,7 +144,7 @@ def test_a_null_moved_by_one_pixel_changes_the_surface(case):
         assert (surf[k].view(np.uint32) != base[k].view(np.uint32)).any(), (k, null)        # and the null shows at all
 
 
-@pytest.mark.parametrize("case", [c for c in cp.SWEEP_CASES if c[0] == "wide"], ids=[i for i, c in zip(SWEEP_IDS, cp.SWEEP_CASES) if c[0] == "wide"])
+@pytest.mark.parametrize("case", [c for c in cp.SWEEP_CASES if c[0] in cp.WIDE], ids=[i for i, c in zip(SWEEP_IDS, cp.SWEEP_CASES) if c[0] in cp.WIDE])
 def test_the_tile_query_finds_each_null_in_exactly_its_tile_windows(case):
     entry, kind, ocw, radius = case
     fx = cp.sweep_fixture(case)
@@ -138,9 +152,9 @@ def test_the_tile_query_finds_each_null_in_exactly_its_tile_windows(case):
     win = cp.tile_windows(ocw, radius)
     nt = (S + 31) // 32
     assert len(win) == nt and win[0][0] == 0 and win[-1][1] == cw + 2 * radius - 1          # the windows cover the box, end to end
-    for k, (side, x, y) in enumerate(fx.nulls):
-        tiles = cp.wn_tiles(fx, k)
-        assert tiles == (set() if side == "chip" else cp.tiles_holding(x, y, ocw, radius)), (k, side, x, y, tiles)
+    seen = cp.wn_tiles_of_every_point(fx)
+    for (side, x, y), tiles in zip(fx.nulls, seen):
+        assert tiles == (set() if side == "chip" else cp.tiles_holding(x, y, ocw, radius)), (side, x, y, tiles)
     # the four positions per tile and axis are in the list, and lie on the side of the window's edge they are meant for
     box = {(x, y) for s, x, y in fx.nulls if s == "box"}
     for t, (a, b) in enumerate(win):
@@ -152,7 +166,26 @@ def test_the_tile_query_finds_each_null_in_exactly_its_tile_windows(case):
                 assert pts, (t, axis, c)
                 for p in pts:
                     assert (t in {tile[axis] for tile in cp.tiles_holding(p[0], p[1], ocw, radius)}) == inside, (t, axis, c, p)
-    assert any(len(cp.wn_tiles(fx, k)) == 1 for k in range(len(fx.nulls))) and any(len(cp.wn_tiles(fx, k)) >= 2 for k in range(len(fx.nulls)))
+    assert any(len(t) == 1 for t in seen) and any(len(t) >= 2 for t in seen)
+    if entry != "wplanes":
+        return
+    # every tile of the grid, on each axis: a point whose null sits IN the first | last column (row) of the tile's window, and the query
+    # of that tile sees it; a point whose null sits one pixel OUTSIDE it (where the box has that pixel), and the query does not
+    point = {(x, y): k for k, (s, x, y) in enumerate(fx.nulls) if s == "box"}
+    met = set()
+    for tx, ty, axis, inside, (x, y) in cp.tile_edge_nulls(ocw, radius):
+        a, b = win[(tx, ty)[axis]]
+        c, d = win[(ty, tx)[axis]]
+        edge = (x, y)[axis]
+        assert edge in ((a, b) if inside else (a - 1, b + 1)) and c <= (x, y)[1 - axis] <= d, (tx, ty, axis, inside, x, y)
+        assert ((tx, ty) in seen[point[(x, y)]]) == inside, (tx, ty, axis, inside, x, y)
+        met.add((tx, ty, axis, edge - a if edge <= a else edge - b + 2))
+    for ty in range(nt):
+        for tx in range(nt):
+            for axis in (0, 1):
+                a, b = win[(tx, ty)[axis]]
+                want = {0, 2} | ({-1} if a > 0 else set()) | ({3} if b + 1 < cw + 2 * radius else set())
+                assert {m[3] for m in met if m[:3] == (tx, ty, axis)} == want, (tx, ty, axis)
 
 
 # ---- 3. plane ends, fractions ------------------------------------------------------------------------------------------------------------------
@@ -190,7 +223,7 @@ def as_a_kernel_would_return(surf, rec, shift, radius, npeaks):
     return t_rec, t_cand, surf
 
 
-@pytest.mark.parametrize("case", [("class", "u8", 10, 7), ("planes", "12bit", 57, 7), ("wide", "u8", 7, 32)], ids=cp.case_id)
+@pytest.mark.parametrize("case", [("class", "u8", 10, 7), ("planes", "12bit", 57, 7), ("wide", "u8", 7, 32), ("wplanes", "12bit", 7, 32)], ids=cp.case_id)
 def test_the_comparison_rejects_a_chip_read_one_pixel_aside(case):
     entry, kind, ocw, radius = case
     f = cp.phase_fixture(case)
@@ -207,7 +240,7 @@ def test_the_comparison_rejects_a_chip_read_one_pixel_aside(case):
             cp.vs_oracle(as_a_kernel_would_return(p_surf, p_rec, shift, radius, 4), o_rec, o_surf, shift, radius, 4, "chip one pixel aside")
 
 
-@pytest.mark.parametrize("case", [("class", "u8", 10, 7), ("planes", "spread12", 57, 7), ("wide", "u8", 25, 32)], ids=cp.case_id)
+@pytest.mark.parametrize("case", [("class", "u8", 10, 7), ("planes", "spread12", 57, 7), ("wide", "u8", 25, 32), ("wplanes", "spread12", 25, 32)], ids=cp.case_id)
 def test_the_comparison_rejects_one_null_left_unmasked(case):
     """one planted null read as a pixel (of 1, the darkest there is) and not masked: one point's surface differs, and the comparison of
     the whole launch fails -- for the first chip null (column 0), the last (CW - 1), and the last box null"""
@@ -227,3 +260,86 @@ def test_the_comparison_rejects_one_null_left_unmasked(case):
         assert differs[k] and sum(differs) == 1
         with pytest.raises(AssertionError):
             cp.vs_oracle(as_a_kernel_would_return(p_surf, p_rec, fx.shift, fx.R, 4), o_rec, o_surf, fx.shift, fx.R, 4, "a null left unmasked")
+
+
+# ---- the judge of the accumulating forms ------------------------------------------------------------------------------------------------------
+def finishes_of(stack):
+    return [stack.finish(k, mc) for k, mc in cp.ACC_FINISHES]
+
+
+def test_the_accumulating_cases_are_search_cases_and_reach_every_instantiation():
+    """every ACC case is a case of the search lists (it reads that case's oracle); per entry KCW = (CW + 15 + 63) / 64, the K chunks per
+    chip row and 16 x 16 cell tile that the kernels are instantiated on, is 1, 2 and 3"""
+    assert set(cp.ACC_PHASE_CASES) <= set(cp.PHASE_CASES) and set(cp.ACC_SWEEP_CASES) <= set(cp.SWEEP_CASES)
+    assert set(cp.ACC_PARTS) <= set(cp.PARTS)
+    for entry in cp.ENTRIES:
+        assert sorted((2 * c[2] + 1 + 15 + 63) // 64 for c in cp.ACC_PHASE_CASES if c[0] == entry) == [1, 2, 3]
+        assert sum(1 for c in cp.ACC_SWEEP_CASES if c[0] == entry) == 1
+
+
+@pytest.mark.parametrize("part", cp.ACC_PARTS)
+@pytest.mark.parametrize("case", cp.ACC_PHASE_CASES, ids=[cp.case_id(c) for c in cp.ACC_PHASE_CASES])
+def test_one_oracle_layer_in_numpy_stack_is_what_the_acc_judge_takes(case, part):
+    """NumpyStack fed the oracle's surface and refused_of(its record): the mean at (4, 1) is that surface at finite cells and NaN
+    elsewhere, one layer per point that is not refused, all NaN at (0, 2) -- and the judge takes it.  Every call holds points of the clean
+    form (no null in chip or box) and of the masked form"""
+    entry, kind, ocw, radius = case
+    f = cp.phase_fixture(case)
+    calls = cp.phase_calls(f)
+    for k in cp.PARTS[part]:
+        offset, shift, swap = calls[k]
+        o_rec, o_surf = cp.phase_oracle(case, k)
+        stack = NumpyStack(f.xy.shape[0], radius, shift).add(o_surf, refused_of(o_rec))
+        (rec, cand, lay, mean), (rec2, cand2, lay2, mean2) = finishes_of(stack)
+        fin = np.isfinite(o_surf)
+        assert np.array_equal(mean.view(np.uint32)[fin], o_surf.view(np.uint32)[fin]) and np.isnan(mean[~fin]).all()
+        assert np.array_equal(lay, (o_rec[:, 2] != -3).astype(np.uint16)) and np.isnan(mean2).all() and (lay == 1).sum() >= 48
+        cp.acc_judge(finishes_of(stack), o_rec, o_surf, radius, shift, "NumpyStack over the oracle's layer")
+        null = cp.call_cells(f, radius, [calls[k]])
+        # (one point of each is what it takes to launch both forms; four of 64 is more than an accident of the grid)
+        assert sum(n for c, n in null.items() if c[2] == 0) >= 4 and sum(n for c, n in null.items() if c[2] != 0) >= 4
+
+
+@pytest.mark.parametrize("case", cp.ACC_SWEEP_CASES, ids=[cp.case_id(c) for c in cp.ACC_SWEEP_CASES])
+def test_every_sweep_point_is_the_masked_forms_and_the_acc_judge_takes_the_oracle(case):
+    fx = cp.sweep_fixture(case)
+    nc, nb = cp.null_counts(fx)
+    assert ((nc > 0) | (nb > 0)).all()
+    o_rec, o_surf = cp.sweep_oracle(fx)
+    stack = NumpyStack(len(fx.nulls), fx.R, fx.shift).add(o_surf, refused_of(o_rec))
+    assert (stack.lay == 1).all()
+    cp.acc_judge(finishes_of(stack), o_rec, o_surf, fx.R, fx.shift, "NumpyStack over the oracle's layer")
+
+
+@pytest.mark.parametrize("case", [("class", "u8", 10, 7), ("planes", "12bit", 57, 7), ("wide", "u8", 10, 16), ("wplanes", "12bit", 25, 32)], ids=cp.case_id)
+def test_the_acc_judge_rejects_a_layer_added_twice_and_a_chip_read_one_pixel_aside(case):
+    entry, kind, ocw, radius = case
+    f = cp.phase_fixture(case)
+    calls = cp.phase_calls(f)
+    n = f.xy.shape[0]
+    q0, q1 = cp.integer_images(f)
+    for k in (2, 8):                                            # forward and swapped
+        offset, shift, swap = calls[k]
+        o_rec, o_surf = cp.phase_oracle(case, k)
+        refused = refused_of(o_rec)
+        twice = NumpyStack(n, radius, shift).add(o_surf, refused).add(o_surf, refused)
+        with pytest.raises(AssertionError):
+            cp.acc_judge(finishes_of(twice), o_rec, o_surf, radius, shift, "the layer twice")
+        # the cells twice behind ONE layer count -- what a point finished by the clean AND the masked launch would leave: the mean at
+        # (4, 1), the counts, record and candidates are the right ones, and only min_count 2 shows it
+        cells = NumpyStack(n, radius, shift).add(o_surf, refused).add(o_surf, np.ones(n, bool))
+        right = finishes_of(NumpyStack(n, radius, shift).add(o_surf, refused))
+        for a, b in zip(finishes_of(cells)[0], right[0]):
+            assert a.tobytes() == b.tobytes()
+        with pytest.raises(AssertionError, match="min_count 2"):
+            cp.acc_judge(finishes_of(cells), o_rec, o_surf, radius, shift, "the cells twice")
+        one = np.zeros(n, bool)
+        one[int(np.flatnonzero(~refused)[5])] = True                # ... and of ONE point only
+        s1 = np.where(one[:, None], o_surf, np.float32(np.nan))
+        cells = NumpyStack(n, radius, shift).add(o_surf, refused).add(s1, np.ones(n, bool))
+        with pytest.raises(AssertionError, match="min_count 2"):
+            cp.acc_judge(finishes_of(cells), o_rec, o_surf, radius, shift, "one point's cells twice")
+        aside = (q0, np.roll(q1, 1, axis=1)) if swap else (np.roll(q0, 1, axis=1), q1)
+        p_rec, p_surf = cp.oracle_search(f, radius, offset, shift, swap, images=aside)
+        with pytest.raises(AssertionError):
+            cp.acc_judge(finishes_of(NumpyStack(n, radius, shift).add(p_surf, refused_of(p_rec))), o_rec, o_surf, radius, shift, "chip one pixel aside")
