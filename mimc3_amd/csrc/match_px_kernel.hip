@@ -82,7 +82,19 @@ __device__ __forceinline__ uint32_t dot4(uint32_t a, uint32_t b, uint32_t c) { r
 __device__ __forceinline__ uint32_t alignb(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
 // 0x80 in every byte that is non-zero
 __device__ __forceinline__ uint32_t nz80(uint32_t v) { return (((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v) & 0x80808080u; }
-__device__ __forceinline__ uint32_t ff_from80(uint32_t t) { return t | (t - (t >> 7)); }
+// 0xFF in every byte that is non-zero, exactly, in four instructions (widening nz80's flags, t | (t - (t >> 7)), made it six):
+//   bytes 0 and 2: (byte + 0x7fff) inside its own half-word has bit 15 set iff byte >= 1 (at most 0x80fe: nothing leaves the half-word);
+//   bytes 1 and 3: the half-word (hi << 8 | lo) + 0x7f00, SATURATING, has bit 15 set iff hi >= 1 (hi == 0: at most 0x7fff;
+//                  hi >= 1: at least 0x8000, and the clamp at 0xffff keeps the bit where the plain sum would wrap);
+//   v_perm_b32's selectors 8 / 9 / 10 / 11 replicate bit 15 / 31 / 47 / 63 of {o, e} over a byte: byte k of the result <- byte k's flag.
+typedef unsigned short nzff_us2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t nzff(uint32_t v)
+{
+    const uint32_t e = (v & 0x00ff00ffu) + 0x7fff7fffu;
+    const nzff_us2_t k = {0x7f00, 0x7f00};
+    const uint32_t o = __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(nzff_us2_t, v), k));
+    return __builtin_amdgcn_perm(o, e, 0x0b090a08u);
+}
 
 template <int LPC>
 __device__ __forceinline__ uint32_t group_sum(uint32_t v)
@@ -187,26 +199,30 @@ struct PxU8 {
             if (static_pad) acc.sxy = dot4(a, bw, acc.sxy); else acc.sy = dot4(a, bw, acc.sy);
             return;
         }
+        // The masked bodies need two things of the window dword: which of its bytes are non-zero, and `a` with the bytes under its
+        // nulls cleared (`am`).  nzff gives the byte mask in four instructions; the masked chip sums both come from `am` (sx is its
+        // dot product with ones), so no 0/1 form of the mask is needed, and the pixel count of a six-sum body is a population count
+        // of the mask, EIGHT per pixel (n_units takes the factor out of a lane's partial count).
         if (MODE == M_WN) {     // the chip has no null (its pad bytes are 0): only the window's nulls mask
-            const uint32_t t = nz80(bw);
-            acc.sx = dot4(a, t >> 7, acc.sx);
-            acc.sxx = dot4(a & ff_from80(t), a, acc.sxx);
+            const uint32_t am = a & nzff(bw);
+            acc.sx = dot4(am, 0x01010101u, acc.sx);
+            acc.sxx = dot4(am, a, acc.sxx);
             acc.sxy = dot4(a, bw, acc.sxy);
             return;
         }
         if (MODE == M_GC && static_pad) {     // null-free chip, row task: the chip mask is the pad mask
-            const uint32_t t = nz80(bw);
-            const uint32_t mb01 = t >> 7, mbff = ff_from80(t);
-            acc.n = dot4(pad01, mb01, acc.n);
-            acc.sx = dot4(a, mb01, acc.sx);
+            const uint32_t mbff = nzff(bw);
+            const uint32_t am = a & mbff;     // (pad bytes of `a` are 0)
+            acc.n += (uint32_t)__popc(padff == 0xffffffffu ? mbff : (mbff & padff));
+            acc.sx = dot4(am, 0x01010101u, acc.sx);
             acc.sy = dot4(pad01, bw, acc.sy);
             acc.sxy = dot4(a, bw, acc.sxy);
-            acc.sxx = dot4(a & mbff, a, acc.sxx);
+            acc.sxx = dot4(am, a, acc.sxx);
             acc.syy = dot4(padff == 0xffffffffu ? bw : (bw & padff), bw, acc.syy);
             return;
         }
         if (OPQ && !(MODE == M_FAST && static_pad)) asm volatile("" : "+v"(a));
-        const uint32_t mf = (MODE == M_FAST && static_pad) ? padff : ff_from80(nz80(a));
+        const uint32_t mf = (MODE == M_FAST && static_pad) ? padff : nzff(a);
         if (MODE == M_FAST) {
             const uint32_t m01 = static_pad ? pad01 : (mf & 0x01010101u);
             const uint32_t mff = static_pad ? padff : mf;
@@ -214,21 +230,23 @@ struct PxU8 {
             acc.syy = dot4((static_pad && padff == 0xffffffffu) ? bw : (bw & mff), bw, acc.syy);
             acc.sxy = dot4(a, bw, acc.sxy);
         } else if (MODE == M_CHIPNULL) {
-            acc.sy = dot4(mf & 0x01010101u, bw, acc.sy);
-            acc.syy = dot4(bw & mf, bw, acc.syy);
+            const uint32_t bm = bw & mf;             // the window bytes under valid chip pixels
+            acc.sy = dot4(bm, 0x01010101u, acc.sy);
+            acc.syy = dot4(bm, bw, acc.syy);
             acc.sxy = dot4(a, bw, acc.sxy);
         } else {
-            const uint32_t t = nz80(bw);
-            const uint32_t mb01 = t >> 7, mbff = ff_from80(t);
-            const uint32_t ma01 = mf & 0x01010101u;
-            acc.n = dot4(ma01, mb01, acc.n);
-            acc.sx = dot4(a, mb01, acc.sx);          // a == 0 where the chip pixel is null
-            acc.sy = dot4(ma01, bw, acc.sy);         // bw == 0 where the window pixel is null
+            const uint32_t mbff = nzff(bw);
+            const uint32_t am = a & mbff, bm = bw & mf;     // a == 0 where the chip pixel is null, bw == 0 where the window pixel is
+            acc.n += (uint32_t)__popc(mbff & mf);
+            acc.sx = dot4(am, 0x01010101u, acc.sx);
+            acc.sy = dot4(bm, 0x01010101u, acc.sy);
             acc.sxy = dot4(a, bw, acc.sxy);
-            acc.sxx = dot4(a & mbff, a, acc.sxx);
-            acc.syy = dot4(bw & mf, bw, acc.syy);
+            acc.sxx = dot4(am, a, acc.sxx);
+            acc.syy = dot4(bm, bw, acc.syy);
         }
     }
+    // a lane's partial pixel count of a six-sum body, out of the units the tasks count in (8 per pixel: whole 0xFF bytes)
+    __device__ static __forceinline__ uint32_t n_units(uint32_t n) { return n >> 3; }
     template <int LPC> __device__ static __forceinline__ Sum gsum(Sum v) { return group_sum<LPC>(v); }
     typedef uint32_t Store;                                    // how a reduced sum is parked in LDS
     __device__ static __forceinline__ Store bits(Sum v) { return v; }
@@ -336,6 +354,7 @@ struct PxU16 {
             acc.syy = dot2(bw & mf, bw, (uint32_t)acc.syy);
         }
     }
+    __device__ static __forceinline__ uint32_t n_units(uint32_t n) { return n; }
     template <int LPC> __device__ static __forceinline__ Sum gsum(Sum v)
     {
         v = dpp_add_u64(v, 0); v = dpp_add_u64(v, 1); v = dpp_add_u64(v, 2); v = dpp_add_u64(v, 3);
@@ -477,6 +496,7 @@ struct PxF32 {
             acc.sxx += (double)(a2 * a2); acc.syy += (double)(b2 * b2); acc.sxy += (double)(a2 * b2);
         }
     }
+    __device__ static __forceinline__ uint32_t n_units(uint32_t n) { return n; }
     template <int LPC> __device__ static __forceinline__ Sum gsum(Sum v)
     {
         v = dpp_add_f64(v, 0); v = dpp_add_f64(v, 1); v = dpp_add_f64(v, 2); v = dpp_add_f64(v, 3);
@@ -714,6 +734,7 @@ __device__ __forceinline__ AccT<typename C::P::Sum> eval_round(const unsigned ch
         else P::template task<MODE, C::OPQ>(acc, av, 0, 0, false, bw, pt.thr);   // tail tasks: pad/null masks come from the chip dword itself
     }
     if constexpr (MODE == M_XY && MIMC3_XY_ACC >= 2) { acc.sxy += acc.sy - sy_in; acc.sy = sy_in; }   // fold the second chain (sy carried the caller's corrections in)
+    if (MODE == M_GENERAL || MODE == M_GC) acc.n = P::n_units(acc.n);   // (the 8-bit policies count eight per pixel)
     if (!REDUCE) return acc;                                        // lane-local partial sums (the caller reduces / parks them)
     acc.sxy = P::template gsum<C::LPC>(acc.sxy);
     if (MODE != M_XY && MODE != M_WN) { acc.sy = P::template gsum<C::LPC>(acc.sy); acc.syy = P::template gsum<C::LPC>(acc.syy); }
