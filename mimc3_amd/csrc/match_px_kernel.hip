@@ -25,7 +25,8 @@
 //     (v_alignbyte_b32 when a dword holds several pixels), accumulates, and the LPC lanes of a cell are reduced with DPP row
 //     operations (groups of 32 / 64 lanes: LDS atomics into the cell's parking slot);
 //   * per-cell modes: XY (null-free box and chip: only sxy is accumulated, the rest is constants + table), WN / GC / GENERAL
-//     (window nulls: three or six masked sums), CHIPNULL, sparse corrections over null lists on the big chips;
+//     (window nulls: three or six masked sums), CHIPNULL, XYC / WNC (chip nulls: the XY / WN task plus corrections from the chip
+//     dwords that hold a null), sparse corrections over null lists on the big chips;
 //   * NCC cache: one f32 word per compact cell (or, COMPACT form for large windows, a 16-bit entry + value slots);
 //   * speculative parallel climb + exact replay of the reference's sequential hill climb (:691-753).
 // DESIGN.md section 4.1 describes each step and what was measured for it.
@@ -47,6 +48,9 @@
 #endif                          // (PxCfg::SAT_DEFER), 0 / 1 = never / always (A/B builds)
 #ifndef MIMC3_WN
 #define MIMC3_WN 1              // window-null cells of a clean chip: three sums + table instead of six
+#endif
+#ifndef MIMC3_CN_SKIP
+#define MIMC3_CN_SKIP 1         // chips with nulls (PxCfg::CN_SKIP): the unmasked bodies + corrections from the chip dwords that hold a null
 #endif
 #ifndef MIMC3_NULL_FLAGS
 #define MIMC3_NULL_FLAGS 1      // sparse-correction configs: skip the window-null walk of dirty-list boxes that hold no null (table look-up)
@@ -139,7 +143,13 @@ __device__ __forceinline__ void argmax_row16(float &v, int &i)
 //            table's (a null is a zero in both sums); sx, sxx (chip pixels over the non-null window pixels) and sxy are accumulated
 //   GC       GENERAL for a null-free chip: the chip-side masks are the compile-time pad masks of the row tasks, nothing is
 //            derived from the chip dwords -- so nothing chip-derived has to stay in registers across the evaluation loops
-enum { M_FAST = 0, M_CHIPNULL = 1, M_GENERAL = 2, M_XY = 3, M_WN = 4, M_GC = 5 };
+//   XYC      CHIPNULL for planes with a table (PxCfg::CN_SKIP): XY's task on every dword; the window pixels under the chip's nulls,
+//            which the table's box sums hold and the NCC loop skips, are summed (csy, csyy) only at the task indices of the point's
+//            flag mask -- the dwords of the chip that hold a null at all
+//   WNC      GENERAL for a chip with nulls, planes with a table: WN's task on every dword (`a` is 0 at a chip null, so sx, sxx, sxy need
+//            the window's mask only); the flagged indices add csy, csyy and J, the pixels that are null on both sides:
+//            n = pixels - chip nulls - nulls of the box + J
+enum { M_FAST = 0, M_CHIPNULL = 1, M_GENERAL = 2, M_XY = 3, M_WN = 4, M_GC = 5, M_XYC = 6, M_WNC = 7 };
 
 template <class S> struct AccT { uint32_t n; S sx, sy, sxx, syy, sxy; };
 
@@ -244,6 +254,20 @@ struct PxU8 {
             acc.sxx = dot4(am, a, acc.sxx);
             acc.syy = dot4(bm, bw, acc.syy);
         }
+    }
+    // The chip-null correction of one FLAGGED dword task (XYC / WNC): za is 0xFF in the valid chip bytes (`pff`: not the pad bytes of a
+    // row's last dword, nothing in a tail lane without a dword) that are null; the window bytes under them leave sy, syy; WIN: the
+    // bytes that are null in the window too were taken out of n twice (eight per pixel, like the six-sum bodies' count).  The mask is
+    // derived on the spot: the empty asm keeps the compiler from hoisting nineteen of them out of the evaluation loops.
+    template <bool WIN, bool OPQ>
+    __device__ static __forceinline__ void cn_task(Sum &csy, Sum &csyy, uint32_t &cj, uint32_t a, uint32_t pff, uint32_t bw)
+    {
+        if (OPQ) asm volatile("" : "+v"(a));
+        const uint32_t za = ~nzff(a) & pff;
+        const uint32_t bz = bw & za;
+        csy = dot4(bz, 0x01010101u, csy);
+        csyy = dot4(bz, bw, csyy);
+        if (WIN) cj += (uint32_t)__popc(za & ~nzff(bw));
     }
     // a lane's partial pixel count of a six-sum body, out of the units the tasks count in (8 per pixel: whole 0xFF bytes)
     __device__ static __forceinline__ uint32_t n_units(uint32_t n) { return n >> 3; }
@@ -586,6 +610,16 @@ struct PxCfg {
     // but on 8-bit planes only where a lane owns two or more full chip rows and there are no null lists (u8 ocw 16: 3.14 -> 3.08 ms;
     // ocw 7 / 15 / 40: +1.4 / +1.1 / +4 %, the byte masks being cheap next to the second table look-up)
     static constexpr bool WN = P_::WN && (!std::is_same<P_, PxU8>::value || ((SHORT ? 1 : CW / LPC_) >= 2 && !((LPC_ >= 64) && P_::INTEGER)));
+    // Chips with nulls on the unmasked bodies (XYC / WNC) with corrections from the flagged dwords only: the one-wave 33-pixel u8
+    // kernel, whose lanes own two full chip rows and one tail dword (19 task indices, all four lane groups hold the same chip).
+    // CN_ELIGIBLE says where the bodies exist; CN_SKIP switches them on.  By measurement only in the point-record form behind
+    // u8_classify (PxRec: the rest list of a u8 step, every point null-affected; BASELINE C2's rest-list launch 1,380 -> 1,321 us).
+    // The memory-header twin of the register-tiled kernel alone (u8px) runs every point, null-free ones included, and came out
+    // slower with the bodies compiled in (2.430 -> 2.504 ms on C2, 1.970 -> 2.126 ms on a null-free pair that never enters them:
+    // the larger kernel's register allocation, 16 bytes of scratch), so it keeps CHIPNULL / GENERAL.  ocw 7 / 15 have no A/B of
+    // their own yet and keep them too.
+    static constexpr bool CN_ELIGIBLE = MIMC3_CN_SKIP && std::is_same<P_, PxU8>::value && NW_ == 1 && OCW_ == 16 && LPC_ == 16 && !CHL_ && !MANY_;
+    static constexpr bool CN_SKIP = false;
     static constexpr bool kOpqSmall = MIMC3_OPQ_SMALL && ((std::is_same<P_, PxU8>::value && OCW_ == 16) || (std::is_same<P_, PxU8o>::value && (OCW_ == 15 || OCW_ == 16)));
     static constexpr bool OPQ = LPC_ >= 64 || kOpqSmall;
     // Big chips with exact integer sums: a cell whose box (or whose chip) holds null pixels is evaluated as the FAST body
@@ -634,6 +668,7 @@ struct PxCfg {
 template <class C0>
 struct PxRec : C0 {
     static constexpr bool REC = true;
+    static constexpr bool CN_SKIP = C0::CN_ELIGIBLE;
 };
 static constexpr int kLwCap = 1024;    // window-null list entries (x | y << 16); more -> the point falls back to GENERAL
 static constexpr int kLcCap = 512;     // chip-null list entries
@@ -654,9 +689,15 @@ __device__ __forceinline__ AccT<typename C::P::Sum> eval_round(const unsigned ch
                                           const uint32_t (&AT)[C::TT > 0 ? C::TT : 1],
                                           const int (&toff)[C::TT > 0 ? C::TT : 1],
                                           AccT<typename C::P::Sum> acc = AccT<typename C::P::Sum>{0, 0, 0, 0, 0, 0},
-                                          const unsigned char *CH = nullptr)
+                                          const unsigned char *CH = nullptr, uint32_t cmask = 0u)
 {
     typedef typename C::P P;
+    // XYC / WNC: the XY / WN task on every dword; bit t of the wave-uniform `cmask` says that the chip dword of task t (row tasks
+    // i * GPR + j, then the tail tasks) holds a null in some lane -- a scalar branch per task of the unrolled list
+    constexpr bool kCnMode = MODE == M_XYC || MODE == M_WNC;
+    static_assert(!kCnMode || (!C::CHIP_LDS && !C::SHORT && C::RF * C::GPR + C::TT <= 32), "flag mask: one bit per task index");
+    [[maybe_unused]] typename P::Sum csy = 0, csyy = 0;
+    [[maybe_unused]] uint32_t cj = 0u;
     [[maybe_unused]] const typename P::Sum sy_in = acc.sy;
     const int X = pt.sh + cx;                                       // pixel offset of the box inside the LDS row
     const uint32_t s = (uint32_t)((X & (P::G - 1)) * P::BPP);       // byte phase inside the first dword
@@ -705,8 +746,11 @@ __device__ __forceinline__ AccT<typename C::P::Sum> eval_round(const unsigned ch
             const uint32_t bw = (P::G > 1) ? alignb(w[j + (P::G > 1 ? 1 : 0)], w[j], s) : w[j];
             const uint32_t p01 = (j == C::GPR - 1) ? C::LAST01 : 0x01010101u;
             const uint32_t pff = (j == C::GPR - 1) ? C::LASTFF : 0xffffffffu;
-            if constexpr (MODE == M_XY) P::template task<M_XY, C::OPQ>(acc, A[i][j], 0, 0, (MIMC3_XY_ACC < 2) || ((i * C::GPR + j) & 1) == 0, bw, pt.thr);
-            else P::template task<MODE, C::OPQ>(acc, A[i][j], p01, pff, true, bw, pt.thr);
+            if constexpr (MODE == M_XY || MODE == M_XYC) P::template task<M_XY, C::OPQ>(acc, A[i][j], 0, 0, (MIMC3_XY_ACC < 2) || ((i * C::GPR + j) & 1) == 0, bw, pt.thr);
+            else P::template task<MODE == M_WNC ? M_WN : MODE, C::OPQ>(acc, A[i][j], p01, pff, true, bw, pt.thr);
+            if constexpr (kCnMode) {
+                if ((cmask >> (i * C::GPR + j)) & 1u) P::template cn_task<MODE == M_WNC, C::OPQ>(csy, csyy, cj, A[i][j], pff, bw);
+            }
         }
     }
     }
@@ -720,7 +764,7 @@ __device__ __forceinline__ AccT<typename C::P::Sum> eval_round(const unsigned ch
             const int tt = l + C::LPC * k;
             av = tt < C::REM * C::GPR ? *reinterpret_cast<const volatile uint32_t *>(CH + (C::RF * C::LPC + tt / C::GPR) * C::CPITCH + 4 * (tt % C::GPR)) : 0u;
         }
-        if constexpr (MODE == M_XY) {
+        if constexpr (MODE == M_XY || MODE == M_XYC) {
             // only sxy: the chip dword is 0 in its pad bytes, at its nulls and in the lanes past the last task -- no mask matters
             P::template task<M_XY, C::OPQ>(acc, av, 0, 0, (MIMC3_XY_ACC < 2) || (k & 1) == 0, bw, pt.thr);
         }
@@ -731,14 +775,23 @@ __device__ __forceinline__ AccT<typename C::P::Sum> eval_round(const unsigned ch
             if (k == C::TT - 1 && (C::REM * C::GPR) % C::LPC != 0) bwt = (l + C::LPC * k < C::REM * C::GPR) ? bw : 0u;
             P::template task<M_FAST, C::OPQ>(acc, av, P::BPP == 1 ? 0x01010101u : 0x00010001u, 0xffffffffu, true, bwt, pt.thr);
         }
-        else P::template task<MODE, C::OPQ>(acc, av, 0, 0, false, bw, pt.thr);   // tail tasks: pad/null masks come from the chip dword itself
+        else P::template task<MODE == M_WNC ? M_WN : MODE, C::OPQ>(acc, av, 0, 0, false, bw, pt.thr);   // tail tasks: pad/null masks come from the chip dword itself
+        if constexpr (kCnMode) {
+            if ((cmask >> (C::RF * C::GPR + k)) & 1u) {
+                const int tt = l + C::LPC * k;                          // (the lanes past the last task hold a zero dword that is no chip pixel)
+                const uint32_t tff = tt < C::REM * C::GPR ? ((tt % C::GPR == C::GPR - 1) ? C::LASTFF : 0xffffffffu) : 0u;
+                P::template cn_task<MODE == M_WNC, C::OPQ>(csy, csyy, cj, av, tff, bw);
+            }
+        }
     }
-    if constexpr (MODE == M_XY && MIMC3_XY_ACC >= 2) { acc.sxy += acc.sy - sy_in; acc.sy = sy_in; }   // fold the second chain (sy carried the caller's corrections in)
+    if constexpr ((MODE == M_XY || MODE == M_XYC) && MIMC3_XY_ACC >= 2) { acc.sxy += acc.sy - sy_in; acc.sy = sy_in; }   // fold the second chain (sy carried the caller's corrections in)
     if (MODE == M_GENERAL || MODE == M_GC) acc.n = P::n_units(acc.n);   // (the 8-bit policies count eight per pixel)
+    if constexpr (kCnMode) { acc.sy = csy; acc.syy = csyy; acc.n = P::n_units(cj); }   // the corrections travel in the slots of the sums they correct (n: J)
     if (!REDUCE) return acc;                                        // lane-local partial sums (the caller reduces / parks them)
     acc.sxy = P::template gsum<C::LPC>(acc.sxy);
     if (MODE != M_XY && MODE != M_WN) { acc.sy = P::template gsum<C::LPC>(acc.sy); acc.syy = P::template gsum<C::LPC>(acc.syy); }
-    if (MODE == M_WN) { acc.sx = P::template gsum<C::LPC>(acc.sx); acc.sxx = P::template gsum<C::LPC>(acc.sxx); }
+    if (MODE == M_WN || MODE == M_WNC) { acc.sx = P::template gsum<C::LPC>(acc.sx); acc.sxx = P::template gsum<C::LPC>(acc.sxx); }
+    if (MODE == M_WNC) acc.n = group_sum<C::LPC>(acc.n);
     if (MODE == M_GENERAL || MODE == M_GC) {
         acc.n = group_sum<C::LPC>(acc.n); acc.sx = P::template gsum<C::LPC>(acc.sx); acc.sxx = P::template gsum<C::LPC>(acc.sxx);
     }
@@ -1313,6 +1366,30 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
     }
     const uint32_t NV = (uint32_t)(C::NPX - exc_chip);       // chip pixels that take part: n, sx, sxx are constants when the box is clean
     const int clean_mode = (exc_chip == 0) ? M_FAST : M_CHIPNULL;
+    // Chip with nulls (CN_SKIP configs): bit t of the wave-uniform flag mask <=> the chip dword of task index t holds a null among
+    // its VALID bytes in some lane (every lane group holds the same chip).  Pad bytes of a row's last dword and the zero dwords of
+    // the tail lanes past the last task are no nulls.  (maybe_excl's false alarm needs a real zero in a lower byte, and the pad
+    // bytes are the upper ones: exact per dword.)
+    constexpr bool kCn = kSat && C::CN_SKIP && !((C::LPC >= 32) && P::INTEGER);
+    [[maybe_unused]] uint32_t cn_mask = 0u;
+    if constexpr (kCn) {
+        if (exc_chip != 0) {
+#pragma unroll
+            for (int i = 0; i < C::RF; i++) {
+#pragma unroll
+                for (int j = 0; j < GPR; j++) {
+                    const bool z = P::maybe_excl(A[i][j], (j == GPR - 1) ? C::LASTFF : 0xffffffffu, pt.thr);
+                    cn_mask |= (__ballot(z) != 0ull) ? (1u << (i * GPR + j)) : 0u;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < C::TT; k++) {
+                const int tt = l + C::LPC * k;
+                const uint32_t tff = tt < C::REM * GPR ? ((tt % GPR == GPR - 1) ? C::LASTFF : 0xffffffffu) : 0u;
+                cn_mask |= (__ballot(P::maybe_excl(AT[k], tff, pt.thr)) != 0ull) ? (1u << (C::RF * GPR + k)) : 0u;
+            }
+        }
+    }
     MIMC3_STAMP(1)
     if (p.debug_stop == 2) { if (tid == 0) p.out[3 * (size_t)gidx] = (float)((uint32_t)P::bits(SX) + (uint32_t)P::bits(SXX) + bad_chip + A[0][0] + AT[0]); return; }
     __syncthreads();   // single-wave workgroup: orders the LDS stores above before the reads below
@@ -1466,6 +1543,10 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
         // dirty boxes of a null-free chip, planes with a table: the WN body (three sums) instead of the six-sum GENERAL body --
         // except where a cell of the wave's round touches the never-written last row / column (T4: the table does not know it)
         const bool wn_ok = kSat && C::WN && MIMC3_WN && dirty_list && exc_chip == 0;
+        // chip with nulls (CN_SKIP configs): dirty boxes run the WNC body under the same T4 rule, clean boxes the XYC body; both
+        // finish from the table
+        const bool cn_ok = kCn && dirty_list && exc_chip != 0;
+        const bool cn_clean = kCn && mode == M_CHIPNULL;
         // SPARSE: the lane's slice of the null lists lives in registers for the whole call (lists are per point)
         uint32_t ew[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, ec[2] = {0xffffffffu, 0xffffffffu};
         if constexpr (C::SPARSE) {
@@ -1491,7 +1572,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
             [[maybe_unused]] SatT cellQ{}, q00{}, q01{}, q10{}, q11{};
             [[maybe_unused]] int cellZ = 0;
             if constexpr (kSat) {
-                const bool need = mode == M_FAST || (C::SPARSE && sparse_on) || (dirty_list && wn_ok);
+                const bool need = mode == M_FAST || (C::SPARSE && sparse_on) || (dirty_list && wn_ok) || cn_ok || cn_clean;
                 if (need && tid < nb) {
                     const uint32_t pk = ids[dir * (b0 + tid)];
                     const SatT *r0 = sat_win + (size_t)(wv0 + (int)((pk >> 8) & 0xffu)) * p.sat_ws + (wu0 + (int)(pk & 0xffu)), *r1 = r0 + (size_t)CW * p.sat_ws;
@@ -1604,13 +1685,19 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
                 }
                 if (!done) {
                     if (mode == M_FAST) acc = eval_round<C, kSat ? M_XY : M_FAST, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH);
-                    else if (mode == M_CHIPNULL) acc = eval_round<C, M_CHIPNULL, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH);
+                    else if (mode == M_CHIPNULL) {
+                        if constexpr (kCn) acc = eval_round<C, M_XYC, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH, cn_mask);
+                        else acc = eval_round<C, M_CHIPNULL, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH);
+                    }
                     else {
                         if constexpr (kSat) {
                             const bool t4 = on && !full_win && (cx == pt.csx - 2 || cy == pt.csy - 2);
-                            wn_round = wn_ok && __ballot(t4) == 0ull;
+                            wn_round = (wn_ok || cn_ok) && __ballot(t4) == 0ull;
                         }
-                        if (kSat && wn_round) acc = eval_round<C, kSat ? M_WN : M_GENERAL, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH);
+                        if (kCn && wn_round && cn_ok) {
+                            if constexpr (kCn) acc = eval_round<C, M_WNC, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH, cn_mask);
+                        }
+                        else if (kSat && wn_round) acc = eval_round<C, kSat ? M_WN : M_GENERAL, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH);
                         else if (MIMC3_GC && exc_chip == 0) acc = eval_round<C, M_GC, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH);   // null-free chip: nothing derived from the chip dwords
                         else acc = eval_round<C, M_GENERAL, !kAPark>(W, pt, cx, cy, l, A, AT, toff, AccT<Sum>{0, 0, 0, 0, 0, 0}, CH);
                     }
@@ -1640,7 +1727,9 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
                     } else {
                         if (mode != M_GENERAL) { acc.n = NV; acc.sx = SX; acc.sxx = SXX; }
                         if (on && l == 0) {
-                            if (kSat && wn_round) { sp[1] = P::bits(acc.sx); sp[3] = P::bits(acc.sxx); sp[5] = P::bits(acc.sxy); }
+                            if (cn_clean) { sp[2] = P::bits(acc.sy); sp[4] = P::bits(acc.syy); sp[5] = P::bits(acc.sxy); }   // csy, csyy, sxy
+                            else if (kSat && wn_round && !cn_ok) { sp[1] = P::bits(acc.sx); sp[3] = P::bits(acc.sxx); sp[5] = P::bits(acc.sxy); }
+                            // (a WNC cell fills the six words: J, sx, csy, sxx, csyy, sxy)
                             else { sp[0] = (Store)acc.n; sp[1] = P::bits(acc.sx); sp[2] = P::bits(acc.sy); sp[3] = P::bits(acc.sxx); sp[4] = P::bits(acc.syy); sp[5] = P::bits(acc.sxy); }
                         }
                     }
@@ -1659,7 +1748,7 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
                 // slots touches the T4 row / column; the finishing lanes all sit in wave 0)
                 bool wn_cell = false;
                 if constexpr (kSat) {
-                    if (wn_ok) {
+                    if (wn_ok || cn_ok) {
                         const bool t4 = !full_win && (cx == pt.csx - 2 || cy == pt.csy - 2);
                         const unsigned long long tm = __ballot(t4);
                         wn_cell = ((tm >> (tid & ~(C::CPR - 1))) & ((1ull << C::CPR) - 1ull)) == 0ull;
@@ -1670,7 +1759,14 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
                         const int z = kSatZ ? cellZ : P::sat_nulls(cellQ);
                         if (p.stats && z == 0) atomicAdd(&p.stats[kStatW * (size_t)blockIdx.x + 15], 1ull);
                         P::sat_win_sums(ty, tyy, cellQ, z, kb, C::NPX, sc_win);
-                        v[0] = (Store)(uint32_t)(C::NPX - z); v[2] = P::bits(ty); v[4] = P::bits(tyy);
+                        bool plain = true;
+                        if constexpr (kCn) {
+                            if (cn_ok) {      // WNC: the slot holds J and the window sums under the chip's nulls
+                                v[0] = (Store)((uint32_t)(C::NPX - exc_chip - z) + (uint32_t)v[0]); v[2] = P::bits(ty) - v[2]; v[4] = P::bits(tyy) - v[4];
+                                plain = false;
+                            }
+                        }
+                        if (plain) { v[0] = (Store)(uint32_t)(C::NPX - z); v[2] = P::bits(ty); v[4] = P::bits(tyy); }
                     }
                 }
                 if constexpr (kAPark) {
@@ -1697,6 +1793,13 @@ __global__ __launch_bounds__(C::NT, C::MINW) void match_ncc_dlc_px(MatchU8Args p
                         Sum ty = 0, tyy = 0;
                         P::sat_win_sums(ty, tyy, cellQ, 0, kb, C::NPX, sc_win);
                         v[0] = (Store)NV; v[1] = P::bits(SX); v[2] = P::bits(ty); v[3] = P::bits(SXX); v[4] = P::bits(tyy);
+                    }
+                    if constexpr (kCn) {
+                        if (cn_clean) {       // XYC: the box sums less the window pixels under the chip's nulls
+                            Sum ty = 0, tyy = 0;
+                            P::sat_win_sums(ty, tyy, cellQ, 0, kb, C::NPX, sc_win);
+                            v[0] = (Store)NV; v[1] = P::bits(SX); v[2] = P::bits(ty) - v[2]; v[3] = P::bits(SXX); v[4] = P::bits(tyy) - v[4];
+                        }
                     }
                 }
                 store_ncc(cx, cy, P::ncc(v, sc_chip, sc_win, ka, kb));
