@@ -945,7 +945,7 @@ int mimc3_match_ncc_pyramid_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t 
  *     the coarser levels never compute candidates.  A point that gets the all-NaN record gets all-NaN candidate slots.
  *   Refusals: those of mimc3_match_ncc_pyramid, with the class rule above in place of "not 8-bit"; npeaks outside 0..8, or cand NULL with
  *   npeaks > 0 / not NULL with npeaks = 0: MIMC3_EINVAL.
- *   Not covered: several devices, a candidates-over-variants driver (api.Context.full_candidates stays single-level). */
+ *   Not covered: several devices, a candidates-over-variants driver of its own (api.Context.full_candidates(levels) goes through mimc3_match_ncc_pyramid_chip). */
 int mimc3_match_ncc_pyramid_dn(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                                const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t levels,
                                int32_t npeaks /*0 = record only*/, int32_t swap, float *out /*[N][8] host*/,
@@ -986,7 +986,7 @@ int mimc3_match_ncc_pyramid_dn_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32
  *     among the largest finite cells).  On an integer-class pair whose float and integer levels coincide, mode 1 returns the bytes of
  *     mimc3_match_ncc_pyramid_dn.
  *   Refusals: those of mimc3_match_ncc_pyramid_dn without its class rule; mode outside 0..1: MIMC3_EINVAL.
- *   Not covered: several GPUs; a candidates-over-variants driver (api.Context.full_candidates stays single-level); MIMC3_hip_offsets
+ *   Not covered: several GPUs; a candidates-over-variants driver of its own (api.Context.full_candidates(levels) goes through mimc3_match_ncc_pyramid_chip); MIMC3_hip_offsets
  *   on float TIFFs. */
 int mimc3_match_ncc_pyramid_any(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
                                 const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t levels,
@@ -997,6 +997,53 @@ int mimc3_match_ncc_pyramid_any(mimc3_ctx *ctx, const double *xyuvav, int32_t N,
 int mimc3_match_ncc_pyramid_any_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                     const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
                                     int32_t mode, float *d_out, float *d_cand, int32_t *d_shift_out /*or NULL*/, void *stream);
+/* ---- Coarse-to-fine exhaustive search at ANY chip half-width 1 <= ocw <= mimc3_full_chip_max_ocw() (80), on the run-time-ocw kernels:
+ *      the reference's chip sets 7/10/15, 11/14 and 30/60/80 coarse to fine, and the 8-bit, 12-bit and filtered pairs on the matrix
+ *      cores on every level.  The arguments of mimc3_match_ncc_pyramid_any.  R 1..15 (every level keeps it), levels 1..5, npeaks 0..8.
+ *
+ *   mimc3_match_ncc_pyramid's definition word for word -- p_l = (u0 >> l, v0 >> l), d_{L-1} = floor((D + 2^{L-2}) / 2^{L-1}),
+ *   d_{l-1} = 2 (d_l + s) with the level's arg-max cell s (a status -4 peak counts) or 2 d_l without one, shift_out = d_0 - offset, the
+ *   +-2^24 bound on the starting displacement, the refusal of a coarsest level smaller than a chip (at the real ocw), the all-NaN record
+ *   (and all-NaN candidate slots) for a level-0 box beyond the 256-px zero border, one stream and no host round trip.
+ *   Levels.  Those of the pair's class -- the existing level sets, so levels built by mimc3_match_ncc_pyramid_dn / _pyramid_any serve
+ *     this entry and the other way round:
+ *       8-bit             the u8 levels with their u8 tables
+ *       scaled-integer    the u16 levels with both tables
+ *       integral f32      the integer-reduced f32 levels of mimc3_match_ncc_pyramid_dn
+ *       any other pair    the float levels of mimc3_match_ncc_pyramid_any
+ *   Kernel.  ONE kernel serves all levels of a call; mimc3_ctx_last_path reports it (mimc3_pyramid_chip_path gives the same value without
+ *     a device: pair_class 0 8-bit, 1 scaled-integer, 2 integral f32, 3 any other; 0 for anything outside the table):
+ *       pair class        mode 0                                                                         mode 1
+ *       8-bit             at one of the six (7, 15, 16, 30, 32, 40): 6, exactly mimc3_match_ncc_pyramid_dn;   12 at every ocw
+ *                         any other ocw: 12 (match_full_chip_u8_kernel.hip)
+ *       scaled-integer    13 (match_full_chip_u16_kernel.hip) at every ocw, the six included             13 at every ocw
+ *       integral f32      at the six: 8, mimc3_match_ncc_pyramid_dn; else 11 (match_full_chip_kernel.hip)    11 at every ocw
+ *       any other         at the six: 9, mimc3_match_ncc_pyramid_any(mode 0); else 11                      11 at every ocw
+ *     (The u16 matrix-core kernel never runs on an 8-bit pair here: the context keeps one integer level set per pair.  The mode-0 choice
+ *      for a scaled-integer pair at the six is measured: on BASELINE C2 as 12-bit DN every pass of this entry was faster than every
+ *      pass of mimc3_match_ncc_pyramid_dn at each of the six -- 25.9 against 104.4 ms at ocw 16, L = 3.)
+ *     Levels L-1 .. 1 run that kernel's record-only form that also stores the arg-max cell (the matrix-core kernels as a clean launch
+ *     over all points plus a masked launch over the points that hold a null: every point gets exactly one cell, or -1, per level);
+ *     level 0 is the same kernel's record form, with candidates if asked, at shift = shift_out.
+ *   Consequences.  On the three integer classes every sum is an exact integer in every kernel, so record, candidates and shift_out are
+ *     the bytes of mimc3_match_ncc_pyramid_dn wherever that entry takes the call (the six), in both modes; at a chip size outside the six,
+ *     record and candidates equal mimc3_match_ncc_full_chip_planes(mode 0, shift = shift_out) wherever that entry accepts the input.  On
+ *     the float class, mode 0 at the six is mimc3_match_ncc_pyramid_any(mode 0); elsewhere shift_out equals a hand-made chain of
+ *     mimc3_match_ncc_full_chip(mode 1, surf) calls over the float levels (arg-max of surf: the lowest k among the largest finite cells)
+ *     and the record equals mimc3_match_ncc_full_chip(mode 1, shift = shift_out).
+ *   Refusals: those of mimc3_match_ncc_pyramid_any, with ocw outside 1..mimc3_full_chip_max_ocw() in place of "not one of the six".
+ *   Not covered: R > 15 on any level; several GPUs; MIMC3_hip_offsets (the command line keeps refusing levels > 1 at a chip size
+ *   outside the six, 16-bit TIFFs, filter, peaks, fb and R > 15: the library entry is the way). */
+int mimc3_match_ncc_pyramid_chip(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                                 const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t levels,
+                                 int32_t npeaks /*0 = record only*/, int32_t swap, int32_t mode, float *out /*[N][8] host*/,
+                                 float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/, int32_t *shift_out /*[N][2] host or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_pyramid_any_dev. */
+int mimc3_match_ncc_pyramid_chip_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                     const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
+                                     int32_t mode, float *d_out, float *d_cand, int32_t *d_shift_out /*or NULL*/, void *stream);
+/* Host query (no device): the mimc3_ctx_last_path value the table above gives, 0 for anything outside it. */
+int mimc3_pyramid_chip_path(int32_t pair_class, int32_t ocw, int32_t mode);
 /* FLOAT level `level` (1..4) of the pair the context currently matches on, whatever its class (mimc3_match_ncc_pyramid_any's levels), as
  * pixel values: out0, out1 [H >> level][W >> level] host.  Builds the float levels that are missing.  A level whose image would be
  * empty: MIMC3_EINVAL.  mimc3_ctx_get_pyramid_level keeps serving the integer levels, and keeps refusing a pair of no class. */

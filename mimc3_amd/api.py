@@ -137,6 +137,9 @@ _lib.mimc3_match_ncc_pyramid_any.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, 
                                              _f32p, _vp, _i32p]
 _lib.mimc3_match_ncc_pyramid_any_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]
+_lib.mimc3_match_ncc_pyramid_chip.argtypes = _lib.mimc3_match_ncc_pyramid_any.argtypes
+_lib.mimc3_match_ncc_pyramid_chip_dev.argtypes = _lib.mimc3_match_ncc_pyramid_any_dev.argtypes
+_lib.mimc3_pyramid_chip_path.argtypes = [C.c_int32, C.c_int32, C.c_int32]
 _lib.mimc3_ctx_get_pyramid_level.argtypes = [_vp, C.c_int32, _f32p, _f32p]
 _lib.mimc3_ctx_get_pyramid_level_any.argtypes = [_vp, C.c_int32, _f32p, _f32p]
 _lib.mimc3_prior_shift.argtypes = [_f64p, C.c_int32, C.c_float, C.c_float, _i32p]
@@ -281,6 +284,12 @@ def _search_arrays(what, xyuvav, shift, npeaks=0, radius=0, surface=False, fb=Fa
 def wide_max_radius(ocw):
     """The largest radius match_ncc_wide takes at this chip size (mimc3_wide_max_radius); 0 for an ocw it does not take."""
     return int(_lib.mimc3_wide_max_radius(int(ocw)))
+
+
+def pyramid_chip_path(pair_class, ocw, mode):
+    """The last_path of match_ncc_pyramid_chip for a pair class (0 8-bit, 1 scaled-integer, 2 integral f32, 3 any other), a chip
+    half-width and a mode (mimc3_pyramid_chip_path; no device): 6 / 12, 13, 8 / 11, 9 / 11 -- 0 for anything outside the table."""
+    return int(_lib.mimc3_pyramid_chip_path(int(pair_class), int(ocw), int(mode)))
 
 
 def full_chip_max_ocw():
@@ -1064,7 +1073,7 @@ class Context:
         return n.value, r.value, k.value
 
     def full_candidates(self, xyuvav, offset, vec_ocw, radius, npeaks, kernels=(None,) + CLI_KERNELS, shift=None, any_pair=False,
-                        any_ocw=False):
+                        any_ocw=False, levels=1):
         """The candidates of the exhaustive search over image variants and chip sizes -> dp float32[ndp][N][3], ndp = len(kernels) *
         len(vec_ocw) * npeaks <= 64: for each variant in order (None = the raw pair, else filter_images(kernel)) and each ocw one
         forward match_ncc_full_dn call, its candidates stacked variant-major, then ocw, then peak rank -- what
@@ -1072,7 +1081,13 @@ class Context:
         The pair is left unfiltered.  any_pair: the calls are match_ncc_full_any's (mode 0), so a float pair goes through every variant.
         any_ocw: the calls are match_ncc_full_chip's (mode 0), so vec_ocw may hold any chip half-width 1 .. full_chip_max_ocw() -- the
         reference's (7, 10, 15, 11) and (14, 30, 60, 80) -- and any pair; at a chip size in range other than the six built ones they are
-        match_ncc_full_chip_planes's (mode 0: an 8-bit or scaled-integer pair on the matrix cores, the same bytes)."""
+        match_ncc_full_chip_planes's (mode 0: an 8-bit or scaled-integer pair on the matrix cores, the same bytes).
+        levels > 1: every (variant, ocw) call is match_ncc_pyramid_chip's (mode 0) over that many levels, whatever any_pair and any_ocw
+        say -- any chip half-width 1 .. full_chip_max_ocw(), any pair; filter, then reduce: the levels are rebuilt after each
+        filter_images.  levels = 1 runs exactly the single-level calls above."""
+        levels = int(levels)
+        if levels < 1:
+            raise ValueError("full_candidates: levels must be at least 1")
         match = self.match_ncc_full_chip if any_ocw else self.match_ncc_full_any if any_pair else self.match_ncc_full_dn
         six = (7, 15, 16, 30, 32, 40)
         kernels = tuple(kernels); vec_ocw = tuple(int(o) for o in vec_ocw); npeaks = int(npeaks)
@@ -1088,6 +1103,9 @@ class Context:
                 if k is not None:
                     self.filter_images(k)
                 for ocw in vec_ocw:
+                    if levels > 1:
+                        blocks.append(self.match_ncc_pyramid_chip(xyuvav, offset, ocw, radius, levels, npeaks, shift=shift)[1])
+                        continue
                     call = self.match_ncc_full_chip_planes if any_ocw and ocw not in six and 1 <= ocw <= full_chip_max_ocw() else match
                     blocks.append(call(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
         finally:
@@ -1154,6 +1172,26 @@ class Context:
         _check(_lib.mimc3_match_ncc_pyramid_any_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius, levels,
                                                     npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_shift_out or None, stream),
                "match_ncc_pyramid_any_dev")
+
+    def match_ncc_pyramid_chip(self, xyuvav, offset, ocw, radius, levels, npeaks=0, shift=None, swap=False, mode=0):
+        """Coarse-to-fine exhaustive search at any chip half-width 1 .. full_chip_max_ocw() (mimc3_match_ncc_pyramid_chip) on any pair ->
+        (float32[N][8] record, float32[npeaks][N][3] candidates or None when npeaks == 0, int32[N][2] shift_out).  The levels are those
+        of the pair's class (match_ncc_pyramid_dn's, or match_ncc_pyramid_any's float levels); one run-time-ocw kernel searches all of
+        them -- the matrix cores on an 8-bit or scaled-integer pair -- see pyramid_chip_path.  mode 0 keeps the templated kernels at the
+        six built chip sizes except on a scaled-integer pair; mode 1 runs the run-time-ocw kernel at every ocw."""
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_pyramid_chip", xyuvav, shift, npeaks=npeaks)
+        sh_out = np.empty((n, 2), np.int32)
+        _check(_lib.mimc3_match_ncc_pyramid_chip(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh),
+                                                 ocw, radius, levels, int(npeaks), 1 if swap else 0, int(mode), out,
+                                                 _ptr(cand), sh_out), "match_ncc_pyramid_chip")
+        return out, cand, sh_out
+
+    def match_ncc_pyramid_chip_dev(self, d_xyuvav, n, offset, ocw, radius, levels, npeaks, d_out, d_cand=0, d_shift=0, d_shift_out=0, stream=0,
+                                   swap=False, mode=0):
+        """Device-pointer variant (enqueue only): as match_ncc_pyramid_any_dev."""
+        _check(_lib.mimc3_match_ncc_pyramid_chip_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius, levels,
+                                                     npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_shift_out or None, stream),
+               "match_ncc_pyramid_chip_dev")
 
     def get_pyramid_level_any(self, level):
         """FLOAT level `level` (1..4) of the pair currently matched on, whatever its class (match_ncc_pyramid_any's levels: the mean of

@@ -202,8 +202,17 @@ struct SearchRules {
                                         // matrix-core wide kernel on the u16 planes (mode 1 always, an 8-bit pair included; mode 0 where
                                         // wide_planes_mode0 names it or the float wide kernel does not take the call), up to
                                         // wide_u16_max_radius(ocw); R <= 15 is the chip_planes entry
+    bool pyramid_chip = false;          // with pyramid and any_ocw (mimc3_match_ncc_pyramid_chip): the kernel is pyramid_chip_kernel's, one of the
+                                        // run-time-ocw kernels wherever the table in include/mimc3_hip.h names it, on the levels of the pair's class
 };
 enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8, ChipU16, WideU8, WideU16 };       // last_path 6 .. 15
+constexpr int kSearchKernels = 10;
+// The level sets of a coarse-to-fine search: u8 planes with u8 tables, u16 planes with both tables, f32 planes reduced on their integers
+// with 16-byte tables, f32 planes reduced as floats (no tables).  A pair has one integer class, so the first three share mimc3_ctx::pyr.
+// level_class(kernel) is the set a kernel reads when nothing else is said; the run-time-ocw float kernel reads the integral-f32 set as
+// well (its planes alone), which is why plane_set takes the class beside the kernel
+enum LevelClass { kLevelU8, kLevelU16, kLevelF32i, kLevelFloat };
+LevelClass level_class(SearchKernel kernel);
 struct PlaneSet {
     const void *p0, *p1, *sat0, *sat1, *satz0, *satz1;
     int32_t H, W, Wp;
@@ -219,7 +228,10 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
 int search_check_host(const mimc3_ctx *c, const char *entry, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
                       int32_t ocw, int32_t R, bool pyramid = false);
 int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel);
-int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &planes);
+int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &planes);      // (on the levels of level_class(kernel))
+int plane_set(mimc3_ctx *c, SearchKernel kernel, LevelClass levels, int level, PlaneSet &planes);
+// mimc3_match_ncc_pyramid_chip's kernel for a pair class, chip size and mode (the table in include/mimc3_hip.h); false outside the table
+bool pyramid_chip_kernel(PairClass cls, int32_t ocw, int32_t mode, SearchKernel &kernel);
 int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &planes, const SearchCall &call);
 
 // Suspends the context's timing flag for a scope: an entry made of several searches records the events around the whole call, and its

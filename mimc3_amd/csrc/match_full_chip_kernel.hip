@@ -53,6 +53,12 @@ struct Cfg {                                        // (what match_full_tail.h a
     static constexpr bool PEAK = false, MULTI = MULTI_;
     static constexpr int VP = kVP;
 };
+// The record-only form that also leaves the arg-max cell (or -1) in full_peak, where a pyramid's next level takes its search centre from
+// (mimc3_match_ncc_pyramid_chip).  A configuration of its own, as PeakCfg of match_full_f32g_kernel.hip: the two Cfg instantiations keep
+// their names and code; it sums in the order of Cfg<false>
+struct PeakCfg : Cfg<false> {
+    static constexpr bool PEAK = true;
+};
 
 struct Layout {
     int CW, CWP, NCH, PB, BR, lds;
@@ -164,7 +170,7 @@ __global__ __launch_bounds__(kNT) void match_ncc_full_chip(MatchU8Args p, float 
     float *sf = surf ? surf + (size_t)gidx * (size_t)NC : nullptr;
 
     auto no_record = [&](float status) __attribute__((always_inline)) {
-        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_cand_fill<C>(p, gidx, status); }
+        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_peak_store<C>(p, gidx, -1); mx::full_cand_fill<C>(p, gidx, status); }
         if (sf) for (int k = tid; k < NC; k += NT) sf[k] = __builtin_nanf("");
     };
     const double *row = p.xyuvav + (size_t)p.xy_stride * (size_t)gidx + p.xy_col;
@@ -369,8 +375,10 @@ int full_chip_band_rows(int ocw, int R)
 hipError_t launch_match_full_chip(MatchU8Args a, float *surf, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
-    if (!a.p0 || !a.p1 || a.full_peak || a.full_R < 1 || a.full_R > 15 || a.ocw < 1 || a.ocw > kFullChipMaxOcw) return hipErrorInvalidValue;
+    if (!a.p0 || !a.p1 || a.full_R < 1 || a.full_R > 15 || a.ocw < 1 || a.ocw > kFullChipMaxOcw) return hipErrorInvalidValue;
     if (a.full_cand && (a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks)) return hipErrorInvalidValue;
+    if (a.full_peak && (a.full_cand || surf)) return hipErrorInvalidValue;
+    if (a.full_peak) return fchip::launch_one<fchip::PeakCfg>(a, surf, stream);
     if (a.full_cand) return fchip::launch_one<fchip::Cfg<true>>(a, surf, stream);
     return fchip::launch_one<fchip::Cfg<false>>(a, surf, stream);
 }

@@ -123,6 +123,15 @@ template <int KCW_, bool GEN_>
 struct AccCfg : Cfg<KCW_, GEN_, false, false> {
     static constexpr bool ACC = true;
 };
+// The PEAK forms, the record-only forms that also leave every point's arg-max cell k = (su + R)(2R + 1) + (sv + R), or -1 without one, in
+// full_peak, where a pyramid's next level takes its search centre from (mimc3_match_ncc_pyramid_chip; FullPeakCfg of match_mx_kernel.hip).
+// Configurations of their own, as AccCfg: the occupancy targets are the record forms'.  Every point gets exactly one store per search:
+// the clean form writes -1 with the NaN record (a chip outside the level, a box beyond the border) and the cell of a point it finishes,
+// and hands a flagged point over untouched; the masked form writes -1 with its -3 and the cell of a point it finishes
+template <int KCW_, bool GEN_>
+struct PeakCfg : Cfg<KCW_, GEN_, false, false> {
+    static constexpr bool PEAK = true;
+};
 
 __device__ __forceinline__ uint32_t alignb(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
 __device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
@@ -244,7 +253,7 @@ __global__ __launch_bounds__(kNT, C::MINW) void match_ncc_full_chip_u8(MatchU8Ar
     // a point that leaves before its surface exists: the record (NaN or a status), every candidate slot, an all-NaN surface
     auto no_record = [&](float status) __attribute__((always_inline)) {
         if constexpr (C::ACC) { mx::stack_acc_none(p, gidx, tid, status); return; }       // (no cell; the layer counts unless refused)
-        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_cand_fill<C>(p, gidx, status); }
+        if (tid == 0) { mx::full_store(p.out + 8 * (size_t)gidx, status); mx::full_peak_store<C>(p, gidx, -1); mx::full_cand_fill<C>(p, gidx, status); }
         if constexpr (C::SURF) {
             float *sf = p.full_surf + (size_t)gidx * (size_t)NC;
             for (int k = tid; k < NC; k += NT) sf[k] = __builtin_nanf("");
@@ -650,6 +659,27 @@ static hipError_t launch_kcw_acc(const MatchU8Args &a, hipStream_t stream)
     }
 }
 
+template <bool GEN>
+static hipError_t launch_kcw_peak(const MatchU8Args &a, hipStream_t stream)
+{
+    switch (chip_u8_layout(a.ocw).KCW) {
+    case 1: return launch_one<PeakCfg<1, GEN>>(a, stream);
+    case 2: return launch_one<PeakCfg<2, GEN>>(a, stream);
+    case 3: return launch_one<PeakCfg<3, GEN>>(a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// the PEAK forms: the same two launches
+static hipError_t launch_forms_peak(MatchU8Args a, int forms, hipStream_t stream)
+{
+    hipError_t e = hipSuccess;
+    if (forms & 1) e = launch_kcw_peak<false>(a, stream);
+    a.point_flags = a.mx_flags; a.flag_value = kMxNulls;
+    if (e == hipSuccess && (forms & 2)) e = launch_kcw_peak<true>(a, stream);
+    return e;
+}
+
 // the accumulating forms: the same two launches, the clean form's hand-over of flagged points unchanged
 static hipError_t launch_forms_acc(MatchU8Args a, int forms, hipStream_t stream)
 {
@@ -684,13 +714,17 @@ bool full_chip_u8_layout(int ocw, int out[4])
 hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
-    if (!a.p0 || !a.p1 || !a.mx_flags || !a.sat0 || !a.sat1 || a.full_peak || a.full_R < 1 || a.full_R > 15 || a.ocw < 1 || a.ocw > kFullChipMaxOcw)
+    if (!a.p0 || !a.p1 || !a.mx_flags || !a.sat0 || !a.sat1 || a.full_R < 1 || a.full_R > 15 || a.ocw < 1 || a.ocw > kFullChipMaxOcw)
         return hipErrorInvalidValue;
     a.point_flags = nullptr;
     if (forms & kFormsAcc) {            // the stack's planes in the list-mode slots; nothing else is written
-        if (!a.stk_sum || !a.stk_cnt || !a.stk_lay || a.out || a.full_cand || a.full_surf) return hipErrorInvalidValue;
+        if (!a.stk_sum || !a.stk_cnt || !a.stk_lay || a.out || a.full_cand || a.full_surf || a.full_peak) return hipErrorInvalidValue;
         if (a.stk_shift && !mx::stack_acc_scaled_ok(a)) return hipErrorInvalidValue;
         return fchip8::launch_forms_acc(a, forms, stream);
+    }
+    if (a.full_peak) {                  // the arg-max cells: with the record alone
+        if (a.full_cand || a.full_surf) return hipErrorInvalidValue;
+        return fchip8::launch_forms_peak(a, forms, stream);
     }
     if (a.full_cand) {
         if (a.full_npeaks < 1 || a.full_npeaks > kFullMaxPeaks) return hipErrorInvalidValue;

@@ -287,7 +287,7 @@ int wide_max_radius(int ocw);
 int wide_lds_bytes(int ocw, int R);     // the dynamic LDS of a launch at radius R (0 outside 1 .. wide_max_radius(ocw))
 hipError_t launch_match_wide(MatchU8Args a, float *surf, hipStream_t stream);
 // the same search at ANY chip half-width 1 <= a.ocw <= kFullChipMaxOcw (match_full_chip_kernel.hip; mimc3_match_ncc_full_chip): the arguments
-// of launch_match_full_f32g without a.full_peak; a.ocw is a run-time value, the chip is walked in bands of full_chip_band_rows(ocw, R) chip
+// of launch_match_full_f32g, a.full_peak included (not together with full_cand or surf); a.ocw is a run-time value, the chip is walked in bands of full_chip_band_rows(ocw, R) chip
 // rows (the whole chip where it fits), each band within kChipLdsBudget bytes of dynamic LDS.  One launch
 constexpr int kFullChipMaxOcw = 80;
 constexpr int kChipLdsBudget = 79 * 1024;       // two workgroups per CU (160 KB), their static slots included
@@ -295,7 +295,9 @@ int full_chip_band_rows(int ocw, int R);        // 0 outside 1 <= ocw <= kFullCh
 hipError_t launch_match_full_chip(MatchU8Args a, float *surf, hipStream_t stream);
 // the same search at any chip half-width on the u8 planes of an 8-BIT pair, on the matrix cores (match_full_chip_u8_kernel.hip;
 // mimc3_match_ncc_full_chip_class): a.p0 / a.p1 the u8 planes, a.sat0 / a.sat1 their packed tables, a.mx_flags N class bytes, zero before
-// the call; a.full_shift, a.full_R, a.full_cand / a.full_npeaks, a.full_surf and a.out as launch_match_full_mx takes them, no a.full_peak.
+// the call; a.full_shift, a.full_R, a.full_cand / a.full_npeaks, a.full_surf and a.out as launch_match_full_mx takes them; a.full_peak
+// (optional; not together with full_cand, full_surf or the accumulating forms) selects the PEAK forms: every point gets exactly one store,
+// its arg-max cell or -1, from the form that finishes it -- the clean form also for the NaN record, the masked form for its -3.
 // forms: bit 0 the clean form over all points (it flags the points that hold a null), bit 1 the masked form over the flagged points --
 // 3 is the search, 1 and 2 are for timing the forms apart.  Bit 2 (kFormsAcc, with any of the above; this kernel and the three below)
 // selects the ACCUMULATING forms (stack_acc.h): each point's finished surface is added into the stack at a.stk_sum / a.stk_cnt / a.stk_lay
@@ -314,7 +316,7 @@ hipError_t launch_match_full_chip_u8(MatchU8Args a, int forms, hipStream_t strea
 bool full_chip_u16_layout(int ocw, int out[4]);
 hipError_t launch_match_full_chip_u16(MatchU8Args a, int forms, hipStream_t stream);
 // the search beyond +-15 px on the u8 planes of an 8-BIT pair at any chip half-width, on the matrix cores (match_wide_u8_kernel.hip;
-// mimc3_match_ncc_wide_class): the arguments and forms of launch_match_full_chip_u8 with 16 <= a.full_R <= 47 -- that kernel over a grid of
+// mimc3_match_ncc_wide_class): the arguments and forms of launch_match_full_chip_u8 (no PEAK forms: no a.full_peak) with 16 <= a.full_R <= 47 -- that kernel over a grid of
 // 32 x 32 cell tiles, the surface at pitch 96 in LDS bytes of its own, the tails of match_full_tail.h and match_wide_tail.h.
 // wide_u8_max_radius: 47 for 1 <= ocw <= kFullChipMaxOcw, else 0.  wide_u8_layout_query: K chunks per chip row, cell tiles per axis, threads
 // per workgroup, dynamic LDS bytes of a launch at (ocw, R) (false outside 1 .. kFullChipMaxOcw x 16 .. 47), from the constexpr layout the launch uses

@@ -1,6 +1,6 @@
 // search.cpp -- the host layer of the exhaustive-search family of the C ABI (include/mimc3_hip.h): mimc3_match_ncc_full, _full_multi,
 // _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _full_chip_planes, _wide, _wide_class, _wide_planes, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
-// _pyramid_any), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
+// _pyramid_any, _pyramid_chip), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
 // (SearchRules); search_check makes every refusal, pick_kernel selects the kernel, plane_set points at the planes it reads (building
 // them on first use), launch_search is the one place that launches.  The stack's layer adds (stack.cpp) go through the same functions.
 #include <algorithm>
@@ -144,9 +144,38 @@ static bool wide_mode0(int32_t ocw, int32_t R) { return ocw >= 1 && ocw <= kFull
 // 5.0 to 16.9), so no (ocw, R) stays on the float kernel
 static bool wide_planes_mode0(int32_t ocw, int32_t R) { return ocw >= 1 && ocw <= kFullChipMaxOcw && R >= 16 && R <= wide_u16_max_radius(ocw); }
 
+// The coarse-to-fine search at any chip size (mimc3_match_ncc_pyramid_chip) runs ONE kernel on every level of a call, level 0 included,
+// on the levels of the pair's class:
+//   8-bit            mode 0 at one of the six: Mx (the entry is then mimc3_match_ncc_pyramid_dn); any other ocw, and all of mode 1: ChipU8
+//   scaled-integer   ChipU16 in both modes -- in mode 0 at one of the six only where pyramid_chip_u16_at_six says so, else U16
+//   integral f32     mode 0 at one of the six: F32i (mimc3_match_ncc_pyramid_dn); else Chip, on the integral-f32 levels' planes
+//   any other        mode 0 at one of the six: F32g on the float levels (mimc3_match_ncc_pyramid_any(mode 0)); else Chip on the float levels
+// (ChipU16 never runs on an 8-bit pair here: the context keeps one integer level set per pair, the u8 one.)
+// The mode-0 choice for a scaled-integer pair at the six: ChipU16 where every pass of its series was faster than every pass of
+// mimc3_match_ncc_pyramid_dn's in the same session, configuration by configuration (tools/pyramid_chip_time.py,
+// profiles/full_search_pyramid_chip/time_C2.jsonl).  On BASELINE C2 as 12-bit DN (R 15, L 2 and 3, npeaks 0 and 4) that holds at all six:
+// L = 3 costs 13.2 against 20.6 ms at ocw 7, 25.9 against 104.4 at ocw 16, 178.4 against 607.3 at ocw 40 (1.5 to 4.0 times faster over
+// the series).  An ocw that a later series hands back to the templated kernel is cut out here.
+static bool pyramid_chip_u16_at_six(int32_t ocw) { return full_ocw_ok(ocw); }
+
+bool pyramid_chip_kernel(PairClass cls, int32_t ocw, int32_t mode, SearchKernel &kernel)
+{
+    if (ocw < 1 || ocw > kFullChipMaxOcw || (mode != 0 && mode != 1)) return false;
+    // the kernel of mimc3_match_ncc_pyramid_dn / _any(mode 0) per pair class, and the run-time-ocw kernel that takes its place
+    static const SearchKernel built[4] = {Mx, U16, F32i, F32g}, chip[4] = {ChipU8, ChipU16, Chip, Chip};     // (in PairClass's order)
+    const bool six = mode == 0 && full_ocw_ok(ocw) && !(cls == kScaledInt && pyramid_chip_u16_at_six(ocw));
+    kernel = six ? built[cls] : chip[cls];
+    return true;
+}
+
 int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel)
 {
-    if (call.R > 15 && rules.wide_planes && (call.mode == 1 || (!c->u8_ok && c->u16_ok))) {
+    if (rules.pyramid_chip) {           // (search_check has refused every ocw and mode outside the table)
+        PairClass cls;
+        RC_TRY(pair_class(c, cls));
+        if (!pyramid_chip_kernel(cls, call.ocw, call.mode, kernel)) return fail(MIMC3_EINVAL, std::string(call.entry) + ": bad argument");
+    }
+    else if (call.R > 15 && rules.wide_planes && (call.mode == 1 || (!c->u8_ok && c->u16_ok))) {
         // (mode 1: search_check has refused every pair that is neither 8-bit nor scaled-integer, and every radius beyond the kernel's;
         //  mode 0, a scaled-integer pair: search_check has refused what neither kernel takes)
         const bool u16 = call.mode == 1 || (call.R <= wide_u16_max_radius(call.ocw) &&
@@ -180,59 +209,88 @@ int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, 
 }
 
 // ---- pyramid levels ----
-// what tells the plane types of the levels apart: the element, and the 2 x 2 null-aware reduction of a plane to the next level
-struct LevelType {
-    size_t elem;
-    hipError_t (*reduce)(const void *src, int Hs, int Ws, int Wps, void *dst, int Hd, int Wd, int Wpd, int shift, hipStream_t s);
-};
-static const LevelType kLevelType[4] = {
-    {1, [](const void *s, int Hs, int Ws, int Wps, void *d, int Hd, int Wd, int Wpd, int, hipStream_t st) {
-         return launch_pyr_reduce(static_cast<const unsigned char *>(s), Hs, Ws, Wps, static_cast<unsigned char *>(d), Hd, Wd, Wpd, kU8Pad, st); }},
-    {2, [](const void *s, int Hs, int Ws, int Wps, void *d, int Hd, int Wd, int Wpd, int, hipStream_t st) {
-         return launch_pyr_reduce_u16(static_cast<const unsigned short *>(s), Hs, Ws, Wps, static_cast<unsigned short *>(d), Hd, Wd, Wpd, kU8Pad, st); }},
-    {4, [](const void *s, int Hs, int Ws, int Wps, void *d, int Hd, int Wd, int Wpd, int shift, hipStream_t st) {
-         return launch_pyr_reduce_f32(static_cast<const float *>(s), Hs, Ws, Wps, static_cast<float *>(d), Hd, Wd, Wpd, kU8Pad, shift, st); }},
-    {4, [](const void *s, int Hs, int Ws, int Wps, void *d, int Hd, int Wd, int Wpd, int, hipStream_t st) {
-         return launch_pyr_reduce_f32g(static_cast<const float *>(s), Hs, Ws, Wps, static_cast<float *>(d), Hd, Wd, Wpd, kU8Pad, st); }},
-};
+// The level set a kernel reads by default: its own plane type's.  (The run-time-ocw float kernel also reads the integral-f32 set, planes
+// alone -- mimc3_match_ncc_pyramid_chip says so through plane_set's LevelClass argument.)
+LevelClass level_class(SearchKernel kernel)
+{
+    static const LevelClass of[kSearchKernels] = {kLevelU8, kLevelU16, kLevelF32i, kLevelFloat, kLevelFloat, kLevelFloat,
+                                                  kLevelU8, kLevelU16, kLevelU8, kLevelU16};     // (in SearchKernel's order)
+    return of[kernel];
+}
+// the level set of a pair's class (in PairClass's order)
+static const LevelClass kLevelOfPair[4] = {kLevelU8, kLevelU16, kLevelF32i, kLevelFloat};
 
 // the tables of one level plane (image k) of an integer class; the float levels have none
-static int level_tables(mimc3_ctx *c, SearchKernel kernel, PyrLevel &d, int k)
+static int tables_u8(mimc3_ctx *c, PyrLevel &d, int k)
 {
     const int Hp = d.H + 2 * kU8Pad;
-    const SatRegion rg{0, 0, d.Wp, Hp};
-    DevBuf &pl = k ? d.pl1 : d.pl0, &sat = k ? d.sat1 : d.sat0, &sz = k ? d.sz1 : d.sz0;
-    if (kernel == F32i) {
-        HIP_TRY(sat.reserve(sat2_bytes(Hp, d.Wp)));
-        HIP_TRY(c->sat_tmp.reserve(sat2_scratch_bytes(Hp, d.Wp)));
-        HIP_TRY(launch_sat_f32i(static_cast<const float *>(pl.p), d.Wp, rg, k ? c->fshift1 : c->fshift0, static_cast<Sat2 *>(sat.p), c->sat_tmp.p, c->stream));
-        return 0;
-    }
+    DevBuf &pl = k ? d.pl1 : d.pl0, &sat = k ? d.sat1 : d.sat0;
     HIP_TRY(sat.reserve(sat_bytes(Hp, d.Wp)));
     HIP_TRY(c->sat_tmp.reserve(sat_scratch_bytes(Hp, d.Wp)));
-    if (kernel == Mx) {
-        HIP_TRY(launch_sat_u8(static_cast<const unsigned char *>(pl.p), d.Wp, rg, static_cast<unsigned long long *>(sat.p), c->sat_tmp.p, c->stream));
-        return 0;
-    }
+    HIP_TRY(launch_sat_u8(static_cast<const unsigned char *>(pl.p), d.Wp, SatRegion{0, 0, d.Wp, Hp}, static_cast<unsigned long long *>(sat.p),
+                          c->sat_tmp.p, c->stream));
+    return 0;
+}
+static int tables_u16(mimc3_ctx *c, PyrLevel &d, int k)
+{
+    const int Hp = d.H + 2 * kU8Pad;
+    DevBuf &pl = k ? d.pl1 : d.pl0, &sat = k ? d.sat1 : d.sat0, &sz = k ? d.sz1 : d.sz0;
+    HIP_TRY(sat.reserve(sat_bytes(Hp, d.Wp)));
+    HIP_TRY(c->sat_tmp.reserve(sat_scratch_bytes(Hp, d.Wp)));
     HIP_TRY(sz.reserve(sat_null_bytes(Hp, d.Wp)));
-    HIP_TRY(launch_sat_u16(static_cast<const unsigned short *>(pl.p), d.Wp, rg, static_cast<unsigned long long *>(sat.p),
+    HIP_TRY(launch_sat_u16(static_cast<const unsigned short *>(pl.p), d.Wp, SatRegion{0, 0, d.Wp, Hp}, static_cast<unsigned long long *>(sat.p),
                            static_cast<unsigned int *>(sz.p), c->sat_tmp.p, c->stream));
     return 0;
 }
-
-// Levels 1 .. L - 1 of the current pair for `kernel` -- the levels of its integer class (u8 planes; u16 planes q = pixel * 2^shift, which
-// keep the image's shift; f32 planes reduced on the integers w = pixel * 2^fshift), each with its tables, or the float levels (the f64
-// mean of the block's included pixels; no tables) -- each from the level above, starting at the level-0 set.  Like every plane-set
-// builder: enqueued on the context's stream and drained before the levels count as built.
-static int build_levels(mimc3_ctx *c, SearchKernel kernel, int L)
+static int tables_f32i(mimc3_ctx *c, PyrLevel &d, int k)
 {
-    const bool flt = kernel >= F32g;
-    PyrLevel *lv = flt ? c->pyrg : c->pyr;
-    int &built = flt ? c->pyrg_levels : c->pyr_levels;
+    const int Hp = d.H + 2 * kU8Pad;
+    DevBuf &pl = k ? d.pl1 : d.pl0, &sat = k ? d.sat1 : d.sat0;
+    HIP_TRY(sat.reserve(sat2_bytes(Hp, d.Wp)));
+    HIP_TRY(c->sat_tmp.reserve(sat2_scratch_bytes(Hp, d.Wp)));
+    HIP_TRY(launch_sat_f32i(static_cast<const float *>(pl.p), d.Wp, SatRegion{0, 0, d.Wp, Hp}, k ? c->fshift1 : c->fshift0,
+                            static_cast<Sat2 *>(sat.p), c->sat_tmp.p, c->stream));
+    return 0;
+}
+
+// what tells the level sets apart: the element, the 2 x 2 null-aware reduction of a plane to the next level, the tables of a level plane
+// (null: none), the kernel whose level-0 planes the set starts from, and where the context keeps the set
+struct LevelType {
+    size_t elem;
+    hipError_t (*reduce)(const void *src, int Hs, int Ws, int Wps, void *dst, int Hd, int Wd, int Wpd, int shift, hipStream_t s);
+    int (*tables)(mimc3_ctx *c, PyrLevel &d, int k);
+    SearchKernel top;
+    PyrLevel (mimc3_ctx::*levels)[4];
+    int mimc3_ctx::*built;
+};
+static const LevelType kLevelType[4] = {      // (in LevelClass's order)
+    {1, [](const void *s, int Hs, int Ws, int Wps, void *d, int Hd, int Wd, int Wpd, int, hipStream_t st) {
+         return launch_pyr_reduce(static_cast<const unsigned char *>(s), Hs, Ws, Wps, static_cast<unsigned char *>(d), Hd, Wd, Wpd, kU8Pad, st); },
+     tables_u8, Mx, &mimc3_ctx::pyr, &mimc3_ctx::pyr_levels},
+    {2, [](const void *s, int Hs, int Ws, int Wps, void *d, int Hd, int Wd, int Wpd, int, hipStream_t st) {
+         return launch_pyr_reduce_u16(static_cast<const unsigned short *>(s), Hs, Ws, Wps, static_cast<unsigned short *>(d), Hd, Wd, Wpd, kU8Pad, st); },
+     tables_u16, U16, &mimc3_ctx::pyr, &mimc3_ctx::pyr_levels},
+    {4, [](const void *s, int Hs, int Ws, int Wps, void *d, int Hd, int Wd, int Wpd, int shift, hipStream_t st) {
+         return launch_pyr_reduce_f32(static_cast<const float *>(s), Hs, Ws, Wps, static_cast<float *>(d), Hd, Wd, Wpd, kU8Pad, shift, st); },
+     tables_f32i, F32i, &mimc3_ctx::pyr, &mimc3_ctx::pyr_levels},
+    {4, [](const void *s, int Hs, int Ws, int Wps, void *d, int Hd, int Wd, int Wpd, int, hipStream_t st) {
+         return launch_pyr_reduce_f32g(static_cast<const float *>(s), Hs, Ws, Wps, static_cast<float *>(d), Hd, Wd, Wpd, kU8Pad, st); },
+     nullptr, F32g, &mimc3_ctx::pyrg, &mimc3_ctx::pyrg_levels},
+};
+
+// Levels 1 .. L - 1 of the current pair in the set `lc` -- the levels of an integer class (u8 planes; u16 planes q = pixel * 2^shift, which
+// keep the image's shift; f32 planes reduced on the integers w = pixel * 2^fshift), each with its tables, or the float levels (the f64
+// mean of the block's included pixels; no tables) -- each from the level above, starting at the level-0 set.  A set is the same whichever
+// kernel asks for it first: an integer class's levels always carry their tables.  Like every plane-set
+// builder: enqueued on the context's stream and drained before the levels count as built.
+static int build_levels(mimc3_ctx *c, LevelClass lc, int L)
+{
+    const LevelType &t = kLevelType[lc];
+    PyrLevel *lv = c->*t.levels;
+    int &built = c->*t.built;
     PlaneSet top;
-    RC_TRY(plane_set(c, kernel, 0, top));
+    RC_TRY(plane_set(c, t.top, 0, top));
     if (built >= L - 1) return 0;
-    const LevelType &t = kLevelType[flt ? 3 : kernel];
     for (int l = built + 1; l < L; ++l) {
         PyrLevel &d = lv[l - 1];
         const PyrLevel *up = l == 1 ? nullptr : &lv[l - 2];
@@ -245,7 +303,7 @@ static int build_levels(mimc3_ctx *c, SearchKernel kernel, int L)
             HIP_TRY(pl.reserve(bytes));
             HIP_TRY(hipMemsetAsync(pl.p, 0, bytes, c->stream));
             HIP_TRY(t.reduce(src, Hs, Ws, Wps, pl.p, d.H, d.W, d.Wp, k ? c->fshift1 : c->fshift0, c->stream));
-            if (!flt) RC_TRY(level_tables(c, kernel, d, k));
+            if (t.tables) RC_TRY(t.tables(c, d, k));
         }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -254,14 +312,16 @@ static int build_levels(mimc3_ctx *c, SearchKernel kernel, int L)
 }
 
 // The planes and tables `kernel` reads on `level`: 0 = the resident pair's set, whose missing parts are built on first use; l >= 1 =
-// the pyramid level, built with the levels above it on first use.
-int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl)
+// the pyramid level of the set `lc`, built with the levels above it on first use.
+int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl) { return plane_set(c, kernel, level_class(kernel), level, pl); }
+
+int plane_set(mimc3_ctx *c, SearchKernel kernel, LevelClass lc, int level, PlaneSet &pl)
 {
     pl = PlaneSet{};
     if (kernel == F32i) { pl.scale0 = 1.0 / (double)(1 << c->fshift0); pl.scale1 = 1.0 / (double)(1 << c->fshift1); }
     if (level > 0) {
-        RC_TRY(build_levels(c, kernel, level + 1));
-        const PyrLevel &d = (kernel >= F32g ? c->pyrg : c->pyr)[level - 1];
+        RC_TRY(build_levels(c, lc, level + 1));
+        const PyrLevel &d = (c->*kLevelType[lc].levels)[level - 1];
         pl.p0 = d.pl0.p; pl.p1 = d.pl1.p; pl.sat0 = d.sat0.p; pl.sat1 = d.sat1.p; pl.satz0 = d.sz0.p; pl.satz1 = d.sz1.p;
         pl.H = d.H; pl.W = d.W; pl.Wp = d.Wp;
         return 0;
@@ -284,6 +344,9 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &pl)
     return 0;
 }
 
+// the kernels that run as a clean launch plus a masked launch in flag mode: one class byte per point (in SearchKernel's order)
+static const bool kKernelFlags[kSearchKernels] = {true, false, false, false, false, false, true, true, true, true};
+
 // One search launch: `kernel` over the call's points on `planes`, with the timing events around it (unless suspended) and last_path.
 int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const SearchCall &call)
 {
@@ -300,7 +363,7 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
     u.p0 = static_cast<const unsigned char *>(pl.p0); u.p1 = static_cast<const unsigned char *>(pl.p1);
     if (pl.sat0) { u.sat0 = pl.sat0; u.sat1 = pl.sat1; u.satz0 = pl.satz0; u.satz1 = pl.satz1; u.sat_ws = sat_pitch(pl.Wp); }
     u.scale0 = pl.scale0; u.scale1 = pl.scale1;
-    const bool flags = kernel == Mx || kernel == ChipU8 || kernel == ChipU16 || kernel == WideU8 || kernel == WideU16;
+    const bool flags = kKernelFlags[kernel];
     // a fused stack layer: the accumulating forms of the four run-time-ocw matrix-core kernels (no other kernel has them)
     const int acc = call.stk_sum ? kFormsAcc : 0;
     if (acc) {
@@ -371,6 +434,7 @@ static const SearchRules kWideFb = {kFloat, false, true, kCandOptional, true};
 static const SearchRules kPyramid = {kU8, false, false, kCandAbsent, false, true};
 static const SearchRules kPyramidDn = {kIntegralF32, false, false, kCandOptional, false, true};
 static const SearchRules kPyramidAny = {kFloat, true, false, kCandOptional, false, true};
+static const SearchRules kPyramidChip = {kFloat, true, false, kCandOptional, false, true, false, false, true, false, false, false, false, true};   // (pyramid, any_ocw, pyramid_chip)
 
 // the description of a _dev entry's call (`levels`, d_fb: the entries that have them set them)
 static SearchCall dev_call(const char *entry, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
@@ -441,6 +505,8 @@ static int full_fb_dev(mimc3_ctx *c, const SearchCall &call, const SearchRules &
 // Coarse-to-fine search over an image pyramid (pyramid_kernel.hip): the levels of the call's kernel, then per level the step and the
 // exhaustive search with the arg-max cells, chained on one stream; level 0 is the plain search at shift = sh (record and candidates).
 // The kernel is the one the same call without levels would run: the float kernel searches the float levels, an integer class its own.
+// mimc3_match_ncc_pyramid_chip (rules.pyramid_chip): the kernel of pyramid_chip_kernel on the levels of the PAIR's class, whichever kernel
+// that is -- the run-time-ocw float kernel reads the integral-f32 levels' planes on an integral-f32 pair.
 static int pyramid_dev(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, int32_t *d_shift_out)
 {
     RC_TRY(search_check(c, call, rules));
@@ -450,8 +516,17 @@ static int pyramid_dev(mimc3_ctx *c, const SearchCall &call, const SearchRules &
     SearchKernel kernel;
     PlaneSet planes;
     RC_TRY(pick_kernel(c, call, rules, kernel));
-    RC_TRY(plane_set(c, kernel, levels - 1, planes));       // (every level the call reads exists before its first launch)
-    if (kernel == Mx) HIP_TRY(c->mxl[0].reserve((size_t)N));
+    LevelClass lc = level_class(kernel);
+    if (rules.pyramid_chip) {
+        PairClass cls;
+        RC_TRY(pair_class(c, cls));
+        lc = kLevelOfPair[cls];
+    }
+    RC_TRY(plane_set(c, kernel, lc, levels - 1, planes));   // (every level the call reads exists before its first launch)
+    // all scratch before anything is enqueued (a buffer that grows is freed first, and hipFree waits for the device): the class bytes of
+    // the kernels that hand points from their clean form to their masked one (launch_search then finds them large enough), then the
+    // points' positions, arg-max cells and shifts
+    if (kKernelFlags[kernel]) HIP_TRY(c->mxl[0].reserve((size_t)N));
     HIP_TRY(c->pyr_pos.reserve(sizeof(double) * 2 * (size_t)N));
     HIP_TRY(c->pyr_peak.reserve(sizeof(int32_t) * (size_t)N));
     if (!d_shift_out) HIP_TRY(c->pyr_sh.reserve(sizeof(int32_t) * 2 * (size_t)N));
@@ -462,16 +537,16 @@ static int pyramid_dev(mimc3_ctx *c, const SearchCall &call, const SearchRules &
     TimingSuspended whole(c);           // (the events bracket the whole pass)
     // the coarsest level's displacement d_{L-1} and positions p_{L-1} (for L = 1: shift_out = shift)
     HIP_TRY(launch_pyr_step(call.d_xyuvav, N, call.off_u, call.off_v, call.d_shift, nullptr, call.R, levels - 1, true, sh, pos, s));
-    SearchCall lc = call;               // level l: the points' positions on it, around sh, and the arg-max cells for the step to level l - 1
-    lc.d_xyuvav = pos; lc.xy_stride = 2; lc.xy_col = 0; lc.off_u = lc.off_v = 0; lc.d_shift = sh; lc.npeaks = 0; lc.d_cand = nullptr; lc.d_peak = peak;
+    SearchCall lv = call;               // level l: the points' positions on it, around sh, and the arg-max cells for the step to level l - 1
+    lv.d_xyuvav = pos; lv.xy_stride = 2; lv.xy_col = 0; lv.off_u = lv.off_v = 0; lv.d_shift = sh; lv.npeaks = 0; lv.d_cand = nullptr; lv.d_peak = peak;
     for (int l = levels - 1; l >= 1; --l) {
-        RC_TRY(plane_set(c, kernel, l, planes));
-        RC_TRY(launch_search(c, kernel, planes, lc));
+        RC_TRY(plane_set(c, kernel, lc, l, planes));
+        RC_TRY(launch_search(c, kernel, planes, lv));
         HIP_TRY(launch_pyr_step(call.d_xyuvav, N, call.off_u, call.off_v, nullptr, peak, call.R, l - 1, false, sh, pos, s));
     }
     SearchCall c0 = call;
     c0.d_shift = sh;
-    RC_TRY(plane_set(c, kernel, 0, planes));
+    RC_TRY(plane_set(c, kernel, lc, 0, planes));
     RC_TRY(launch_search(c, kernel, planes, c0));
     if (whole.was) { HIP_TRY(hipEventRecord(c->ev1, s)); c->timed = true; }
     return 0;
@@ -820,6 +895,15 @@ extern "C" int mimc3_match_ncc_pyramid_any_dev(mimc3_ctx *c, const double *d_xyu
     return pyramid_dev(c, call, kPyramidAny, d_shift_out);
 }
 
+extern "C" int mimc3_match_ncc_pyramid_chip_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                                const int32_t *d_shift, int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap,
+                                                int32_t mode, float *d_out, float *d_cand, int32_t *d_shift_out, void *stream)
+{
+    SearchCall call = dev_call("mimc3_match_ncc_pyramid_chip_dev", d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, nullptr, stream);
+    call.levels = levels;
+    return pyramid_dev(c, call, kPyramidChip, d_shift_out);
+}
+
 extern "C" int mimc3_match_ncc_pyramid(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
                                        int32_t ocw, int32_t R, int32_t levels, int32_t swap, float *out, int32_t *shift_out)
 {
@@ -838,6 +922,22 @@ extern "C" int mimc3_match_ncc_pyramid_any(mimc3_ctx *c, const double *xyuvav, i
                                            float *cand, int32_t *shift_out)
 {
     return search_host(c, kPyramidAny, "mimc3_match_ncc_pyramid_any", xyuvav, N, offset, shift, ocw, R, levels, npeaks, swap, mode, out, cand, nullptr, nullptr, shift_out);
+}
+
+// ... at any chip half-width 1 .. 80, on the run-time-ocw kernels (the matrix cores on 8-bit and scaled-integer pairs)
+extern "C" int mimc3_match_ncc_pyramid_chip(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                            int32_t ocw, int32_t R, int32_t levels, int32_t npeaks, int32_t swap, int32_t mode, float *out,
+                                            float *cand, int32_t *shift_out)
+{
+    return search_host(c, kPyramidChip, "mimc3_match_ncc_pyramid_chip", xyuvav, N, offset, shift, ocw, R, levels, npeaks, swap, mode, out, cand, nullptr, nullptr, shift_out);
+}
+
+// the last_path of that entry for a pair class (0 8-bit, 1 scaled-integer, 2 integral f32, 3 any other), chip size and mode; 0 outside the table
+extern "C" int mimc3_pyramid_chip_path(int32_t pair_class, int32_t ocw, int32_t mode)
+{
+    SearchKernel kernel;
+    if (pair_class < 0 || pair_class > 3 || !pyramid_chip_kernel(static_cast<PairClass>(pair_class), ocw, mode, kernel)) return 0;
+    return 6 + (int)kernel;
 }
 
 // One level (1..4) of the current pair as pixel values, for tests of the reduction: the planes' interior of the level `kernel` reads.
