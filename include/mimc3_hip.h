@@ -96,6 +96,8 @@ int mimc3_ctx_set_images_dev(mimc3_ctx *ctx, const float *d_i0, const float *d_i
  *  15 = the exhaustive search beyond +-15 px of mimc3_match_ncc_wide_planes on a scaled-integer pair (R >= 16), or on an 8-bit or
  *       scaled-integer pair with its mode 1: the matrix-core wide search kernel on the u16 planes (two 6-bit planes per pixel) and their
  *       tables, at any chip half-width 1..80.
+ *  16 = the exhaustive search beyond +-15 px of mimc3_match_ncc_wide_chip (R >= 16) with its mode 1, or in mode 0 on a pair and at an
+ *       (ocw, R) no other wide kernel takes: the run-time-ocw wide float search kernel on the f32 planes, at any chip half-width 1..80.
  * All three give results bit-identical to the reference on integral-DN data.  mode 1 forces kernel 0,
  * mode 2 skips the integer kernels, mode 3 skips only the u8 kernel, mode 4 is mode 0 without kernel 5 (tests use
  * them to cover every kernel on 8-bit inputs too).
@@ -592,7 +594,8 @@ int mimc3_match_ncc_wide_class_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32
  *   mimc3_match_ncc_wide takes goes to the matrix-core kernel; ocw 80, where it is the only kernel: 1170.5 / 1407.1 ms at R 16 / 27.
  *   MIMC3_hip_offsets calls this entry in mode 0 where it called mimc3_match_ncc_wide_class: the same files, a filtered pair and a 12-bit
  *   pair in a 16-bit TIFF on the matrix cores.
- *   Out of scope: integral-f32 (16-bit DN) pairs beyond R 15; mimc3_stack_add*, mimc3_match_ncc_wide_fb and Context.full_candidates through
+ *   Integral-f32 (16-bit DN) and float pairs beyond R 15 at any chip size: mimc3_match_ncc_wide_chip, below.
+ *   Out of scope: mimc3_stack_add*, mimc3_match_ncc_wide_fb and Context.full_candidates through
  *   the class wide kernels; an ocw outside the six on the command line at R > 15; the pyramids; several GPUs. */
 int mimc3_wide_planes_max_radius(int32_t ocw);
 int mimc3_wide_planes_layout(int32_t ocw, int32_t R, int32_t out[4]);
@@ -604,6 +607,58 @@ int mimc3_match_ncc_wide_planes(mimc3_ctx *ctx, const double *xyuvav, int32_t N,
 int mimc3_match_ncc_wide_planes_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
                                     const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
                                     float *d_out, float *d_cand, float *d_surf, void *stream);
+
+/* ---- The exhaustive search beyond +-15 px on ANY pair -- 16-bit DN (Landsat 8/9, Sentinel-2), float pixels (SAR amplitude), NaN or negative
+ *      nulls -- at ANY chip half-width 1 <= ocw <= 80 (match_wide_chip_kernel.hip).
+ *   The arguments are those of mimc3_match_ncc_wide_planes: 1 <= ocw <= 80, 1 <= R <= mimc3_wide_chip_max_radius(ocw) (47 in range, 0
+ *   outside), npeaks 0..8, mode 0 or 1, surf optional; anything else MIMC3_EINVAL.  Every refusal comes before anything is enqueued or
+ *   written, in the family's order.  In mode 0 the entry refuses no pair and no (ocw, R) in range.
+ *                                  mode 0                                                      mode 1
+ *   R <= 15                        mimc3_match_ncc_full_chip_planes(mode 0): its kernel,       mimc3_match_ncc_full_chip(mode 1)
+ *                                  its bytes, its last_path                                    (last_path 11)
+ *   R >= 16, 8-bit pair            where mimc3_match_ncc_wide_class(mode 0) sends it (14)      the kernel of this entry (16)
+ *   R >= 16, scaled-integer pair   R <= mimc3_wide_planes_max_radius(ocw): where               16
+ *                                  mimc3_match_ncc_wide_planes(mode 0) sends it (15);
+ *                                  beyond: 16
+ *   R >= 16, any other pair        ocw one of the six and R <= mimc3_wide_max_radius(ocw):     16
+ *                                  mimc3_match_ncc_wide's kernel and bytes (10); else 16
+ *   Definition (mode 1, and last_path 16 in mode 0): mimc3_match_ncc_full_any in mode 1, word for word, as mimc3_match_ncc_wide and
+ *   mimc3_match_ncc_full_chip state it -- both null rules, f32 products widened to f64, additions only, the reference's f64 finish, the
+ *   first-wins arg-max and the statuses -2 / -3 / -4, candidates by mimc3_match_ncc_wide's tail, the all-NaN record, candidates and
+ *   surface for a point of the _dev entry that breaks the bounds.
+ *   The kernel.  One workgroup of four wave64 per grid point.  The surface of S = 2R + 1 cells per side is ceil(S / 32)^2 tiles of 32 x 32
+ *   cells (256 tasks of four cells, one per thread); per tile the chip is walked in bands of out[1] chip rows as
+ *   mimc3_match_ncc_full_chip walks it: a band's chip rows and the h + 31 box rows they meet over the tile's window columns are staged,
+ *   the band runs the clean or the masked body (a workgroup-uniform choice on the band's excluded pixels), the f64 accumulators stay in
+ *   registers across the bands, the four cells are finished after the last band into a surface at pitch 96 with LDS bytes of its own.
+ *   The validity counts (status -3) come from one pass over chip and box in front of the tiles.  Staging loads a pixel only if its BOX
+ *   coordinates lie inside the (2R + 2 ocw + 1)^2 box: the overhang of a partial tile is staged as zeros, never read, never counted.
+ *   The order of the additions is a function of (ocw, R) and of which body runs in which (tile, band), never of N, the point's place in the
+ *   grid or timing; on 8-, 12- and 16-bit DN every sum is an exact integer and the bytes are those of the reference-order sums.
+ *   mimc3_wide_chip_layout(ocw, R, out)   out[0] cell tiles per axis (2..3), out[1] chip rows per band, out[2] bands, out[3] workgroups
+ *              per CU the LDS allows (at most 8), out[4] dynamic LDS bytes, from the constexpr layout the launch uses; returns 1, or 0
+ *              outside 1 <= ocw <= 80, 16 <= R <= 47.  Two workgroups per CU wherever the whole chip is then one band; otherwise one
+ *              workgroup and the tallest band that fits (ocw 80, R 47: 71 rows, three bands).
+ *   mimc3_wide_chip_path(pair_class, ocw, R, mode)   the table above as a last_path number for a pair class (0 8-bit, 1 scaled-integer,
+ *              2 integral f32, 3 any other); -1 outside the table.  No device.
+ *   At the six chip sizes mode 0 keeps mimc3_match_ncc_wide's templated kernel: tools/wide_chip_time.py times the two side by side
+ *   (profiles/full_search_wide_chip/, 18,906 of C2's points as 16-bit DN, one MI355X): ocw 16 at R 16 / 31 / 47: 29.70 / 34.77 / 77.12 ms
+ *   against 11.1 / 40.5 / 136.6; ocw 40 at R 16 / 31: 350.4 / 349.0 against 172.2 / 352.5 -- faster with full tiles, 2.0 to 2.7 times slower at
+ *   R 16, where three of the four tiles are nearly empty and cost full ones; ocw 80, where it is the only kernel: 1413.1 / 1385.5 / 3072.5.
+ *   Not every pass is faster in every configuration, so nothing is moved.
+ *   Out of scope: MIMC3_hip_offsets; forward-backward and mimc3_stack_add / _add_fused through this kernel; the pyramids beyond R 15;
+ *   several GPUs; ocw above 80. */
+int mimc3_wide_chip_max_radius(int32_t ocw);
+int mimc3_wide_chip_layout(int32_t ocw, int32_t R, int32_t out[5]);
+int mimc3_wide_chip_path(int32_t pair_class, int32_t ocw, int32_t R, int32_t mode);
+int mimc3_match_ncc_wide_chip(mimc3_ctx *ctx, const double *xyuvav, int32_t N, const int32_t offset[2],
+                              const int32_t *shift /*[N][2] or NULL*/, int32_t ocw, int32_t R, int32_t npeaks /*0 = record only*/,
+                              int32_t swap, int32_t mode, float *out /*[N][8] host*/,
+                              float *cand /*[npeaks][N][3] host; NULL iff npeaks == 0*/, float *surf /*[N][(2R+1)^2] host, or NULL*/);
+/* Device-resident variant: the contract of mimc3_match_ncc_wide_planes_dev. */
+int mimc3_match_ncc_wide_chip_dev(mimc3_ctx *ctx, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                  const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                  float *d_out, float *d_cand, float *d_surf, void *stream);
 
 /* ---- Forward-backward consistency of the exhaustive search: is a peak RECIPROCAL -- does matching back from where a point landed return
  *      to where it started?  (The back-matching test AMPCOR and IMCORR users apply after the run; the record's quality columns all

@@ -89,6 +89,11 @@ _lib.mimc3_wide_planes_max_radius.argtypes = [C.c_int32]
 _lib.mimc3_wide_planes_layout.argtypes = [C.c_int32, C.c_int32, _vp]
 _lib.mimc3_match_ncc_wide_planes.argtypes = _lib.mimc3_match_ncc_full_chip.argtypes
 _lib.mimc3_match_ncc_wide_planes_dev.argtypes = _lib.mimc3_match_ncc_full_chip_dev.argtypes
+_lib.mimc3_wide_chip_max_radius.argtypes = [C.c_int32]
+_lib.mimc3_wide_chip_layout.argtypes = [C.c_int32, C.c_int32, _vp]
+_lib.mimc3_wide_chip_path.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+_lib.mimc3_match_ncc_wide_chip.argtypes = _lib.mimc3_match_ncc_full_chip.argtypes
+_lib.mimc3_match_ncc_wide_chip_dev.argtypes = _lib.mimc3_match_ncc_full_chip_dev.argtypes
 _lib.mimc3_match_ncc_full_dn_dev.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _vp, _vp, _vp]
 _lib.mimc3_match_ncc_full_fb.argtypes = [_vp, _f64p, C.c_int32, _i32p, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _vp, _vp]
@@ -346,6 +351,26 @@ def wide_planes_layout(ocw, radius):
     16 <= radius <= wide_planes_max_radius(ocw)."""
     out = (C.c_int32 * 4)()
     return tuple(int(v) for v in out) if _lib.mimc3_wide_planes_layout(int(ocw), int(radius), out) else None
+
+
+def wide_chip_max_radius(ocw):
+    """The largest radius match_ncc_wide_chip takes at this chip half-width (mimc3_wide_chip_max_radius): 47 for 1 <= ocw <=
+    full_chip_max_ocw(), else 0."""
+    return int(_lib.mimc3_wide_chip_max_radius(int(ocw)))
+
+
+def wide_chip_layout(ocw, radius):
+    """The layout of match_ncc_wide_chip's run-time-ocw wide float kernel (mimc3_wide_chip_layout) -> (32 x 32 cell tiles per axis, chip
+    rows per band, bands, workgroups per CU the LDS allows, dynamic LDS bytes); None outside 1 <= ocw <= full_chip_max_ocw(),
+    16 <= radius <= 47."""
+    out = (C.c_int32 * 5)()
+    return tuple(int(v) for v in out) if _lib.mimc3_wide_chip_layout(int(ocw), int(radius), out) else None
+
+
+def wide_chip_path(pair_class, ocw, radius, mode):
+    """The last_path of match_ncc_wide_chip for a pair class (0 8-bit, 1 scaled-integer, 2 integral f32, 3 any other), a chip half-width,
+    a radius and a mode (mimc3_wide_chip_path; no device); -1 for anything outside the table."""
+    return int(_lib.mimc3_wide_chip_path(int(pair_class), int(ocw), int(radius), int(mode)))
 
 
 def wide_lds_bytes(ocw, radius):
@@ -837,6 +862,26 @@ class Context:
                                                     npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
                "match_ncc_wide_planes_dev")
 
+    def match_ncc_wide_chip(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, swap=False, mode=0, surface=False):
+        """The exhaustive search beyond +-15 px on ANY pair -- 16-bit DN, float pixels, NaN or negative nulls -- at every chip half-width
+        1..80 (mimc3_match_ncc_wide_chip), 1 <= radius <= wide_chip_max_radius(ocw) = 47.  Mode 1 is match_ncc_full_any(mode=1)'s
+        definition on the run-time-ocw kernels: radius <= 15 is match_ncc_full_chip(mode=1), byte for byte ("f32g_chip"); radius >= 16
+        runs the run-time-ocw wide float kernel ("f32g_wide_chip").  Mode 0 refuses no pair and no (ocw, radius) in range: radius <= 15
+        is match_ncc_full_chip_planes(mode=0); radius >= 16 goes where match_ncc_wide_class / match_ncc_wide_planes (mode 0) send an
+        8-bit / scaled-integer pair, to "f32g_wide" where match_ncc_wide takes (ocw, radius), and to "f32g_wide_chip" everywhere else
+        (wide_chip_path has the table) -> (record, candidates or None[, surfaces]) as match_ncc_wide."""
+        xy, n, out, cand, surf, fb, sh = _search_arrays("match_ncc_wide_chip", xyuvav, shift, npeaks=npeaks, radius=radius, surface=surface)
+        _check(_lib.mimc3_match_ncc_wide_chip(self._h, xy, n, np.ascontiguousarray(offset, np.int32), _ptr(sh), ocw, radius, int(npeaks),
+                                              1 if swap else 0, int(mode), out, _ptr(cand), _ptr(surf)), "match_ncc_wide_chip")
+        return (out, cand, surf) if surface else (out, cand)
+
+    def match_ncc_wide_chip_dev(self, d_xyuvav, n, offset, ocw, radius, npeaks, d_out, d_cand=0, d_shift=0, stream=0, swap=False, mode=0,
+                                d_surf=0):
+        """Device-pointer variant (enqueue only): as match_ncc_full_chip_dev."""
+        _check(_lib.mimc3_match_ncc_wide_chip_dev(self._h, d_xyuvav, n, int(offset[0]), int(offset[1]), d_shift or None, ocw, radius,
+                                                  npeaks, 1 if swap else 0, int(mode), d_out, d_cand or None, d_surf or None, stream),
+               "match_ncc_wide_chip_dev")
+
     def match_ncc_full_fb(self, xyuvav, offset, ocw, radius, npeaks=0, shift=None, mode=0):
         """Forward-backward consistency of the exhaustive search (mimc3_match_ncc_full_fb): the forward pass is match_ncc_full_any(swap
         False, mode), bit for bit; every forward result -- the record and each of the npeaks candidates -- is then matched back from
@@ -1081,7 +1126,8 @@ class Context:
         The pair is left unfiltered.  any_pair: the calls are match_ncc_full_any's (mode 0), so a float pair goes through every variant.
         any_ocw: the calls are match_ncc_full_chip's (mode 0), so vec_ocw may hold any chip half-width 1 .. full_chip_max_ocw() -- the
         reference's (7, 10, 15, 11) and (14, 30, 60, 80) -- and any pair; at a chip size in range other than the six built ones they are
-        match_ncc_full_chip_planes's (mode 0: an 8-bit or scaled-integer pair on the matrix cores, the same bytes).
+        match_ncc_full_chip_planes's (mode 0: an 8-bit or scaled-integer pair on the matrix cores, the same bytes).  any_ocw with
+        radius > 15 (up to wide_chip_max_radius(ocw), levels = 1): every call is match_ncc_wide_chip's (mode 0), any pair at any ocw.
         levels > 1: every (variant, ocw) call is match_ncc_pyramid_chip's (mode 0) over that many levels, whatever any_pair and any_ocw
         say -- any chip half-width 1 .. full_chip_max_ocw(), any pair; filter, then reduce: the levels are rebuilt after each
         filter_images.  levels = 1 runs exactly the single-level calls above."""
@@ -1107,6 +1153,8 @@ class Context:
                         blocks.append(self.match_ncc_pyramid_chip(xyuvav, offset, ocw, radius, levels, npeaks, shift=shift)[1])
                         continue
                     call = self.match_ncc_full_chip_planes if any_ocw and ocw not in six and 1 <= ocw <= full_chip_max_ocw() else match
+                    if any_ocw and int(radius) > 15:
+                        call = self.match_ncc_wide_chip
                     blocks.append(call(xyuvav, offset, ocw, radius, npeaks, shift=shift)[1])
         finally:
             self.filter_images(None)
@@ -1437,7 +1485,7 @@ class Context:
         _check(_lib.mimc3_ctx_set_path(self._h, {"auto": 0, "general": 1, "f32": 2, "u16": 3, "u8px": 4}.get(mode, mode)), "set_path")
 
     def last_path(self):
-        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip", 12: "u8_mfma_chip", 13: "u16_mfma_chip", 14: "u8_mfma_wide", 15: "u16_mfma_wide"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
+        return {0: "general_f32", 1: "u8_exact", 2: "f32_tiled", 3: "u16_scaled", 4: "u8_offset", 5: "u8_mfma", 6: "u8_mfma_full", 7: "u16_full", 8: "f32i_full", 9: "f32g_full", 10: "f32g_wide", 11: "f32g_chip", 12: "u8_mfma_chip", 13: "u16_mfma_chip", 14: "u8_mfma_wide", 15: "u16_mfma_wide", 16: "f32g_wide_chip"}.get(int(_lib.mimc3_ctx_last_path(self._h)), "none")
 
     # -- timing -------------------------------------------------------------------------------
     def enable_timing(self, on=True):

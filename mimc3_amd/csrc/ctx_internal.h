@@ -204,9 +204,12 @@ struct SearchRules {
                                         // wide_u16_max_radius(ocw); R <= 15 is the chip_planes entry
     bool pyramid_chip = false;          // with pyramid and any_ocw (mimc3_match_ncc_pyramid_chip): the kernel is pyramid_chip_kernel's, one of the
                                         // run-time-ocw kernels wherever the table in include/mimc3_hip.h names it, on the levels of the pair's class
+    bool wide_chip = false;             // with any_ocw (mimc3_match_ncc_wide_chip): the radius limit is wide_chip_max_radius(ocw) and no pair is
+                                        // refused in either mode; the kernel is wide_chip_kernel's (the table in include/mimc3_hip.h), the
+                                        // run-time-ocw wide float kernel wherever no sibling takes the call; whichever kernel runs serves the surfaces
 };
-enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8, ChipU16, WideU8, WideU16 };       // last_path 6 .. 15
-constexpr int kSearchKernels = 10;
+enum SearchKernel { Mx, U16, F32i, F32g, Wide, Chip, ChipU8, ChipU16, WideU8, WideU16, WideChip };       // last_path 6 .. 16
+constexpr int kSearchKernels = 11;
 // The level sets of a coarse-to-fine search: u8 planes with u8 tables, u16 planes with both tables, f32 planes reduced on their integers
 // with 16-byte tables, f32 planes reduced as floats (no tables).  A pair has one integer class, so the first three share mimc3_ctx::pyr.
 // level_class(kernel) is the set a kernel reads when nothing else is said; the run-time-ocw float kernel reads the integral-f32 set as
@@ -232,6 +235,8 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, int level, PlaneSet &planes);  
 int plane_set(mimc3_ctx *c, SearchKernel kernel, LevelClass levels, int level, PlaneSet &planes);
 // mimc3_match_ncc_pyramid_chip's kernel for a pair class, chip size and mode (the table in include/mimc3_hip.h); false outside the table
 bool pyramid_chip_kernel(PairClass cls, int32_t ocw, int32_t mode, SearchKernel &kernel);
+// mimc3_match_ncc_wide_chip's kernel for a pair class, chip size, radius and mode (the table in include/mimc3_hip.h); false outside the table
+bool wide_chip_kernel(PairClass cls, int32_t ocw, int32_t R, int32_t mode, SearchKernel &kernel);
 int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &planes, const SearchCall &call);
 
 // Suspends the context's timing flag for a scope: an entry made of several searches records the events around the whole call, and its

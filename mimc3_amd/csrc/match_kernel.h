@@ -330,6 +330,14 @@ hipError_t launch_match_wide_u8(MatchU8Args a, int forms, hipStream_t stream);
 int wide_u16_max_radius(int ocw);
 bool wide_u16_layout_query(int ocw, int R, int out[4]);
 hipError_t launch_match_wide_u16(MatchU8Args a, int forms, hipStream_t stream);
+// the search beyond +-15 px on the f32 planes of ANY pair at any chip half-width (match_wide_chip_kernel.hip; mimc3_match_ncc_wide_chip): the
+// arguments of launch_match_wide with 1 <= a.ocw <= kFullChipMaxOcw and 16 <= a.full_R <= 47 -- launch_match_full_chip's band loop once per
+// 32 x 32 cell tile, the surface at pitch 96 in LDS bytes of its own.  wide_chip_max_radius: 47 for 1 <= ocw <= kFullChipMaxOcw, else 0.
+// wide_chip_layout_query: cell tiles per axis, chip rows per band, bands, workgroups per CU the LDS allows, dynamic LDS bytes of a launch
+// at (ocw, R) (false outside 1 .. kFullChipMaxOcw x 16 .. 47), from the constexpr layout the launch uses
+int wide_chip_max_radius(int ocw);
+bool wide_chip_layout_query(int ocw, int R, int out[5]);
+hipError_t launch_match_wide_chip(MatchU8Args a, float *surf, hipStream_t stream);
 static_assert(sizeof(MatchU8Args) == 344,"MatchU8Args: the unions over its slots keep the struct's size");
 // The coarse-to-fine search (mimc3_match_ncc_pyramid, pyramid_kernel.hip).  One level of a zero-bordered u8 plane pair from the level
 // above: pixel (x, y) = the rounded mean (s + n/2) / n of the non-zero pixels of the 2 x 2 block at (2x, 2y), 0 if the block is all

@@ -1,5 +1,5 @@
 // search.cpp -- the host layer of the exhaustive-search family of the C ABI (include/mimc3_hip.h): mimc3_match_ncc_full, _full_multi,
-// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _full_chip_planes, _wide, _wide_class, _wide_planes, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
+// _full_planes, _full_dn, _full_any, _full_surf, _full_chip, _full_chip_class, _full_chip_planes, _wide, _wide_class, _wide_planes, _wide_chip, forward-backward (_full_fb, _wide_fb) and the coarse-to-fine searches (_pyramid, _pyramid_dn,
 // _pyramid_any, _pyramid_chip), each with its _dev twin.  One shape for all of them: an entry describes its call (SearchCall) and what it accepts
 // (SearchRules); search_check makes every refusal, pick_kernel selects the kernel, plane_set points at the planes it reads (building
 // them on first use), launch_search is the one place that launches.  The stack's layer adds (stack.cpp) go through the same functions.
@@ -43,12 +43,13 @@ static int check_class(mimc3_ctx *c, PairClass widest, const std::string &en)
 
 // Every refusal the family makes from a call's description, in this order (the first one met decides the code):
 //   1. the arguments, MIMC3_EINVAL: a null context, point array or record, N <= 0, candidates that do not go with npeaks, no surfaces
-//      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six (any_ocw: outside 1..80); R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw); wide_class: 1..mimc3_wide_class_max_radius(ocw)); levels outside 1..5
+//      where the entry is for them (mimc3_match_ncc_full_surf); npeaks out of range; ocw not one of the six (any_ocw: outside 1..80); R outside 1..15 (wide: 1..mimc3_wide_max_radius(ocw); wide_class: 1..mimc3_wide_class_max_radius(ocw); wide_chip: 1..mimc3_wide_chip_max_radius(ocw)); levels outside 1..5
 //   2. the context's state, MIMC3_ESTATE: no images; a chip-atlas context
 //   3. the pair's class, MIMC3_EUNSUPPORTED (chip_class in mode 1: any pair that is not 8-bit; chip_planes in mode 1: any pair that is
 //      neither 8-bit nor scaled-integer; wide_class beyond R 15 in mode 0: a pair that is not 8-bit at an (ocw, R) the float wide kernel does
 //      not take; wide_planes beyond R 15: in mode 1 a radius beyond mimc3_wide_planes_max_radius(ocw), in mode 0 a scaled-integer pair
-//      beyond that radius at an (ocw, R) the float wide kernel does not take -- every other class as wide_class)
+//      beyond that radius at an (ocw, R) the float wide kernel does not take -- every other class as wide_class; wide_chip: none, in
+//      either mode)
 //   4. MIMC3_EINVAL again: a coarsest pyramid level smaller than a chip; a mode other than 0 or 1; forward-backward rows without d_fb.
 //      The _dev entries of the full searches have always made the last two with the arguments, under 1, and keep doing so: without
 //      images they answer a bad mode with MIMC3_EINVAL where their host entries and the pyramids answer MIMC3_ESTATE.
@@ -71,8 +72,9 @@ int search_check(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules)
     if (rules.any_ocw) {
         if (call.ocw < 1 || call.ocw > kFullChipMaxOcw) return fail(MIMC3_EINVAL, en + ": ocw must be in 1.." + std::to_string(kFullChipMaxOcw));
     } else if (!full_ocw_ok(call.ocw)) return fail(MIMC3_EINVAL, en + ": ocw must be one of 7, 15, 16, 30, 32, 40");
-    if (!rules.layer && (call.R < 1 || call.R > (rules.wide_class ? wide_u8_max_radius(call.ocw) : rules.wide ? wide_max_radius(call.ocw) : 15)))
-        return fail(MIMC3_EINVAL, en + (rules.wide_class ? ": R must be in 1..mimc3_wide_class_max_radius(ocw)"
+    if (!rules.layer && (call.R < 1 || call.R > (rules.wide_chip ? wide_chip_max_radius(call.ocw) : rules.wide_class ? wide_u8_max_radius(call.ocw) : rules.wide ? wide_max_radius(call.ocw) : 15)))
+        return fail(MIMC3_EINVAL, en + (rules.wide_chip ? ": R must be in 1..mimc3_wide_chip_max_radius(ocw)"
+                                        : rules.wide_class ? ": R must be in 1..mimc3_wide_class_max_radius(ocw)"
                                         : rules.wide     ? ": R must be in 1..mimc3_wide_max_radius(ocw)" : ": R must be in 1..15"));
     if (rules.pyramid && (call.levels < 1 || call.levels > 5)) return fail(MIMC3_EINVAL, en + ": levels must be in 1..5");
     if (!c->d_i0 || !c->d_i1) return fail(MIMC3_ESTATE, en + ": images not set");
@@ -168,8 +170,38 @@ bool pyramid_chip_kernel(PairClass cls, int32_t ocw, int32_t mode, SearchKernel 
     return true;
 }
 
+// The kernel of mimc3_match_ncc_wide_chip (the table in include/mimc3_hip.h).  R <= 15: mode 1 the run-time-ocw float kernel
+// (mimc3_match_ncc_full_chip), mode 0 what mimc3_match_ncc_full_chip_planes(mode 0) runs.  R >= 16: mode 1 the run-time-ocw wide float
+// kernel; mode 0 the sibling that takes the call -- an 8-bit pair where mimc3_match_ncc_wide_class(mode 0) sends it, a scaled-integer pair
+// within wide_u16_max_radius(ocw) where mimc3_match_ncc_wide_planes(mode 0) sends it, any other pair the templated wide float kernel at
+// the (ocw, R) it takes -- and the run-time-ocw wide float kernel everywhere else.  At the six chip sizes mode 0 keeps the templated
+// kernel: tools/wide_chip_time.py measures the two side by side, and nothing is moved before a series says so.
+bool wide_chip_kernel(PairClass cls, int32_t ocw, int32_t R, int32_t mode, SearchKernel &kernel)
+{
+    if (ocw < 1 || ocw > kFullChipMaxOcw || R < 1 || R > wide_chip_max_radius(ocw) || (mode != 0 && mode != 1)) return false;
+    if (R <= 15) {
+        static const SearchKernel built[4] = {Mx, U16, F32i, F32g};         // (in PairClass's order)
+        if (mode == 1) kernel = Chip;
+        else if (full_ocw_ok(ocw)) kernel = built[cls];
+        else kernel = cls == kU8 && chip_mode0(ChipU8, ocw) ? ChipU8 : cls == kScaledInt && chip_mode0(ChipU16, ocw) ? ChipU16 : Chip;
+        return true;
+    }
+    const bool takes = wide_float_takes(ocw, R);
+    if (mode == 1) kernel = WideChip;
+    else if (cls == kU8) kernel = wide_mode0(ocw, R) || !takes ? WideU8 : Wide;
+    else if (cls == kScaledInt && R <= wide_u16_max_radius(ocw)) kernel = wide_planes_mode0(ocw, R) || !takes ? WideU16 : Wide;
+    else kernel = takes && cls != kScaledInt ? Wide : WideChip;
+    return true;
+}
+
 int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, SearchKernel &kernel)
 {
+    if (rules.wide_chip) {              // (search_check has refused every ocw, R and mode outside the table)
+        PairClass cls = kFloat;
+        if (call.mode != 1) RC_TRY(pair_class(c, cls));
+        if (!wide_chip_kernel(cls, call.ocw, call.R, call.mode, kernel)) return fail(MIMC3_EINVAL, std::string(call.entry) + ": bad argument");
+        return 0;                       // (whichever kernel runs serves the surfaces)
+    }
     if (rules.pyramid_chip) {           // (search_check has refused every ocw and mode outside the table)
         PairClass cls;
         RC_TRY(pair_class(c, cls));
@@ -214,7 +246,7 @@ int pick_kernel(mimc3_ctx *c, const SearchCall &call, const SearchRules &rules, 
 LevelClass level_class(SearchKernel kernel)
 {
     static const LevelClass of[kSearchKernels] = {kLevelU8, kLevelU16, kLevelF32i, kLevelFloat, kLevelFloat, kLevelFloat,
-                                                  kLevelU8, kLevelU16, kLevelU8, kLevelU16};     // (in SearchKernel's order)
+                                                  kLevelU8, kLevelU16, kLevelU8, kLevelU16, kLevelFloat};     // (in SearchKernel's order)
     return of[kernel];
 }
 // the level set of a pair's class (in PairClass's order)
@@ -345,7 +377,7 @@ int plane_set(mimc3_ctx *c, SearchKernel kernel, LevelClass lc, int level, Plane
 }
 
 // the kernels that run as a clean launch plus a masked launch in flag mode: one class byte per point (in SearchKernel's order)
-static const bool kKernelFlags[kSearchKernels] = {true, false, false, false, false, false, true, true, true, true};
+static const bool kKernelFlags[kSearchKernels] = {true, false, false, false, false, false, true, true, true, true, false};
 
 // One search launch: `kernel` over the call's points on `planes`, with the timing events around it (unless suspended) and last_path.
 int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const SearchCall &call)
@@ -353,7 +385,7 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
     static const char *const what[] = {"full-search kernel launch", "full-search u16 kernel launch", "full-search f32 kernel launch",
                                        "full-search general f32 kernel launch", "wide-search kernel launch", "full-search any-chip kernel launch",
                                        "full-search any-chip u8 kernel launch", "full-search any-chip u16 kernel launch", "wide-search u8 kernel launch",
-                                       "wide-search u16 kernel launch"};
+                                       "wide-search u16 kernel launch", "wide-search any-chip kernel launch"};
     hipStream_t s = call.stream;
     MatchU8Args u = u8_args(c, call.d_xyuvav, call.xy_stride, call.xy_col, call.N, call.off_u, call.off_v, call.ocw, call.swap, call.d_out);
     u.H = pl.H; u.W = pl.W; u.Wp = pl.Wp;
@@ -409,6 +441,7 @@ int launch_search(mimc3_ctx *c, SearchKernel kernel, const PlaneSet &pl, const S
     else if (kernel == F32i) e = launch_match_full_f32(u, s);
     else if (kernel == F32g) e = launch_match_full_f32g(u, call.d_surf, s);
     else if (kernel == Chip) e = launch_match_full_chip(u, call.d_surf, s);
+    else if (kernel == WideChip) e = launch_match_wide_chip(u, call.d_surf, s);
     else e = launch_match_wide(u, call.d_surf, s);
     if (e != hipSuccess) return hip_fail(e, what[kernel]);
     c->last_path = 6 + (int)kernel;
@@ -435,6 +468,7 @@ static const SearchRules kPyramid = {kU8, false, false, kCandAbsent, false, true
 static const SearchRules kPyramidDn = {kIntegralF32, false, false, kCandOptional, false, true};
 static const SearchRules kPyramidAny = {kFloat, true, false, kCandOptional, false, true};
 static const SearchRules kPyramidChip = {kFloat, true, false, kCandOptional, false, true, false, false, true, false, false, false, false, true};   // (pyramid, any_ocw, pyramid_chip)
+static const SearchRules kWideChip = {kFloat, true, false, kCandOptional, false, false, false, false, true, false, false, false, false, false, true};   // (any_ocw, wide_chip)
 
 // the description of a _dev entry's call (`levels`, d_fb: the entries that have them set them)
 static SearchCall dev_call(const char *entry, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v, const int32_t *d_shift,
@@ -834,6 +868,37 @@ extern "C" int mimc3_match_ncc_wide_planes(mimc3_ctx *c, const double *xyuvav, i
                                            float *surf)
 {
     return search_host(c, kWidePlanes, "mimc3_match_ncc_wide_planes", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
+}
+
+// ... and beyond +-15 px on ANY pair at every chip size (match_wide_chip_kernel.hip): mode 1 is mimc3_match_ncc_full_any's definition on the
+// run-time-ocw kernels (R <= 15 IS mimc3_match_ncc_full_chip(mode 1)); mode 0 runs the sibling that takes the call (wide_chip_kernel)
+extern "C" int mimc3_wide_chip_max_radius(int32_t ocw) { return wide_chip_max_radius(ocw); }
+extern "C" int mimc3_wide_chip_layout(int32_t ocw, int32_t R, int32_t out[5])
+{
+    int l[5];
+    if (!out || !wide_chip_layout_query(ocw, R, l)) return 0;
+    for (int i = 0; i < 5; i++) out[i] = l[i];
+    return 1;
+}
+// the last_path of that entry for a pair class (0 8-bit, 1 scaled-integer, 2 integral f32, 3 any other), chip size, radius and mode; -1 outside the table
+extern "C" int mimc3_wide_chip_path(int32_t pair_class, int32_t ocw, int32_t R, int32_t mode)
+{
+    SearchKernel kernel;
+    if (pair_class < 0 || pair_class > 3 || !wide_chip_kernel(static_cast<PairClass>(pair_class), ocw, R, mode, kernel)) return -1;
+    return 6 + (int)kernel;
+}
+extern "C" int mimc3_match_ncc_wide_chip_dev(mimc3_ctx *c, const double *d_xyuvav, int32_t N, int32_t off_u, int32_t off_v,
+                                             const int32_t *d_shift, int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode,
+                                             float *d_out, float *d_cand, float *d_surf, void *stream)
+{
+    return search_dev(c, dev_call("mimc3_match_ncc_wide_chip_dev", d_xyuvav, N, off_u, off_v, d_shift, ocw, R, npeaks, swap, mode, d_out, d_cand, d_surf, stream),
+                      kWideChip);
+}
+extern "C" int mimc3_match_ncc_wide_chip(mimc3_ctx *c, const double *xyuvav, int32_t N, const int32_t offset[2], const int32_t *shift,
+                                         int32_t ocw, int32_t R, int32_t npeaks, int32_t swap, int32_t mode, float *out, float *cand,
+                                         float *surf)
+{
+    return search_host(c, kWideChip, "mimc3_match_ncc_wide_chip", xyuvav, N, offset, shift, ocw, R, 0, npeaks, swap, mode, out, cand, surf, nullptr, nullptr);
 }
 
 // ... and with forward-backward consistency
